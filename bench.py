@@ -3,6 +3,7 @@
 bench.py -- the hot path's headline metric on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--config 4|5]
+                    [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): Mcells/s of SinkFill (to convergence) + D8FlowDirection
 on a 16384^2 float32 DEM, inputs resident in HBM when the timed region starts,
@@ -19,7 +20,19 @@ starts its N ranks itself, as fresh child processes, before anything touches a G
 HDEM_REHEARSE=1 puts every rank on cuda:0 over gloo: the N > 1 code path on a one-GPU
 box, never a performance number.
 
-One JSON line on stdout (rank 0) with, besides the contract keys:
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times the K steps and
+prints the contract keys (metric, value, unit, higher_is_better, dtype, ms_per_step) with
+the workload (`config`: tile visits etc. of the last step, returned by the step itself).
+
+--dump-outputs DIR: after the timed steps, what the last step returned -- the filled
+raster and the D8 codes -- as DIR/filled.npy and DIR/d8.npy, float32 (the uint8 codes are
+exact in it).  Rasters of up to DUMP_CELLS cells are written whole (H x W); larger ones at
+the same seeded sample of DUMP_CELLS distinct flat cell indices, ascending (dump_index()):
+32 MB in all.  The inputs are seeded (hdem_synth), so two builds compare output for output.
+N > 1: the ranks' owned rows, gathered on rank 0 in global row order.
+
+--full adds, besides the contract keys (the timed steps then run with the library's
+HIP-event brackets around every launch, and the extras run after them):
   roofline      dominant kernel = fill_async_kernel (the sink-fill tile relaxation):
                   achieved     visit bytes / its HIP-event time over the timed steps: 12 B per
                                cell of a visit that writes its tile back (Z in, W in, W out),
@@ -36,8 +49,11 @@ One JSON line on stdout (rank 0) with, besides the contract keys:
   filters       the other operators of the scope table on the same raster (outside the timed
                 region), with the NumPy / SciPy oracle timed beside them on a crop (CPU-B)
   config2       BASELINE configs[1]: the same step at 4096^2
+  config1_raster, batch_of_tiles   the step on the reference's 519 x 508 DEM; sixteen
+                1201^2 tiles one call each against one canvas call
   cpu_baseline  the C priority-flood oracle + C D8 on the FULL workload raster, one core;
                 the NumPy Jacobi oracle on a crop beside it (size-dependent, context only).
+  per_rank      N > 1: every rank's kernel times and visits over the timed steps.
 """
 import argparse
 import hashlib
@@ -60,6 +76,8 @@ FLOOR_BYTES_PER_CELL = 8    # a whole fill: read Z once, write W once (SURVEY 8d
 FILL_KERNEL = "fill_async_kernel<false, 0>"
 TRAFFIC_RECORD = os.path.join(ROOT, "profiles", "r03_fill_traffic.json")
 FILL_SOURCES = ("hydrodem_amd/csrc/hdem_sinkfill.hip", "hydrodem_amd/csrc/hdem_internal.h")
+DUMP_CELLS = 1 << 22        # --dump-outputs: whole rasters up to this many cells, else a sample
+DUMP_SEED = 20240607        # of this many: 2 x 16 MB of float32
 
 
 def parse():
@@ -72,9 +90,15 @@ def parse():
                    help="BASELINE configs[3] / configs[4]: 32768^2 on 4 GPUs, 65536^2 on 8 "
                         "(sets the raster; --gpus defaults to the configuration's)")
     p.add_argument("--cpu-sample", type=int, default=1024,
-                   help="edge of the crop the NumPy Jacobi oracle is timed on (0 = no CPU lines)")
+                   help="with --full: edge of the crop the NumPy Jacobi oracle is timed on "
+                        "(0 = no CPU lines)")
     p.add_argument("--no-filters", action="store_true",
-                   help="skip the untimed extras (filters, config2)")
+                   help="with --full: skip the untimed extras (filters, config2)")
+    p.add_argument("--full", action="store_true",
+                   help="also the roofline, per-kernel and per-rank figures, the filter paths, "
+                        "the other configurations and the CPU baselines (off: the headline only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -156,6 +180,22 @@ def profiled_traffic(size):
         meta["traffic_note"] = f"PMC record is of size {rec.get('size')}"
         return None, meta
     return rec["bytes_per_launch"], meta
+
+
+def dump_index(cells):
+    """Flat indices of the cells --dump-outputs writes: None (all of them) up to DUMP_CELLS,
+    else the same seeded sample of DUMP_CELLS distinct indices, ascending, whatever the build."""
+    if cells <= DUMP_CELLS:
+        return None
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.sort(rng.choice(cells, DUMP_CELLS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, filled, codes):
+    """The last timed step's results (whole or sampled by dump_index) as float32 .npy files."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "filled.npy"), np.ascontiguousarray(filled, dtype=np.float32))
+    np.save(os.path.join(path, "d8.npy"), np.ascontiguousarray(codes, dtype=np.float32))
 
 
 def roofs(gbs, copy_gbs):
@@ -497,8 +537,9 @@ def main():
     for _ in range(a.warmup):
         step()
     del step_stats[:]
-    ctx.profile(True)
-    ctx.profile_reset()
+    if a.full:
+        ctx.profile(True)
+        ctx.profile_reset()
     sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
@@ -506,16 +547,41 @@ def main():
     sync()
     elapsed = reduce_max(time.perf_counter() - t0)
 
-    kt = ctx.profile_get(B.K_FILL_TILE)
-    kc = ctx.profile_get(B.K_FILL_COARSE)
-    kb = ctx.profile_get(B.K_BLOCKMAX)
-    kr = ctx.profile_get(B.K_FILL_ROUND)
-    ki = ctx.profile_get(B.K_FILL_INIT)
-    kh = ctx.profile_get(B.K_FILL_HUB)
-    ctx.profile(False)
+    if a.full:
+        kt = ctx.profile_get(B.K_FILL_TILE)
+        kc = ctx.profile_get(B.K_FILL_COARSE)
+        kb = ctx.profile_get(B.K_BLOCKMAX)
+        kr = ctx.profile_get(B.K_FILL_ROUND)
+        ki = ctx.profile_get(B.K_FILL_INIT)
+        kh = ctx.profile_get(B.K_FILL_HUB)
+        ctx.profile(False)
     last = step_stats[-1]
+    if a.dump_outputs:
+        # before the extras of --full: they reuse the output rasters as scratch
+        if N == 1:
+            w_all, d_all = wd.to_host(), dd.to_host()
+            idx = dump_index(w_all.size)
+            if idx is not None:
+                w_all, d_all = w_all.ravel()[idx], d_all.ravel()[idx]
+            dump_outputs(a.dump_outputs, w_all, d_all)
+            del w_all, d_all
+        else:
+            r0, r1 = P.row_range(rank, world, H)
+            lo = r0 - g0
+            w_own = wt[lo:lo + r1 - r0].cpu().numpy()
+            d_own = dt_[lo:lo + r1 - r0].cpu().numpy()
+            idx = dump_index(H * Wd)
+            if idx is not None:
+                sel = idx[(idx >= r0 * Wd) & (idx < r1 * Wd)] - r0 * Wd
+                w_own, d_own = w_own.ravel()[sel], d_own.ravel()[sel]
+            parts = [None] * world
+            dist.all_gather_object(parts, (w_own, d_own))
+            if rank == 0:
+                dump_outputs(a.dump_outputs, np.concatenate([p[0] for p in parts]),
+                             np.concatenate([p[1] for p in parts]))
+            del parts, w_own, d_own
     per_rank = None
-    if N > 1:
+    if N > 1 and a.full:
         # every rank's share of the step, gathered after the timed region
         mine = torch.tensor([kt["ms"], kc["ms"] + kb["ms"] + kh["ms"], kr["ms"], ki["ms"],
                              float(sum(s["tile_visits"] for s in step_stats)),
@@ -547,44 +613,9 @@ def main():
                     "shared_gpu_solves": [int(p[9]) for p in parts]}
 
     if rank == 0:
-        copy_gbs = B.copy_rate(ctx)
         cells_total = H * Wd
         ms_per_step = elapsed / a.steps * 1e3
-        # rank 0's fill launches: cells of all window visits (profile units; visits of flat
-        # tiles read ~500 cells and are not in them), of which the unchanged ones skipped the
-        # write-back
-        ft2 = 62 * 62
-        unchanged_cells = sum(s["visits_unchanged"] - s.get("flat_unchanged", 0)
-                              for s in step_stats) * ft2
-        visit_bytes = VISIT_BYTES_WRITING * kt["units"] - \
-            (VISIT_BYTES_WRITING - VISIT_BYTES_UNCHANGED) * min(unchanged_cells, kt["units"])
-        fill_gbs = visit_bytes / max(kt["ms"], 1e-9) / 1e6
-        launches = max(kt["launches"], 1)
-        traffic, traffic_meta = profiled_traffic(S) if N == 1 else (None, {})
-        useful_gbs = FLOOR_BYTES_PER_CELL * cells_total / N / ms_per_step / 1e6   # per GPU
-        roofline = {"bound": "hbm", "kernel": FILL_KERNEL, "peak": HBM_PEAK_GBS}
-        roofline.update(roofs(fill_gbs, copy_gbs))
-        roofline.update({
-            "copy_rate_measured": copy_gbs,
-            "useful_frac": useful_gbs / HBM_PEAK_GBS,
-            "useful_frac_of_copy": useful_gbs / copy_gbs,
-            "end_to_end_bytes_over_floor": (visit_bytes / a.steps + 17.0 * cells_total / N)
-                                           / (FLOOR_BYTES_PER_CELL * cells_total / N),
-            "traffic": traffic,
-            "counter_to_algorithmic": traffic / (visit_bytes / launches) if traffic else None,
-            "launches": kt["launches"], "ms_total": kt["ms"],
-            "bytes_per_launch": visit_bytes / launches,
-            "avg_launch_ms": kt["ms"] / launches,
-            "note": "rank 0.  achieved/frac: algorithmic bytes of the tile visits (12 B per cell "
-                    "of a writing visit, 8 B of an unchanged one) over the kernel's HIP-event "
-                    "time; useful_frac: 8 B per raster cell over the whole step.  "
-                    "end_to_end_bytes_over_floor adds the start values (hub start: Z in, d out, "
-                    "8 B/cell) and the certifying pass (9 B/cell)"})
-        roofline.update(traffic_meta)
-        certify_gbs = 9 * kr["units"] / max(kr["ms"], 1e-9) / 1e6
-        init_gbs = 8 * ki["units"] / max(ki["ms"], 1e-9) / 1e6
         size_name = f"{S}^2" if N == 1 else f"{H}x{Wd}"
-        hub_gbs = 8 * kh["units"] / max(kh["ms"], 1e-9) / 1e6
         named = {4: "BASELINE configs[3]: 32768x32768 DEM, row-block decomposed, 4 GPUs",
                  5: "BASELINE configs[4]: 65536x65536 mosaic, 8 GPUs"}.get(a.config)
         out = {
@@ -612,42 +643,78 @@ def main():
                        "certifying_rounds": last.get("rounds", 0),
                        "halo_exchanges": last.get("exchanges", 0),
                        "verifications": last.get("verifications")},
-            "roofline": roofline,
-            "kernels": {"certify_d8_kernel": dict(
-                            roofs(certify_gbs, copy_gbs), launches=kr["launches"],
-                            ms_total=kr["ms"], algorithmic_bytes_per_cell=9,
-                            note="certifying pass behind the asynchronous launch, one stream "
-                                 "over the raster: reads Z and W, writes the D8 codes; rounds of "
-                                 "tile visits (fill_round_kernel) only if it finds a cell to "
-                                 "lower -- then they are counted here too"),
-                        "fill_init_kernel": dict(
-                            roofs(init_gbs, copy_gbs), algorithmic_bytes_per_cell=8,
-                            ms_per_step=ki["ms"] / a.steps,
-                            note="start values of the fine raster (and of the coarse one: two "
-                                 "launches per step)"),
-                        "hub_dist_kernel": dict(
-                            roofs(hub_gbs, copy_gbs), algorithmic_bytes_per_cell=8,
-                            ms_per_step=kh["ms"] / a.steps,
-                            note="hub start: per tile the minimax path cost of every cell to "
-                                 "the tile's hub (Z in, d out) + the crossings between hubs; "
-                                 "three rounds of directional scans per tile; waits on its loads and stores (its time does not depend on the number of rounds), tiles in XCD-aware order"),
-                        "start_raster_solve": {
-                            "blockmax_avg_launch_ms": kb["ms"] / max(kb["launches"], 1),
-                            "fill_async_kernel<false, 1>_avg_launch_ms":
-                                kc["ms"] / max(kc["launches"], 1),
-                            "note": "fill of the hub raster (one node per 62x62 tile and the "
-                                    "crossings between them, 1/930 of the cells; N > 1: of the "
-                                    "16x16 block maxima): latency-bound"}},
         }
-        if per_rank:
-            out["per_rank"] = per_rank
-        if N == 1 and not a.no_filters:
-            out["filters"] = filter_paths(B, ctx, zd, wd, S, copy_gbs, bool(a.cpu_sample))
-            out["config2"] = config2(B, ctx)
-            out["config1_raster"] = config1(B, ctx)
-            out["batch_of_tiles"] = batch_line(B, ctx)
-        if a.cpu_sample and N == 1:
-            out["cpu_baseline"] = cpu_baseline(z, a.cpu_sample)
+        if a.full:
+            copy_gbs = B.copy_rate(ctx)
+            # rank 0's fill launches: cells of all window visits (profile units; visits of flat
+            # tiles read ~500 cells and are not in them), of which the unchanged ones skipped the
+            # write-back
+            ft2 = 62 * 62
+            unchanged_cells = sum(s["visits_unchanged"] - s.get("flat_unchanged", 0)
+                                  for s in step_stats) * ft2
+            visit_bytes = VISIT_BYTES_WRITING * kt["units"] - \
+                (VISIT_BYTES_WRITING - VISIT_BYTES_UNCHANGED) * min(unchanged_cells, kt["units"])
+            fill_gbs = visit_bytes / max(kt["ms"], 1e-9) / 1e6
+            launches = max(kt["launches"], 1)
+            traffic, traffic_meta = profiled_traffic(S) if N == 1 else (None, {})
+            useful_gbs = FLOOR_BYTES_PER_CELL * cells_total / N / ms_per_step / 1e6   # per GPU
+            roofline = {"bound": "hbm", "kernel": FILL_KERNEL, "peak": HBM_PEAK_GBS}
+            roofline.update(roofs(fill_gbs, copy_gbs))
+            roofline.update({
+                "copy_rate_measured": copy_gbs,
+                "useful_frac": useful_gbs / HBM_PEAK_GBS,
+                "useful_frac_of_copy": useful_gbs / copy_gbs,
+                "end_to_end_bytes_over_floor": (visit_bytes / a.steps + 17.0 * cells_total / N)
+                                               / (FLOOR_BYTES_PER_CELL * cells_total / N),
+                "traffic": traffic,
+                "counter_to_algorithmic": traffic / (visit_bytes / launches) if traffic else None,
+                "launches": kt["launches"], "ms_total": kt["ms"],
+                "bytes_per_launch": visit_bytes / launches,
+                "avg_launch_ms": kt["ms"] / launches,
+                "note": "rank 0.  achieved/frac: algorithmic bytes of the tile visits (12 B per cell "
+                        "of a writing visit, 8 B of an unchanged one) over the kernel's HIP-event "
+                        "time; useful_frac: 8 B per raster cell over the whole step.  "
+                        "end_to_end_bytes_over_floor adds the start values (hub start: Z in, d out, "
+                        "8 B/cell) and the certifying pass (9 B/cell)"})
+            roofline.update(traffic_meta)
+            certify_gbs = 9 * kr["units"] / max(kr["ms"], 1e-9) / 1e6
+            init_gbs = 8 * ki["units"] / max(ki["ms"], 1e-9) / 1e6
+            hub_gbs = 8 * kh["units"] / max(kh["ms"], 1e-9) / 1e6
+            out["roofline"] = roofline
+            out["kernels"] = {"certify_d8_kernel": dict(
+                                  roofs(certify_gbs, copy_gbs), launches=kr["launches"],
+                                  ms_total=kr["ms"], algorithmic_bytes_per_cell=9,
+                                  note="certifying pass behind the asynchronous launch, one stream "
+                                       "over the raster: reads Z and W, writes the D8 codes; rounds of "
+                                       "tile visits (fill_round_kernel) only if it finds a cell to "
+                                       "lower -- then they are counted here too"),
+                              "fill_init_kernel": dict(
+                                  roofs(init_gbs, copy_gbs), algorithmic_bytes_per_cell=8,
+                                  ms_per_step=ki["ms"] / a.steps,
+                                  note="start values of the fine raster (and of the coarse one: two "
+                                       "launches per step)"),
+                              "hub_dist_kernel": dict(
+                                  roofs(hub_gbs, copy_gbs), algorithmic_bytes_per_cell=8,
+                                  ms_per_step=kh["ms"] / a.steps,
+                                  note="hub start: per tile the minimax path cost of every cell to "
+                                       "the tile's hub (Z in, d out) + the crossings between hubs; "
+                                       "three rounds of directional scans per tile; waits on its loads and stores (its time does not depend on the number of rounds), tiles in XCD-aware order"),
+                              "start_raster_solve": {
+                                  "blockmax_avg_launch_ms": kb["ms"] / max(kb["launches"], 1),
+                                  "fill_async_kernel<false, 1>_avg_launch_ms":
+                                      kc["ms"] / max(kc["launches"], 1),
+                                  "note": "fill of the hub raster (one node per 62x62 tile and the "
+                                          "crossings between them, 1/930 of the cells; N > 1: of the "
+                                          "16x16 block maxima): latency-bound"}}
+            if per_rank:
+                out["per_rank"] = per_rank
+            if N == 1 and not a.no_filters:
+                out["filters"] = filter_paths(B, ctx, zd, wd, S, copy_gbs, bool(a.cpu_sample))
+                out["config2"] = config2(B, ctx)
+                out["config1_raster"] = config1(B, ctx)
+                out["batch_of_tiles"] = batch_line(B, ctx)
+            if a.cpu_sample and N == 1:
+                out["cpu_baseline"] = cpu_baseline(z, a.cpu_sample)
         print(json.dumps(out), flush=True)
     if N > 1:
         dist.barrier()

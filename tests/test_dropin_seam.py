@@ -101,70 +101,98 @@ def test_custom_filters_namespace_covers_the_reference_module():
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
 
 
-REF_TESTS = "/root/reference/cguerrero/tests"
+SLIDING_SMALL = os.path.join(ROOT, "tests", "golden", "sliding_small.npz")
+
+# what the checks below share: build a case of tests/golden/sliding_small.npz with the
+# classes the import statement of the caller bound (``classes``)
+_CASE_HELPERS = f"""
+import json
+import numpy as np
+from numpy import testing
+g = np.load({SLIDING_SMALL!r})
+cases = {{c["name"]: c for c in json.loads(str(g["cases"]))}}
+
+def make(name):
+    c = cases[name]
+    grid = np.arange(c["rows"] * c["cols"]).reshape((c["rows"], c["cols"]))
+    kw = {{"window_size": c["window_size"]}}
+    if c["inner_size"]:
+        kw["inner_size"] = c["inner_size"]
+    return classes[c["class"]](grid, **kw)
+"""
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_TESTS, "test_sliding_window.py")),
-                    reason="the reference tree is only present in the build container")
 def test_the_references_own_sliding_window_tests_behave_the_same_against_the_dropin():
-    """`cguerrero/tests/test_sliding_window.py` -- the reference's own 16 test methods with
-    their known-answer literals (`tests/constants.py`) -- run unmodified, in fresh
-    interpreters, once against the reference tree and once with `dropin/` first on `sys.path`
-    (its `from cguerrero.hydrodem.sliding_window import ...` then binds this package's
-    classes): the same tests pass and the same tests fail.  (With NumPy 2 two of the
-    reference's tests raise on its own code -- `array == array` of different shapes -- and do
-    the same here.  Runs where the reference tree is; the committed goldens of
-    tests/test_sliding_window.py carry the same windows to the GPU box.)"""
-    body = f"""
-        import unittest
-        sys.path.append({REF_TESTS!r})                 # `from constants import ...`
-        sys.dont_write_bytecode = True
-        import test_sliding_window as t
-        print('BOUND', t.SlidingWindow.__module__)
-        suite = unittest.defaultTestLoader.loadTestsFromModule(t)
-        result = unittest.TextTestRunner(verbosity=0, stream=open(os.devnull, 'w')).run(suite)
-        bad = sorted(str(test).split()[0] for test, _ in result.failures + result.errors)
-        print('RAN', result.testsRun, 'BAD', ','.join(bad))
+    """The known answers of the reference's `cguerrero/tests/test_sliding_window.py` -- the
+    literals of its `tests/constants.py`, committed as data with the case and position each
+    is checked at (tests/golden/sliding_small.npz, tests/golden/make_golden_sliding_small.py)
+    -- hold for the classes its import statement `from cguerrero.hydrodem.sliding_window
+    import ...` binds in a fresh interpreter with `dropin/` first on `sys.path`: the windows
+    and centres of the iterations over 4 x 4, 3 x 3, 3 x 4, 6 x 6 and 9 x 9 grids and the
+    __getitem__ windows, NaN positions included."""
+    code = """
+        from cguerrero.hydrodem.sliding_window import (SlidingWindow, InnerWindow,
+                                                       SlidingIgnoreBorder, CircularWindow,
+                                                       NoCenterWindow, IgnoreBorderInnerSliding)
+        classes = {c.__name__: c for c in (SlidingWindow, InnerWindow, SlidingIgnoreBorder,
+                                           CircularWindow, NoCenterWindow,
+                                           IgnoreBorderInnerSliding)}
+        assert all(c.__module__ == 'hydrodem_amd.sliding_window' for c in classes.values())
         """
-    mine = run("import os\n" + textwrap.dedent(body))
-    ref_head = ("import sys, os\nsys.path[:0] = ['/root/reference', "
-                "'/root/reference/cguerrero/hydrodem']\n")
-    theirs = subprocess.run([sys.executable, "-c", ref_head + textwrap.dedent(body)],
-                            capture_output=True, text=True, cwd="/")
-    assert mine.returncode == 0 and theirs.returncode == 0, mine.stderr + theirs.stderr
-    pick = lambda out, key: [ln for ln in out.stdout.splitlines() if ln.startswith(key)][0]
-    assert pick(mine, "BOUND") == "BOUND hydrodem_amd.sliding_window"
-    assert pick(theirs, "BOUND") == "BOUND cguerrero.hydrodem.sliding_window"
-    assert pick(mine, "RAN") == pick(theirs, "RAN")
-    ran, bad = pick(mine, "RAN").split(" BAD ")
-    assert ran == "RAN 16" and len([b for b in bad.split(",") if b]) <= 2
-
-
-REF_SLIDING = "/root/reference/cguerrero/hydrodem/sliding_window.py"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_SLIDING),
-                    reason="the reference tree is only present in the build container")
-def test_the_88_doctest_examples_of_the_references_sliding_window_hold_for_the_dropin():
-    """The known-answer literals of SURVEY 8c: every `>>>` example in the docstrings of the
-    reference's `sliding_window.py` (read as text, not imported), executed with `dropin/`
-    first on `sys.path` -- `from sliding_window import SlidingWindow` in the examples binds
-    this package's class -- prints exactly what the docstring says."""
-    code = f"""
-        import ast, doctest, io
-        tree = ast.parse(open({REF_SLIDING!r}).read())
-        docs = [(getattr(n, 'name', 'module'), ast.get_docstring(n, clean=False))
-                for n in ast.walk(tree) if isinstance(n, (ast.Module, ast.ClassDef, ast.FunctionDef))]
-        runner = doctest.DocTestRunner(verbose=False,
-                                       optionflags=doctest.NORMALIZE_WHITESPACE | doctest.ELLIPSIS)
-        sink = io.StringIO()
-        for name, doc in docs:
-            if doc and '>>>' in doc:
-                runner.run(doctest.DocTestParser().get_doctest(doc, {{}}, name, None, 0), out=sink.write)
-        import sliding_window
-        assert sliding_window.SlidingWindow.__module__ == 'hydrodem_amd.sliding_window'
-        print(runner.tries, runner.failures)
-        assert runner.tries == 88 and runner.failures == 0, sink.getvalue()[-3000:]
-        """
+    code = textwrap.dedent(code) + _CASE_HELPERS + textwrap.dedent("""
+        known = json.loads(str(g["known"]))
+        for k in known:
+            sliding = make(k["case"])
+            if k["position"] is not None:
+                testing.assert_array_equal(sliding[tuple(k["position"])], g["known_" + k["const"]],
+                                           err_msg=k["const"])
+                continue
+            got = list(sliding)
+            want_w = g["known_" + k["const"] + "_windows"]
+            first = k.get("nth", 0)
+            got = got[first:first + len(want_w)]
+            assert len(got) == len(want_w), k["const"]
+            for (win, centre), w, c in zip(got, want_w, g["known_" + k["const"] + "_centres"]):
+                testing.assert_array_equal(win, w, err_msg=k["const"])
+                if "nth" not in k:
+                    assert tuple(centre) == tuple(c), (k["const"], centre, c)
+        print('checked', len(known))
+        """)
     out = run(code)
     assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stdout.split() == ["checked", "24"]
+
+
+def test_the_88_doctest_examples_of_the_references_sliding_window_hold_for_the_dropin():
+    """The results the docstring examples of the reference's `sliding_window.py` show --
+    for each class the first windows of `iter(sliding)` on its first grid, every window of
+    the loop over its `grid_2` (3 x 3, 3 x 4, 4 x 4, 6 x 6) and `sliding[1, 1]`,
+    `sliding[3, 3]`, `sliding[1, 3]` -- recorded from the reference as data
+    (tests/golden/sliding_small.npz), hold for the classes the examples' own
+    `from sliding_window import ...` binds with `dropin/` first on `sys.path`."""
+    code = """
+        import sliding_window
+        from sliding_window import (SlidingWindow, SlidingIgnoreBorder, CircularWindow,
+                                    InnerWindow, NoCenterWindow, IgnoreBorderInnerSliding)
+        assert sliding_window.SlidingWindow.__module__ == 'hydrodem_amd.sliding_window'
+        classes = {c.__name__: c for c in (SlidingWindow, SlidingIgnoreBorder, CircularWindow,
+                                           InnerWindow, NoCenterWindow,
+                                           IgnoreBorderInnerSliding)}
+        """
+    code = textwrap.dedent(code) + _CASE_HELPERS + textwrap.dedent("""
+        names = json.loads(str(g["doctest_cases"]))
+        for name in names:
+            got = list(make(name))
+            assert len(got) == len(g[name + "_windows"]), name
+            for (win, centre), w, c in zip(got, g[name + "_windows"], g[name + "_centres"]):
+                testing.assert_array_equal(win, w, err_msg=name)
+                assert tuple(centre) == tuple(c), (name, centre, c)
+        s = make("SlidingWindow_5x5_3")
+        pos = [tuple(p) for p in cases["SlidingWindow_5x5_3"]["positions"]]
+        for p in [(1, 1), (3, 3), (1, 3)]:
+            testing.assert_array_equal(s[p], g["SlidingWindow_5x5_3_getitem"][pos.index(p)])
+        print('checked', len(names))
+        """)
+    out = run(code)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stdout.split() == ["checked", "11"]

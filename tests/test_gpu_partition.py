@@ -81,30 +81,51 @@ def test_two_rank_rehearsal_on_one_gpu(tmp_path, built, world, H, W):
                           backend.boxmean3_dev(backend.DeviceRaster.from_host(got_g)).to_host())
 
 
-def test_bench_starts_its_own_ranks(built):
+def test_bench_starts_its_own_ranks(built, tmp_path):
     """`python bench.py --gpus 2` with no launcher around it -- the shape of command the
     driver issues -- spawns its ranks itself (here both on cuda:0 over gloo:
-    HDEM_REHEARSE=1) and prints rank 0's one JSON line with the per-rank detail."""
+    HDEM_REHEARSE=1) and prints rank 0's one JSON line: with --full, with the per-rank
+    detail; plain, the headline only, and --dump-outputs gathers the ranks' sampled rows
+    on rank 0."""
     import json
     import subprocess
     import sys
+    import bench
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HDEM_REHEARSE"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--size",
-                          "2048", "--steps", "2", "--warmup", "1"], env=env, capture_output=True,
-                         text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
-    assert len(lines) == 1
-    rec = json.loads(lines[0])
-    assert rec["n_gpus"] == 2 and rec["scaling"] == "weak" and rec["value"] > 0
-    assert rec["metric"].endswith("4096x2048 float32 DEM")
-    assert rec["config"]["halo_exchanges"] >= 2 and rec["config"]["tiles"] > 0
-    assert rec["config"]["visits_unchanged"] is not None
+
+    def bench_line(*extra):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
+                              "--size", "2048", "--steps", "2", "--warmup", "1", *extra],
+                             env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec["n_gpus"] == 2 and rec["scaling"] == "weak" and rec["value"] > 0
+        assert rec["metric"].endswith("4096x2048 float32 DEM")
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert rec["config"]["halo_exchanges"] >= 2 and rec["config"]["tiles"] > 0
+        assert rec["config"]["visits_unchanged"] is not None
+        return rec
+
+    rec = bench_line("--full")
     assert len(rec["per_rank"]["fill_async_ms_per_step"]) == 2
     assert all(v > 0 for v in rec["per_rank"]["tile_visits_per_step"])
+    dump = tmp_path / "outputs"
+    rec = bench_line("--dump-outputs", str(dump))
+    for key in ("per_rank", "roofline", "kernels"):
+        assert key not in rec
+    # the 4096 x 2048 raster is sampled: the same cells as the unpartitioned oracle's
+    z = oracle.synth_dem(4096, 2048)
+    want = c_oracle.sinkfill_pflood(z)
+    idx = bench.dump_index(z.size)
+    assert idx is not None
+    assert np.array_equal(np.load(dump / "filled.npy"), want.ravel()[idx])
+    assert np.array_equal(np.load(dump / "d8.npy"),
+                          c_oracle.d8(want).ravel()[idx].astype(np.float32))
     # a rank that dies takes the whole run down with a non-zero status
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--size",
                           "-5"], env=env, capture_output=True, text=True, timeout=600)

@@ -232,3 +232,19 @@ def test_bench_reports_pmc_traffic_only_for_the_kernel_it_was_taken_from(tmp_pat
         committed = json.load(open(bench.TRAFFIC_RECORD))
         assert committed["kernel_hash"] == bench.kernel_source_hash(), \
             "hdem_sinkfill.hip changed after the PMC passes: re-run tools/profile_round.sh"
+
+
+def test_bench_dump_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: whole rasters up to DUMP_CELLS, beyond it the same seeded sample of
+    distinct cells, ascending, every run and every build; the files stay under 64 MB in all."""
+    import bench
+    assert bench.dump_index(bench.DUMP_CELLS) is None
+    cells = 16384 * 16384
+    a, b = bench.dump_index(cells), bench.dump_index(cells)
+    assert np.array_equal(a, b) and a.size == bench.DUMP_CELLS
+    assert a[0] >= 0 and a[-1] < cells and np.all(np.diff(a) > 0)      # distinct, ascending
+    filled = np.arange(bench.DUMP_CELLS, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path), filled, filled.astype(np.uint8))
+    got = np.load(tmp_path / "d8.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, filled.astype(np.uint8))
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 << 20

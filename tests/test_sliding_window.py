@@ -5,6 +5,9 @@ window the reference's classes yield on `np.arange(81).reshape(9, 9)`
 examples of the reference's doctests (`sliding_window.py:221-245,750-793`) and
 its validation tests (`cguerrero/tests/test_sliding_window.py:35-133`).
 """
+import json
+import os
+
 import numpy as np
 import pytest
 from numpy import nan
@@ -49,6 +52,35 @@ def test_every_window_matches_the_reference(golden, name):
     # iterating twice gives the same windows (the mask is built once)
     again = list(sliding)
     np.testing.assert_array_equal(again[0][0], got[0][0])
+
+
+SMALL = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                             "sliding_small.npz"))
+SMALL_CASES = json.loads(str(SMALL["cases"]))
+
+
+@pytest.mark.parametrize("case", SMALL_CASES, ids=[c["name"] for c in SMALL_CASES])
+def test_small_grid_windows_match_the_reference(case):
+    """The grids of the reference's unit tests and docstring examples (3 x 3, 3 x 4, 4 x 4,
+    5 x 5, 6 x 6 and 9 x 9 aranges): every window and centre the reference yields, and its
+    __getitem__ at the positions its tests index and at every centre
+    (tests/golden/sliding_small.npz)."""
+    import hydrodem_amd.sliding_window as sw
+    grid = np.arange(case["rows"] * case["cols"]).reshape((case["rows"], case["cols"]))
+    kw = {"window_size": case["window_size"]}
+    if case["inner_size"]:
+        kw["inner_size"] = case["inner_size"]
+    sliding = getattr(sw, case["class"])(grid, **kw)
+    got = list(sliding)
+    want_w, want_c = SMALL[case["name"] + "_windows"], SMALL[case["name"] + "_centres"]
+    assert len(got) == len(want_w)
+    for (win, centre), w, c in zip(got, want_w, want_c):
+        np.testing.assert_array_equal(win, w)
+        assert tuple(centre) == tuple(c)
+    want_items = SMALL[case["name"] + "_getitem"]
+    assert len(case["positions"]) == len(want_items)
+    for pos, want in zip(case["positions"], want_items):
+        np.testing.assert_array_equal(sliding[tuple(pos)], want, err_msg=str(pos))
 
 
 def test_creation_attributes():

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/fstats" -o filters -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --cpu-sample 0 > "$OUT/filters_under_rocprof.json"
+rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/fstats" -o filters -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --full --cpu-sample 0 > "$OUT/filters_under_rocprof.json"
 cp "$(find "$OUT/fstats" -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_filters_kernel_stats.csv"
 : > "$OUT/${TAG}_groves_pmc_sq.csv"
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU" \

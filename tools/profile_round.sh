@@ -12,7 +12,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 10 --warmup 3 --no-filters --cpu-sample 0"
+BENCH="python3 $ROOT/bench.py --steps 10 --warmup 3 --full --no-filters --cpu-sample 0"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/stats" -o bench -- $BENCH > "$OUT/bench_under_rocprof.json"
 cp "$(find "$OUT/stats" -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_bench_kernel_stats.csv"
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -29,5 +29,5 @@ for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU" \
     python3 "$ROOT/tools/summarize_pmc.py" "$(find "$d" -name '*counter_collection.csv' | head -1)" \
         | grep -E "Kernel_Name|fill_async_kernel<false, 0>" >> "$OUT/${TAG}_fill_pmc_sq.csv"
 done
-python3 "$ROOT/bench.py" --steps 20 --warmup 5 > "$OUT/${TAG}_bench.json"
+python3 "$ROOT/bench.py" --steps 20 --warmup 5 --full > "$OUT/${TAG}_bench.json"
 ls -la "$OUT"
