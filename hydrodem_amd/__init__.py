@@ -21,7 +21,8 @@ from .filters import Filter, ComposedFilter, ComposedFilterResults  # noqa: F401
 from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F401
                                      GrovesCorrection, GrovesCorrectionsIter,
                                      PostProcessingFinal, SinkFill,
-                                     D8FlowDirection, HydroConditioning,
+                                     D8FlowDirection, FlowAccumulation,
+                                     HydroConditioning,
                                      ExpandFilter, IsolatedPoints, BlanksFourier,
                                      DetectBlanksFourier, MaskFourier, FourierInitial,
                                      FourierProcessQuarters, DetectApplyFourier,

@@ -30,6 +30,7 @@ K_D8, K_FILL_INIT, K_FILL_TILE, K_BOXMEAN, K_GROVES, K_CONVOLVE, K_COPY, K_FILL_
 K_BLOCKMAX, K_FFT, K_FOURIER_ROWSUM, K_FOURIER_DETECT, K_FOURIER_MASK, K_FOURIER_POINT = range(8, 14)
 K_LAGOON, K_MAJORITY, K_FILL_COARSE, K_FILL_FLAT, K_ELEMENTWISE = 14, 15, 16, 17, 18
 K_FILL_HUB = 19
+K_FLOWACC = 20
 
 # element-wise operators and raster types of hdem_elementwise_dev
 EW_MUL, EW_ADD, EW_RSUB, EW_GT, EW_LT, EW_NONZERO = range(6)
@@ -57,6 +58,16 @@ class FillStats(ctypes.Structure):
                 ("pending", ctypes.c_int64), ("partial_residency", ctypes.c_int32),
                 ("flat_unchanged", ctypes.c_int32),
                 ("deferred_visits", ctypes.c_int64), ("deferred_unchanged", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FlowAccStats(ctypes.Structure):
+    _fields_ = [("exits", ctypes.c_int64), ("max_hops", ctypes.c_int32),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_tile", ctypes.c_float), ("ms_forest", ctypes.c_float),
+                ("ms_final", ctypes.c_float)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -129,6 +140,8 @@ SIGNATURES = {
     "hdem_quadratic_f32_dev": [_vp, _vp, _i, _i, _i, _vp],
     "hdem_groves_f32": [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
     "hdem_groves_f32_dev": [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp],
+    "hdem_flowacc_u8": [_vp, _vp, _i, _i, _vp, _c.POINTER(FlowAccStats)],
+    "hdem_flowacc_u8_dev": [_vp, _vp, _i, _i, _vp, _c.POINTER(FlowAccStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 
@@ -311,7 +324,8 @@ def device_count():
 
 
 _DTYPES = {np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.uint8),
-           np.dtype(np.complex64), np.dtype(np.complex128), np.dtype(np.int64)}
+           np.dtype(np.complex64), np.dtype(np.complex128), np.dtype(np.int64),
+           np.dtype(np.uint32)}
 
 
 class _HostBlocks:
@@ -481,6 +495,18 @@ def d8_dev(z, out=None):
     c = z.ctx
     c.check(c.lib.hdem_d8_f32_dev(c.handle, z.ptr, z.shape[0], z.shape[1], out.ptr))
     return out
+
+
+def flowacc_dev(codes, out=None):
+    """D8 flow accumulation of a uint8 code raster (``hdem_flowacc_u8_dev``): a uint32
+    raster and the stats dict.  Synchronises (the call reads its validity counters)."""
+    _need(codes, np.uint8)
+    out = out or DeviceRaster.empty(codes.shape, np.uint32, codes.ctx)
+    c = codes.ctx
+    st = FlowAccStats()
+    c.check(c.lib.hdem_flowacc_u8_dev(c.handle, codes.ptr, codes.shape[0], codes.shape[1],
+                                      out.ptr, ctypes.byref(st)))
+    return out, st.as_dict()
 
 
 def sinkfill_dev(z, eps=0.0, max_rounds=0, out=None, flags=FILL_INIT):
@@ -814,6 +840,20 @@ def d8(z):
     c.check(c.lib.hdem_d8_f32(c.handle, z.ctypes.data, z.shape[0], z.shape[1],
                               out.ctypes.data))
     return out
+
+
+def flowacc(codes, return_stats=False):
+    """D8 flow accumulation of a uint8 code raster (``hdem_flowacc_u8``): uint32."""
+    codes = np.asarray(codes)
+    if codes.dtype != np.uint8:
+        raise ValueError(f"flow accumulation takes uint8 D8 codes, got {codes.dtype}")
+    c = context()
+    codes = _host2d(codes, np.uint8)
+    out = host_empty(codes.shape, np.uint32)
+    st = FlowAccStats()
+    c.check(c.lib.hdem_flowacc_u8(c.handle, codes.ctypes.data, codes.shape[0], codes.shape[1],
+                                  out.ctypes.data, ctypes.byref(st)))
+    return (out, st.as_dict()) if return_stats else out
 
 
 def sinkfill(z, eps=0.0, max_rounds=0, return_stats=False):

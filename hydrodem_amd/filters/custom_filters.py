@@ -23,8 +23,8 @@ construction, SURVEY section 2 #9 / 8e "not shardable"; no kernel is wanted):
 :801-831.  They exist so that `image_hsheds.py:6-7,203-205` imports and runs
 unchanged when ``filters`` resolves here.
 
-New operators (the reference has neither): ``SinkFill`` and
-``D8FlowDirection``, shaped like every other ``Filter``.
+New operators (the reference has neither): ``SinkFill``,
+``D8FlowDirection`` and ``FlowAccumulation``, shaped like every other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -289,6 +289,54 @@ class D8FlowDirection(Filter):  # pylint: disable=too-few-public-methods
 
     def apply_device(self, raster):
         return backend.d8_dev(raster)
+
+
+class FlowAccumulation(Filter):  # pylint: disable=too-few-public-methods
+    """D8 flow accumulation (new operator).  Input: a uint8 H x W raster of ESRI D8
+    codes as ``D8FlowDirection`` returns them (E=1, SE=2, S=4, SW=8, W=16, NW=32, N=64,
+    NE=128); code 0, or a code that points outside the raster, makes a cell terminal.
+    Returns uint32: ``acc[c]`` is the number of cells whose D8 path passes through ``c``,
+    ``c`` included, so every cell is >= 1 -- the unique solution of
+    ``acc[c] = 1 + sum(acc[d])`` over the neighbours ``d`` whose code points at ``c``.
+    Exact integers, identical from run to run.
+
+    Nodata: NaN cells of a DEM get code 0 from D8 and are never chosen as a receiver,
+    so they read 1; masking them is the caller's job.
+
+    ``ValueError`` for a dtype other than uint8 or a raster that is not 2-D (checked
+    before the device is touched), for a byte that is not a D8 code, for codes that form
+    a cycle (only user-supplied codes can: D8 always points to a strictly lower cell) and
+    for more than 2^32 - 1 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        exits (nodes of the exit forest), max_hops (tile crossings of the longest forest
+        walk), tile_h / tile_w of the last call; phase times when profiling is on.
+    """
+
+    auto_device = True      # device form == host form for a uint8 code raster
+
+    def __init__(self):
+        self.stats = {}
+
+    @staticmethod
+    def _check(dtype, ndim):
+        if dtype != np.uint8:
+            raise ValueError(f"FlowAccumulation takes uint8 D8 codes, got {dtype}")
+        if ndim != 2:
+            raise ValueError(f"FlowAccumulation takes a 2-D raster, got {ndim} dimensions")
+
+    def apply(self, image_to_filter):
+        super().apply(image_to_filter)
+        self._check(image_to_filter.dtype, image_to_filter.ndim)
+        out, self.stats = backend.flowacc(image_to_filter, return_stats=True)
+        return out
+
+    def apply_device(self, raster):
+        self._check(raster.dtype, len(raster.shape))
+        out, self.stats = backend.flowacc_dev(raster)
+        return out
 
 
 class HydroConditioning(ComposedFilter):  # pylint: disable=too-few-public-methods

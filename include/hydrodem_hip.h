@@ -110,7 +110,8 @@ typedef enum hdem_kernel_id {
     HDEM_K_FILL_FLAT = 17,      /* sink fill: interiors of the tiles that ended flat      */
     HDEM_K_ELEMENTWISE = 18,    /* element-wise operators on device rasters               */
     HDEM_K_FILL_HUB = 19,       /* sink fill: hub start (in-tile path costs + hub raster)  */
-    HDEM_K_COUNT = 20
+    HDEM_K_FLOWACC = 20,        /* D8 flow accumulation: its four launches together        */
+    HDEM_K_COUNT = 21
 } hdem_kernel_id;
 
 typedef struct hdem_kernel_stat {
@@ -397,6 +398,35 @@ int hdem_groves_f32(hdem_ctx *ctx, const float *img, const uint8_t *groves,
 int hdem_groves_f32_dev(hdem_ctx *ctx, const float *img, const uint8_t *groves,
                         int H, int W, int ws, float thr, int iters,
                         float *scratch_dev, float *out);
+
+/* ---- A5  FlowAccumulation.apply  (new operator: D8 flow accumulation) ---
+ * d8: uint8 ESRI codes as hdem_d8_f32 writes them (E=1, SE=2, S=4, SW=8, W=16, NW=32,
+ * N=64, NE=128).  Code 0, or a code pointing outside the raster, makes a cell terminal;
+ * any other byte is invalid.  out: uint32, acc[c] = the number of cells whose D8 path
+ * passes through c, c itself included (every cell >= 1): the unique solution of
+ * acc[c] = 1 + sum acc[d] over the neighbours d whose code points at c.  Nodata cells of
+ * a DEM get code 0 from D8 and are never chosen as a receiver, so they read 1.  Integers:
+ * bit-exact and run-to-run identical.
+ * HDEM_ERR_BAD_ARG, in bounded time, for an invalid byte, for codes that form a cycle
+ * ("flow directions form a cycle: N cells never drain"; the codes of hdem_d8_f32 always
+ * point to a strictly lower cell and cannot), and -- before any allocation or launch --
+ * for H * W > 2^32 - 1.  On error the contents of out are unspecified.
+ * Workspace: about 1.5 B per cell from the context's arena.  The _dev form synchronises
+ * the context's stream to read its validity counters (as sink fill does).  stats may be
+ * NULL; the three phase times are filled only while profiling is on
+ * (hdem_profile_enable), and the whole call is timed under HDEM_K_FLOWACC. */
+typedef struct hdem_flowacc_stats {
+    int64_t exits;       /* nodes of the exit forest (cells draining into another tile) */
+    int32_t max_hops;    /* longest walk of phase B (tile crossings)                    */
+    int32_t tile_h, tile_w;
+    float ms_tile;       /* phase A: in-tile pass (HIP events; profiling only)          */
+    float ms_forest;     /* phase B: exit forest                                        */
+    float ms_final;      /* phase C: in-tile pass again, writes out                     */
+} hdem_flowacc_stats;
+int hdem_flowacc_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, uint32_t *out,
+                    hdem_flowacc_stats *stats);          /* host pointers, synchronous */
+int hdem_flowacc_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, uint32_t *out,
+                        hdem_flowacc_stats *stats);      /* device pointers */
 
 #ifdef __cplusplus
 }
