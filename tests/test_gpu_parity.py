@@ -274,7 +274,9 @@ def test_convolve_general_weights():
         w = rng.standard_normal(shape)
         want = convolve(x, weights=w) / w.size
         got = hd.Convolve(w).apply(x)
-        assert np.allclose(got, want, rtol=0, atol=2e-5 * np.abs(want).max())
+        assert got.dtype == want.dtype == np.float32
+        # double accumulator, one rounding to float32: within one ulp of the result
+        assert (np.abs(got - want) <= np.spacing(np.abs(want))).all()
 
 
 # --------------------------------------------------------------------------
