@@ -21,7 +21,7 @@ from .filters import Filter, ComposedFilter, ComposedFilterResults  # noqa: F401
 from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F401
                                      GrovesCorrection, GrovesCorrectionsIter,
                                      PostProcessingFinal, SinkFill,
-                                     D8FlowDirection, FlowAccumulation,
+                                     D8FlowDirection, FlowAccumulation, Watersheds,
                                      HydroConditioning,
                                      ExpandFilter, IsolatedPoints, BlanksFourier,
                                      DetectBlanksFourier, MaskFourier, FourierInitial,

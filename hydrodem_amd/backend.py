@@ -73,6 +73,25 @@ class FlowAccStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class WatershedStats(ctypes.Structure):
+    """``hdem_watershed_stats``; ``struct_size`` is set on construction, as the C ABI asks."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("forest_rounds", ctypes.c_int32),
+                ("basins", ctypes.c_int64), ("exits", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_tile", ctypes.c_float), ("ms_forest", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_
+                if k not in ("struct_size", "reserved")}
+
+
+WS_COMPACT = 1      # HDEM_WS_COMPACT
+
 _c = ctypes
 _vp, _i, _f = _c.c_void_p, _c.c_int, _c.c_float
 # name -> argtypes; every function returns int except the three noted
@@ -142,6 +161,9 @@ SIGNATURES = {
     "hdem_groves_f32_dev": [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp],
     "hdem_flowacc_u8": [_vp, _vp, _i, _i, _vp, _c.POINTER(FlowAccStats)],
     "hdem_flowacc_u8_dev": [_vp, _vp, _i, _i, _vp, _c.POINTER(FlowAccStats)],
+    "hdem_watershed_u8": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _c.POINTER(WatershedStats)],
+    "hdem_watershed_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp,
+                              _c.POINTER(WatershedStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 
@@ -509,6 +531,39 @@ def flowacc_dev(codes, out=None):
     return out, st.as_dict()
 
 
+def watershed_dev(codes, seeds=None, compact=False, out=None):
+    """D8 watershed labels of a uint8 code raster (``hdem_watershed_u8_dev``): a uint32
+    raster, the ``outlets`` of the compact numbering (a host uint32 array of K flat indices,
+    ``None`` otherwise) and the stats dict.  ``seeds``: a uint32 raster of pour points or
+    ``None``.  Synchronises (the call reads its validity counters)."""
+    _need(codes, np.uint8)
+    if seeds is not None:
+        _need(seeds, np.uint32)
+        if tuple(seeds.shape) != tuple(codes.shape):
+            raise ValueError(f"seeds are {tuple(seeds.shape)}, the codes {tuple(codes.shape)}")
+        if compact:
+            raise ValueError("compact labels number the outlets: no pour points with them")
+    c = codes.ctx
+    out = out or DeviceRaster.empty(codes.shape, np.uint32, c)
+    st = WatershedStats()
+    # every cell may be an outlet: room for all, the first K come back
+    room = DeviceRaster.empty(codes.shape, np.uint32, c) if compact else None
+    try:
+        c.check(c.lib.hdem_watershed_u8_dev(
+            c.handle, codes.ptr, codes.shape[0], codes.shape[1],
+            seeds.ptr if seeds is not None else None, WS_COMPACT if compact else 0, out.ptr,
+            room.ptr if compact else None, ctypes.byref(st)))
+        outlets = None
+        if compact:
+            outlets = np.empty(st.basins, np.uint32)
+            c.check(c.lib.hdem_memcpy_d2h(c.handle, outlets.ctypes.data, room.ptr,
+                                          outlets.nbytes))
+    finally:
+        if room is not None:
+            room.free()
+    return out, outlets, st.as_dict()
+
+
 def sinkfill_dev(z, eps=0.0, max_rounds=0, out=None, flags=FILL_INIT):
     _need(z, np.float32)
     out = out or DeviceRaster.empty(z.shape, np.float32, z.ctx)
@@ -854,6 +909,36 @@ def flowacc(codes, return_stats=False):
     c.check(c.lib.hdem_flowacc_u8(c.handle, codes.ctypes.data, codes.shape[0], codes.shape[1],
                                   out.ctypes.data, ctypes.byref(st)))
     return (out, st.as_dict()) if return_stats else out
+
+
+def watershed(codes, seeds=None, compact=False):
+    """D8 watershed labels of a uint8 code raster (``hdem_watershed_u8``): the uint32
+    labels, the ``outlets`` of the compact numbering (``None`` otherwise) and the stats
+    dict.  ``seeds``: a uint32 raster of pour points of the codes' shape, or ``None``."""
+    codes = np.asarray(codes)
+    if codes.dtype != np.uint8:
+        raise ValueError(f"watershed labelling takes uint8 D8 codes, got {codes.dtype}")
+    codes = _host2d(codes, np.uint8)
+    if seeds is not None:
+        seeds = np.asarray(seeds)
+        if seeds.dtype != np.uint32:
+            raise ValueError(f"seeds are uint32, got {seeds.dtype}")
+        if seeds.shape != codes.shape:
+            raise ValueError(f"seeds are {seeds.shape}, the codes {codes.shape}")
+        if compact:
+            raise ValueError("compact labels number the outlets: no pour points with them")
+        seeds = np.ascontiguousarray(seeds)
+    c = context()
+    out = host_empty(codes.shape, np.uint32)
+    # every cell may be an outlet: room for all (untouched pages cost nothing), K are written
+    room = np.empty(codes.size, np.uint32) if compact else None
+    st = WatershedStats()
+    c.check(c.lib.hdem_watershed_u8(
+        c.handle, codes.ctypes.data, codes.shape[0], codes.shape[1],
+        seeds.ctypes.data if seeds is not None else None, WS_COMPACT if compact else 0,
+        out.ctypes.data, room.ctypes.data if compact else None, ctypes.byref(st)))
+    outlets = room[:st.basins].copy() if compact else None
+    return out, outlets, st.as_dict()
 
 
 def sinkfill(z, eps=0.0, max_rounds=0, return_stats=False):

@@ -24,7 +24,8 @@ construction, SURVEY section 2 #9 / 8e "not shardable"; no kernel is wanted):
 unchanged when ``filters`` resolves here.
 
 New operators (the reference has neither): ``SinkFill``,
-``D8FlowDirection`` and ``FlowAccumulation``, shaped like every other ``Filter``.
+``D8FlowDirection``, ``FlowAccumulation`` and ``Watersheds``, shaped like every other
+``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -336,6 +337,139 @@ class FlowAccumulation(Filter):  # pylint: disable=too-few-public-methods
     def apply_device(self, raster):
         self._check(raster.dtype, len(raster.shape))
         out, self.stats = backend.flowacc_dev(raster)
+        return out
+
+
+class Watersheds(Filter):  # pylint: disable=too-few-public-methods
+    """D8 watershed labelling (new operator).  Input: a uint8 H x W raster of ESRI D8 codes
+    exactly as ``FlowAccumulation`` takes them; code 0, or a code that points outside the
+    raster, makes a cell terminal.  Returns uint32 labels.
+
+    ``Watersheds()``: ``label[c]`` is 1 + the flat index ``y * W + x`` of the terminal
+    cell that ``c``'s D8 path ends in (a terminal cell labels itself), so every cell is
+    >= 1.  NaN cells of a DEM get code 0 from D8: each is its own one-cell basin; masking
+    them is the caller's job.
+
+    ``Watersheds(labels="compact")``: the same basins numbered 1 ... K, K the number of
+    terminal cells; ``outlets`` (uint32, K flat indices) maps label ``k`` to
+    ``outlets[k - 1]``.  The numbering is fixed for a raster (by 64 x 64 tile, row-major
+    inside a tile) and the same from ``apply`` and ``apply_device``.
+
+    ``Watersheds(pour_points=...)``: ``label[c]`` is the label of the first pour point on
+    ``c``'s path, ``c`` included, and 0 when the path ends without meeting one, so nested
+    pour points give sub-catchments.  ``pour_points`` is a seeds raster of the codes'
+    shape (any integer dtype whose values fit uint32, or a uint32 ``DeviceRaster``; 0 = no
+    pour point, anything else that cell's label) or a sequence (not an array: an array is
+    a raster) of ``(row, col)`` / ``(row, col, label)``; bare pairs are labelled 1 ... n
+    in order.
+
+    ``ValueError`` for codes that are not a 2-D uint8 raster, seeds of another shape or
+    dtype, coordinates outside the raster, label 0, ``compact`` together with pour points
+    (all before the device is touched), a byte that is not a D8 code, codes that form a
+    cycle (in pour-point mode a loop that holds a pour point is legal) and more than
+    2^32 - 1 cells.  Exact integers, identical from run to run.
+
+    Attributes
+    ----------
+    stats : dict
+        basins (terminal cells), exits, forest_rounds, tile_h / tile_w of the last call;
+        phase times when profiling is on.
+    outlets : numpy.ndarray or None
+        the outlets of the compact numbering of the last call.
+    """
+
+    auto_device = True      # device form == host form for a uint8 code raster
+
+    def __init__(self, pour_points=None, labels="outlet"):
+        if labels not in ("outlet", "compact"):
+            raise ValueError(f"labels is 'outlet' or 'compact', got {labels!r}")
+        if labels == "compact" and pour_points is not None:
+            raise ValueError("compact labels number the outlets: they cannot be combined "
+                             "with pour points")
+        self.labels = labels
+        self.stats = {}
+        self.outlets = None
+        self._seeds = self._points = None
+        if pour_points is None:
+            return
+        if hasattr(pour_points, "ptr") and hasattr(pour_points, "to_host"):   # DeviceRaster
+            if pour_points.dtype != np.uint32 or len(pour_points.shape) != 2:
+                raise ValueError("a device seeds raster is 2-D uint32, got "
+                                 f"{pour_points.dtype} {tuple(pour_points.shape)}")
+            self._seeds = pour_points
+        elif isinstance(pour_points, np.ndarray):      # an array is a raster, never a list
+            if pour_points.ndim != 2:
+                raise ValueError(f"a seeds raster is 2-D, got {pour_points.ndim} dimensions")
+            self._seeds = self._seeds_raster(pour_points)
+        else:
+            self._points = self._point_list(pour_points)
+
+    @staticmethod
+    def _seeds_raster(seeds):
+        if not np.issubdtype(seeds.dtype, np.integer):
+            raise ValueError(f"a seeds raster has an integer dtype, got {seeds.dtype}")
+        if seeds.size and (int(seeds.min()) < 0 or int(seeds.max()) > 0xFFFFFFFF):
+            raise ValueError("seed labels must fit uint32")
+        return np.ascontiguousarray(seeds, dtype=np.uint32)
+
+    @staticmethod
+    def _point_list(points):
+        out = []
+        for k, p in enumerate(points):
+            p = tuple(int(v) for v in p)
+            if len(p) == 2:
+                p += (k + 1,)
+            if len(p) != 3:
+                raise ValueError(f"pour point {k} is (row, col) or (row, col, label), got {p}")
+            if not 0 < p[2] <= 0xFFFFFFFF:
+                raise ValueError(f"pour point {k}: label {p[2]} is not in 1 ... 2^32 - 1 "
+                                 "(0 means no pour point)")
+            out.append(p)
+        return out
+
+    def _host_seeds(self, shape):
+        """The uint32 seeds raster for codes of ``shape`` (None in the outlet modes)."""
+        if self._points is not None:
+            seeds = np.zeros(shape, np.uint32)
+            for k, (row, col, label) in enumerate(self._points):
+                if not (0 <= row < shape[0] and 0 <= col < shape[1]):
+                    raise ValueError(f"pour point {k} at ({row}, {col}) is outside the "
+                                     f"{shape[0]} x {shape[1]} raster")
+                seeds[row, col] = label
+            return seeds
+        if self._seeds is not None and tuple(self._seeds.shape) != tuple(shape):
+            raise ValueError(f"seeds are {tuple(self._seeds.shape)}, the codes {tuple(shape)}")
+        return self._seeds
+
+    @staticmethod
+    def _check(dtype, ndim):
+        if dtype != np.uint8:
+            raise ValueError(f"Watersheds takes uint8 D8 codes, got {dtype}")
+        if ndim != 2:
+            raise ValueError(f"Watersheds takes a 2-D raster, got {ndim} dimensions")
+
+    def apply(self, image_to_filter):
+        super().apply(image_to_filter)
+        self._check(image_to_filter.dtype, image_to_filter.ndim)
+        seeds = self._host_seeds(image_to_filter.shape)
+        if seeds is not None and not isinstance(seeds, np.ndarray):
+            seeds = seeds.to_host()
+        out, self.outlets, self.stats = backend.watershed(image_to_filter, seeds,
+                                                          self.labels == "compact")
+        return out
+
+    def apply_device(self, raster):
+        self._check(raster.dtype, len(raster.shape))
+        seeds = self._host_seeds(raster.shape)
+        mine = isinstance(seeds, np.ndarray)
+        if mine:
+            seeds = backend.DeviceRaster.from_host(seeds, dtype=np.uint32, ctx=raster.ctx)
+        try:
+            out, self.outlets, self.stats = backend.watershed_dev(raster, seeds,
+                                                                  self.labels == "compact")
+        finally:
+            if mine:
+                seeds.free()
         return out
 
 

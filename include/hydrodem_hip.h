@@ -428,6 +428,49 @@ int hdem_flowacc_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, uint32_t *ou
 int hdem_flowacc_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, uint32_t *out,
                         hdem_flowacc_stats *stats);      /* device pointers */
 
+/* ---- A6  Watersheds.apply  (new operator: D8 watershed labelling) -------
+ * d8: uint8 ESRI codes exactly as hdem_flowacc_u8 takes them (0, or a code pointing outside
+ * the raster, is terminal; any byte that is not a code is invalid).  out: uint32 labels.
+ *   seeds == NULL, flags == 0   outlet mode: label[c] = 1 + flat index (y * W + x) of the
+ *       terminal cell that c's D8 path ends in; a terminal cell labels itself.
+ *   seeds != NULL               pour-point mode: seeds is uint32 H x W, 0 = no pour point,
+ *       anything else that cell's label.  label[c] = the seed of the first seeded cell on
+ *       c's path, c included; 0 when the path reaches a terminal cell without meeting one.
+ *   flags == HDEM_WS_COMPACT    outlet mode with labels 1 ... K, K = stats.basins = the
+ *       number of terminal cells, and outlets[k - 1] = flat index of the outlet of label k.
+ *       outlets is required then (and only then) and must have room for H * W entries
+ *       (every cell may be terminal); the host form writes K of them.  The numbering
+ *       is by tile (row-major), then row-major inside a 64 x 64 tile: fixed for a raster,
+ *       the same from both entry points, not row-major over the raster.
+ * Exact integers, identical from run to run.  HDEM_ERR_BAD_ARG, in bounded time, for an
+ * invalid byte, for codes that form a cycle ("N cells never resolve"; in pour-point mode
+ * a loop that holds a seeded cell resolves there and is legal), for compact together with
+ * seeds, for unknown flags and -- before any allocation or launch -- for
+ * H * W > 2^32 - 1.  On error the contents of out and outlets are unspecified.
+ * Workspace: about 2.1 B per cell from the context's arena.  The _dev form synchronises
+ * the context's stream to read its validity counters.  stats may be NULL; otherwise the
+ * caller sets stats->struct_size = sizeof(hdem_watershed_stats) first (48 bytes in this
+ * version; a shorter struct is filled as far as it goes).  The three phase times are
+ * filled only while profiling is on (hdem_profile_enable); the call has no kernel id. */
+#define HDEM_WS_COMPACT 1
+typedef struct hdem_watershed_stats {
+    uint32_t struct_size;   /* in: sizeof(hdem_watershed_stats), set by the caller          */
+    int32_t forest_rounds;  /* pointer-jumping launches of phase B that had work to do      */
+    int64_t basins;         /* terminal cells: K, the number of basins of the outlet modes  */
+    int64_t exits;          /* unseeded cells draining into another tile                    */
+    int32_t tile_h, tile_w;
+    float ms_tile;          /* phase A: in-tile pointer doubling (HIP events; profiling)    */
+    float ms_forest;        /* phase B: the forest of perimeter slots                       */
+    float ms_final;         /* phase C: labels written                                      */
+    int32_t reserved;       /* 0                                                            */
+} hdem_watershed_stats;     /* sizeof == 48 */
+int hdem_watershed_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const uint32_t *seeds,
+                      int flags, uint32_t *out, uint32_t *outlets,
+                      hdem_watershed_stats *stats);      /* host pointers, synchronous */
+int hdem_watershed_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W,
+                          const uint32_t *seeds, int flags, uint32_t *out, uint32_t *outlets,
+                          hdem_watershed_stats *stats);  /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
