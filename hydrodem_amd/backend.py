@@ -92,6 +92,31 @@ class WatershedStats(ctypes.Structure):
 
 WS_COMPACT = 1      # HDEM_WS_COMPACT
 
+
+class FlowTraceStats(ctypes.Structure):
+    """``hdem_flowtrace_stats``; ``struct_size`` is set on construction, as the C ABI asks."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("forest_rounds", ctypes.c_int32),
+                ("stops", ctypes.c_int64), ("unreached", ctypes.c_int64),
+                ("exits", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_tile", ctypes.c_float), ("ms_forest", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_
+                if k not in ("struct_size", "reserved")}
+
+
+# HDEM_FT_STREAMS_*
+FT_STREAMS_NONE, FT_STREAMS_MASK_U8, FT_STREAMS_ACC_U32 = 0, 1, 2
+# outputs of the flow trace, in the order of the C ABI's pointers
+FT_OUTPUTS = (("stop", np.uint32), ("ncard", np.uint32), ("ndiag", np.uint32),
+              ("distance", np.float32), ("hand", np.float32))
+
 _c = ctypes
 _vp, _i, _f = _c.c_void_p, _c.c_int, _c.c_float
 # name -> argtypes; every function returns int except the three noted
@@ -164,6 +189,10 @@ SIGNATURES = {
     "hdem_watershed_u8": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _c.POINTER(WatershedStats)],
     "hdem_watershed_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp,
                               _c.POINTER(WatershedStats)],
+    "hdem_flowtrace_u8": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _vp, _c.c_double,
+                          _vp, _vp, _vp, _vp, _vp, _i, _c.POINTER(FlowTraceStats)],
+    "hdem_flowtrace_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _vp, _c.c_double,
+                              _vp, _vp, _vp, _vp, _vp, _i, _c.POINTER(FlowTraceStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 
@@ -564,6 +593,92 @@ def watershed_dev(codes, seeds=None, compact=False, out=None):
     return out, outlets, st.as_dict()
 
 
+def flowtrace_args(codes, streams, threshold, dem, cellsize, want):
+    """The checks of the flow trace that need no device: ``codes``, ``streams`` and ``dem`` are
+    anything with ``dtype`` and ``shape`` (NumPy arrays or device rasters).  Returns the
+    stream kind, the threshold for the C call and ``want`` as a tuple in the ABI's order."""
+    if np.dtype(codes.dtype) != np.uint8:
+        raise ValueError(f"the flow trace takes uint8 D8 codes, got {codes.dtype}")
+    shape = tuple(codes.shape)
+    if len(shape) != 2:
+        raise ValueError(f"the flow trace takes a 2-D raster, got {len(shape)} dimensions")
+    if isinstance(want, str):
+        want = (want,)
+    names = [n for n, _ in FT_OUTPUTS]
+    unknown = [w for w in want if w not in names]
+    if unknown:
+        raise ValueError(f"unknown flow trace outputs {unknown}: choose among {names}")
+    want = tuple(n for n in names if n in want)
+    if not want:
+        raise ValueError(f"no output wanted: choose among {names}")
+    if streams is None:
+        kind = FT_STREAMS_NONE
+        if threshold is not None:
+            raise ValueError("a threshold needs the uint32 raster it applies to")
+        threshold = 0
+    else:
+        if tuple(streams.shape) != shape:
+            raise ValueError(f"streams are {tuple(streams.shape)}, the codes {shape}")
+        if np.dtype(streams.dtype) == np.uint8:
+            kind = FT_STREAMS_MASK_U8
+            if threshold is not None:
+                raise ValueError("a uint8 stream mask takes no threshold")
+            threshold = 0
+        elif np.dtype(streams.dtype) == np.uint32:
+            kind = FT_STREAMS_ACC_U32
+            if threshold is None:
+                raise ValueError("a uint32 stream raster needs a threshold")
+            if isinstance(threshold, bool) or int(threshold) != threshold or \
+                    not 1 <= int(threshold) <= 0xFFFFFFFF:
+                raise ValueError(f"threshold is an integer in 1 ... 2^32 - 1, got {threshold!r}")
+            threshold = int(threshold)
+        else:
+            raise ValueError("streams are a uint8 mask or a uint32 raster with a threshold, "
+                             f"got {streams.dtype}")
+    if dem is not None:
+        if np.dtype(dem.dtype) != np.float32:
+            raise ValueError(f"the dem is float32, got {dem.dtype}")
+        if tuple(dem.shape) != shape:
+            raise ValueError(f"the dem is {tuple(dem.shape)}, the codes {shape}")
+    elif "hand" in want:
+        raise ValueError("hand needs the dem it is measured on")
+    try:
+        cellsize = float(cellsize)
+    except (TypeError, ValueError):
+        raise ValueError(f"cellsize is a number, got {cellsize!r}") from None
+    if not np.isfinite(cellsize) or cellsize <= 0:
+        raise ValueError(f"cellsize must be finite and positive, got {cellsize}")
+    return kind, threshold, want
+
+
+def flowtrace_dev(codes, streams=None, threshold=None, dem=None, cellsize=1.0,
+                  want=("distance",)):
+    """D8 flow trace of a uint8 code raster (``hdem_flowtrace_u8_dev``): for every cell the
+    first stop on its path and the steps to it.  ``streams``: ``None`` (paths end at terminal
+    cells), a uint8 mask raster, or a uint32 raster with ``threshold`` (stream where
+    ``>= threshold``).  ``want``: any of ``stop``, ``ncard``, ``ndiag`` (uint32), ``distance``,
+    ``hand`` (float32; ``hand`` needs the float32 ``dem``).  Returns ``{name: DeviceRaster}``
+    and the stats dict.  Synchronises (the call reads its validity counters)."""
+    kind, threshold, want = flowtrace_args(codes, streams, threshold, dem, cellsize, want)
+    c = codes.ctx
+    dtypes = dict(FT_OUTPUTS)
+    outs = {}
+    st = FlowTraceStats()
+    try:
+        for name in want:
+            outs[name] = DeviceRaster.empty(codes.shape, dtypes[name], c)
+        c.check(c.lib.hdem_flowtrace_u8_dev(
+            c.handle, codes.ptr, codes.shape[0], codes.shape[1],
+            streams.ptr if streams is not None else None, kind, threshold,
+            dem.ptr if dem is not None else None, float(cellsize),
+            *[outs[n].ptr if n in outs else None for n, _ in FT_OUTPUTS], 0, ctypes.byref(st)))
+    except Exception:
+        for r in outs.values():
+            r.free()
+        raise
+    return outs, st.as_dict()
+
+
 def sinkfill_dev(z, eps=0.0, max_rounds=0, out=None, flags=FILL_INIT):
     _need(z, np.float32)
     out = out or DeviceRaster.empty(z.shape, np.float32, z.ctx)
@@ -939,6 +1054,31 @@ def watershed(codes, seeds=None, compact=False):
         out.ctypes.data, room.ctypes.data if compact else None, ctypes.byref(st)))
     outlets = room[:st.basins].copy() if compact else None
     return out, outlets, st.as_dict()
+
+
+def flowtrace(codes, streams=None, threshold=None, dem=None, cellsize=1.0, want=("distance",)):
+    """D8 flow trace of host arrays (``hdem_flowtrace_u8``; see :func:`flowtrace_dev`):
+    ``{name: ndarray}`` and the stats dict.  A bool ``streams`` array is a mask."""
+    for name, a in (("codes", codes), ("streams", streams), ("dem", dem)):
+        if a is not None and not isinstance(a, np.ndarray):
+            raise ValueError(f"{name} is a NumPy array, got {type(a)}")
+    if streams is not None and streams.dtype == np.bool_:
+        streams = streams.view(np.uint8)
+    kind, threshold, want = flowtrace_args(codes, streams, threshold, dem, cellsize, want)
+    codes = np.ascontiguousarray(codes)
+    streams = np.ascontiguousarray(streams) if streams is not None else None
+    dem = np.ascontiguousarray(dem) if dem is not None else None
+    c = context()
+    dtypes = dict(FT_OUTPUTS)
+    outs = {name: host_empty(codes.shape, dtypes[name]) for name in want}
+    st = FlowTraceStats()
+    c.check(c.lib.hdem_flowtrace_u8(
+        c.handle, codes.ctypes.data, codes.shape[0], codes.shape[1],
+        streams.ctypes.data if streams is not None else None, kind, threshold,
+        dem.ctypes.data if dem is not None else None, float(cellsize),
+        *[outs[n].ctypes.data if n in outs else None for n, _ in FT_OUTPUTS], 0,
+        ctypes.byref(st)))
+    return outs, st.as_dict()
 
 
 def sinkfill(z, eps=0.0, max_rounds=0, return_stats=False):

@@ -1,0 +1,529 @@
+// D8 flow trace (new operators; FlowDistance, HeightAboveDrainage, DemToHAND).
+//
+// For every cell c: s(c), the first *stop* on c's D8 path (c included), and ncard(c) /
+// ndiag(c), the cardinal and diagonal steps taken to get there.  A stop is a terminal cell
+// (code 0 or pointing outside the raster) or, when streams are given, a stream cell
+// (mask != 0, or acc >= threshold).  With streams, a terminal cell that is no stream cell is
+// *dry*: it and everything that ends in it are unreached (stop 0, distance and HAND NaN, the
+// counts still those to the terminal).  "First stop downstream" and "steps to it" compose
+// along a path, (stop, n) o (stop', n') = (stop', n + n'), so the scheme is that of
+// hdem_watershed.hip with a payload on every pointer: 64 x 64 tiles, 252 perimeter slots per
+// tile, a forest over the slots, pointer jumping, no atomics on the data path.
+//   A  (flowtrace_tile_kernel)   per tile: every cell's in-tile receiver, then Jacobi pointer
+//      doubling in LDS on 64-bit words (pointer | ncard << 16 | ndiag << 32; a path inside a
+//      tile has at most 4095 steps) until every cell points at a stop or at an *exit* (a
+//      cell that is no stop and whose receiver lies in a neighbouring tile).  Writes 6 B per
+//      cell (2 B: which stop / which exit; 4 B: the in-tile counts and the dry bit) and one
+//      16-byte forest node per perimeter slot: "resolved, stop S, counts" when the frame
+//      cell's in-tile path ends in a stop, else "next = the slot of the cell its exit drains
+//      into, counts up to and including the crossing step".  The stream test reads the
+//      cell's own value: no tile looks at the streams of its halo.
+//   B  (flowtrace_forest_kernel) pointer jumping with payload over the slot nodes,
+//      node <- (next(next), n + n').  A node is 16 bytes, wider than any single naturally
+//      atomic word, so nothing is done in place: there are two node arrays, launch r reads
+//      only array r & 1 and writes only array (r + 1) & 1, every node every launch, and the
+//      launches are ordered by the stream.  No reader can see a half-written node because no
+//      launch reads what it writes.  The host enqueues ceil(log2 slots) + 1 launches; a
+//      launch whose predecessor left nothing unresolved returns at once (the count stays on
+//      the device), so a cycle costs the full schedule and nothing more.  C works out from
+//      the same counts which array holds the result.
+//   C  (flowtrace_final_kernel)  per tile, streaming: the tile's 252 resolved nodes in LDS,
+//      6 B per cell in, 4 B per cell and wanted output out.  HAND gathers dem[s(c)].
+#include "hdem_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace {
+
+constexpr int NT = 256;               // threads per forest / final workgroup
+constexpr int TNT = 1024;             // threads per tile workgroup (4 cells each; the LDS
+                                      // allows two workgroups per CU whatever their size: A at
+                                      // 16384^2 takes 3.48 ms with 256, 2.17 with 512, 1.72
+                                      // with 1024)
+constexpr int TS = 64;                // tile edge
+constexpr int TC = TS * TS;           // cells per tile (12-bit local index)
+constexpr int PER = 4 * TS - 4;       // perimeter slots per tile
+constexpr int DOUBLINGS = 12;         // 2^12 >= the longest path inside a tile (4095 steps)
+constexpr int JUMPS = 4;              // forest jumps per node and launch, all in the source
+                                      // array (B at 16384^2, distance to the outlet: 1.01 ms
+                                      // with 1, 0.71 with 2, 0.54 with 4)
+constexpr int MAX_ROUNDS = 32;        // forest launches: slots < 2^31
+constexpr uint16_t T_EXIT = 0x8000;   // per-cell target: perimeter slot of the exit reached
+constexpr uint32_t C_DRY = 1u << 31;  // per-cell counts word: the stop reached is a dry terminal
+constexpr uint32_t RESOLVED = 1u;     // node.y
+
+// kind[] of a cell
+constexpr uint8_t K_TRAVEL = 0;       // has an in-tile receiver
+constexpr uint8_t K_EXIT = 1;         // receiver in a neighbouring tile, cell no stop
+constexpr uint8_t K_STOP = 2;         // terminal or stream cell (outside the raster too)
+constexpr uint8_t K_DRY = 3;          // terminal, streams given, no stream cell
+
+// node: x = stop (1 + flat index, 0 = dry) when resolved, else the next slot; y = RESOLVED or
+// 0; z = ncard; w = ndiag
+typedef uint4 node_t;
+
+struct flowtrace_counters {
+    unsigned long long stops;         // stop cells (stream cells and terminal cells)
+    unsigned long long exits;         // exit cells (forest pointers of their own)
+    unsigned long long bad;           // cells holding an invalid byte
+    unsigned long long unreached;     // cells whose path ends in a dry terminal
+    unsigned long long stuck_cells;   // cells that never reached a stop
+    unsigned long long stuck_slots;   // forest nodes that never resolved
+    unsigned long long unresolved[MAX_ROUNDS];   // forest nodes left after each round
+};
+
+// bit b of a code -> (dy, dx), packed (d + 1) in 4 bits per entry; odd bits are diagonal
+__device__ __forceinline__ int code_dy(int b) { return ((0x00012221u >> (4 * b)) & 3) - 1; }
+__device__ __forceinline__ int code_dx(int b) { return ((0x21000122u >> (4 * b)) & 3) - 1; }
+
+// perimeter slot of a frame cell: top row, bottom row, left column, right column
+__device__ __forceinline__ int perim_pos(int ly, int lx)
+{
+    return ly == 0 ? lx : ly == TS - 1 ? TS + lx : lx == 0 ? 2 * TS + ly - 1 : 3 * TS - 2 + ly - 1;
+}
+__device__ __forceinline__ void perim_cell(int p, int &ly, int &lx)
+{
+    if (p < TS) { ly = 0; lx = p; }
+    else if (p < 2 * TS) { ly = TS - 1; lx = p - TS; }
+    else if (p < 3 * TS - 2) { ly = p - 2 * TS + 1; lx = 0; }
+    else { ly = p - (3 * TS - 2) + 1; lx = TS - 1; }
+}
+
+// Slot of local frame position (ny, nx) that lies one cell outside tile (ty, tx): the
+// perimeter slot of that cell in the tile that holds it.
+__device__ __forceinline__ int64_t slot_of(int ty, int tx, int tiles_x, int ny, int nx)
+{
+    const int sy = ny < 0 ? -1 : ny >= TS ? 1 : 0;
+    const int sx = nx < 0 ? -1 : nx >= TS ? 1 : 0;
+    const int64_t tile = (int64_t)(ty + sy) * tiles_x + (tx + sx);
+    return tile * PER + perim_pos(ny - sy * TS, nx - sx * TS);
+}
+
+// LDS word of A: pointer in bits 0-15, ncard in 16-31, ndiag in 32-47.  A stop or an exit
+// holds (itself, 0, 0), so composing "a then b" is one addition of b to a's counts.
+__device__ __forceinline__ uint32_t w_ptr(uint64_t w) { return (uint32_t)w & 0xFFFFu; }
+__device__ __forceinline__ uint32_t w_nc(uint64_t w) { return (uint32_t)(w >> 16) & 0xFFFFu; }
+__device__ __forceinline__ uint32_t w_nd(uint64_t w) { return (uint32_t)(w >> 32) & 0xFFFFu; }
+
+// A.  STREAMS 0: none, 1: uint8 mask, 2: uint32 raster against a threshold.
+template <int STREAMS>
+__global__ __launch_bounds__(TNT) void flowtrace_tile_kernel(
+    const uint8_t *__restrict__ d8, const void *__restrict__ streams, uint32_t threshold, int H,
+    int W, int tiles_x, uint16_t *__restrict__ target, uint32_t *__restrict__ counts,
+    node_t *__restrict__ node, flowtrace_counters *__restrict__ cnt)
+{
+    __shared__ uint8_t code[TC];
+    __shared__ uint8_t kind[TC];
+    __shared__ uint64_t jump[2][TC];
+    __shared__ unsigned int s_cnt[4];            // invalid codes, stops, exits, stuck cells
+
+    const int tid = threadIdx.x;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const int y0 = ty * TS, x0 = tx * TS;
+    const int th = min(TS, H - y0), tw = min(TS, W - x0);
+    const int64_t base = (int64_t)blockIdx.x * PER;
+
+    if (tid < 4) s_cnt[tid] = 0;
+    __syncthreads();
+
+    // receivers; a stop or an exit points at itself with no steps taken
+    unsigned int bad = 0, stops = 0;
+    for (int i = tid; i < TC; i += TNT) {
+        const int ly = i / TS, lx = i % TS;
+        uint8_t k = K_STOP;
+        uint64_t w = (uint64_t)i;
+        int c = 0;
+        if (ly < th && lx < tw) {
+            const size_t g = (size_t)(y0 + ly) * W + x0 + lx;
+            c = d8[g];
+            bool stream = false;
+            if (STREAMS == 1) stream = static_cast<const uint8_t *>(streams)[g] != 0;
+            if (STREAMS == 2) stream = static_cast<const uint32_t *>(streams)[g] >= threshold;
+            bool terminal = true;
+            int ny = 0, nx = 0, b = 0;
+            if (c & (c - 1)) {
+                ++bad;
+            } else if (c) {
+                b = __builtin_ctz(c);
+                ny = ly + code_dy(b);
+                nx = lx + code_dx(b);
+                const int gy = y0 + ny, gx = x0 + nx;
+                terminal = !(gy >= 0 && gy < H && gx >= 0 && gx < W);
+            }
+            if (stream || terminal) {
+                k = (STREAMS == 0 || stream) ? K_STOP : K_DRY;
+                ++stops;
+            } else if (ny >= 0 && ny < TS && nx >= 0 && nx < TS) {
+                k = K_TRAVEL;
+                w = (uint64_t)(ny * TS + nx) | ((b & 1) ? 1ull << 32 : 1ull << 16);
+            } else {
+                k = K_EXIT;
+            }
+        }
+        code[i] = (uint8_t)c;
+        kind[i] = k;
+        jump[0][i] = w;
+    }
+    if (bad) atomicAdd(&s_cnt[0], bad);
+    if (stops) atomicAdd(&s_cnt[1], stops);
+    __syncthreads();
+
+    // pointer doubling: after round k a cell points 2^k steps down its in-tile path, or at
+    // the stop / exit that ends it, and carries the steps to where it points
+    int cur = 0;
+    for (int round = 0; round < DOUBLINGS; ++round) {
+        int changed = 0;
+        for (int i = tid; i < TC; i += TNT) {
+            const uint64_t a = jump[cur][i];
+            const uint64_t b = jump[cur][w_ptr(a)];
+            jump[cur ^ 1][i] = (a & ~0xFFFFull) + b;     // a's counts + b's counts, b's pointer
+            changed |= w_ptr(a) != w_ptr(b);
+        }
+        cur ^= 1;
+        if (!__syncthreads_or(changed)) break;
+    }
+    const uint64_t *jmp = jump[cur];
+
+    // 6 B per cell for C: the stop (local index) or the exit (perimeter slot) it reaches,
+    // and the steps to it
+    unsigned int stuck = 0;
+    for (int i = tid; i < TC; i += TNT) {
+        const int ly = i / TS, lx = i % TS;
+        if (ly >= th || lx >= tw) continue;
+        const uint64_t w = jmp[i];
+        const uint32_t t = w_ptr(w);
+        const uint8_t k = kind[t];
+        if (k == K_TRAVEL) ++stuck;                      // a cycle inside the tile
+        target[(size_t)blockIdx.x * TC + i] =
+            k == K_EXIT ? (uint16_t)(T_EXIT | perim_pos(t / TS, t % TS)) : (uint16_t)t;
+        counts[(size_t)blockIdx.x * TC + i] =
+            (w_nc(w) & 0xFFFu) | ((w_nd(w) & 0xFFFu) << 12) | (k == K_DRY ? C_DRY : 0u);
+    }
+    if (stuck) atomicAdd(&s_cnt[3], stuck);
+
+    // the perimeter slots
+    if (tid < PER) {
+        int ly, lx;
+        perim_cell(tid, ly, lx);
+        node_t n = make_uint4(0u, RESOLVED, 0u, 0u);     // outside the raster: never read
+        if (ly < th && lx < tw) {
+            const int i = ly * TS + lx;
+            const uint64_t w = jmp[i];
+            const int t = (int)w_ptr(w);
+            const uint8_t k = kind[t];
+            const int t_ly = t / TS, t_lx = t % TS;
+            n.z = w_nc(w);
+            n.w = w_nd(w);
+            if (k == K_STOP) {
+                n.x = (uint32_t)((size_t)(y0 + t_ly) * W + x0 + t_lx) + 1u;
+            } else if (k == K_DRY) {
+                n.x = 0u;
+            } else if (k == K_EXIT) {
+                const int b = __builtin_ctz(code[t]);
+                n.x = (uint32_t)slot_of(ty, tx, tiles_x, t_ly + code_dy(b), t_lx + code_dx(b));
+                n.y = 0u;
+                if (b & 1) ++n.w; else ++n.z;            // the crossing step
+            } else {
+                n = make_uint4((uint32_t)(base + tid), 0u, 0u, 0u);   // a cycle: never resolves
+            }
+            if (kind[i] == K_EXIT) atomicAdd(&s_cnt[2], 1u);
+        }
+        node[base + tid] = n;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (s_cnt[0]) atomicAdd(&cnt->bad, (unsigned long long)s_cnt[0]);
+        if (s_cnt[1]) atomicAdd(&cnt->stops, (unsigned long long)s_cnt[1]);
+        if (s_cnt[2]) atomicAdd(&cnt->exits, (unsigned long long)s_cnt[2]);
+        if (s_cnt[3]) atomicAdd(&cnt->stuck_cells, (unsigned long long)s_cnt[3]);
+    }
+}
+
+// B: one round of pointer jumping with payload, src -> dst.  Grid-stride.
+__global__ __launch_bounds__(NT) void flowtrace_forest_kernel(int64_t nslots, int round,
+                                                              const node_t *__restrict__ src,
+                                                              node_t *__restrict__ dst,
+                                                              flowtrace_counters *__restrict__ cnt)
+{
+    if (round > 0 && __hip_atomic_load(&cnt->unresolved[round - 1], __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT) == 0)
+        return;
+    __shared__ unsigned int s_left;
+    if (threadIdx.x == 0) s_left = 0;
+    __syncthreads();
+    unsigned int left = 0;
+    for (int64_t s = (int64_t)blockIdx.x * NT + threadIdx.x; s < nslots;
+         s += (int64_t)gridDim.x * NT) {
+        node_t n = src[s];
+        for (int j = 0; j < JUMPS && !(n.y & RESOLVED); ++j) {
+            const node_t t = src[n.x];                   // my pointer's node, as the last launch left it
+            n = make_uint4(t.x, t.y, n.z + t.z, n.w + t.w);
+        }
+        dst[s] = n;
+        left += !(n.y & RESOLVED);
+    }
+    for (int m = 32; m >= 1; m >>= 1) left += __shfl_xor(left, m);
+    if ((threadIdx.x & 63) == 0 && left) atomicAdd(&s_left, left);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_left) atomicAdd(&cnt->unresolved[round], (unsigned long long)s_left);
+}
+
+// C.  Every output pointer may be null (not wanted).  cs2 = cellsize * sqrt(2), in double.
+__global__ __launch_bounds__(NT) void flowtrace_final_kernel(
+    int H, int W, int tiles_x, int rounds, const uint16_t *__restrict__ target,
+    const uint32_t *__restrict__ counts, const node_t *__restrict__ node0,
+    const node_t *__restrict__ node1, const float *__restrict__ dem, double cs, double cs2,
+    uint32_t *__restrict__ out_stop, uint32_t *__restrict__ out_nc, uint32_t *__restrict__ out_nd,
+    float *__restrict__ out_dist, float *__restrict__ out_hand,
+    flowtrace_counters *__restrict__ cnt)
+{
+    __shared__ uint32_t n_stop[PER], n_nc[PER], n_nd[PER];
+    __shared__ uint8_t known[PER];
+    __shared__ unsigned int s_cnt[3];            // stuck cells, stuck slots, unreached cells
+
+    const int tid = threadIdx.x;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const int y0 = ty * TS, x0 = tx * TS;
+    const int th = min(TS, H - y0), tw = min(TS, W - x0);
+    const uint16_t *tg = target + (size_t)blockIdx.x * TC;
+    const uint32_t *ct = counts + (size_t)blockIdx.x * TC;
+
+    if (tid < 3) s_cnt[tid] = 0;
+    if (tid < PER) {
+        // launch r of B wrote array (r + 1) & 1; the first that left nothing unresolved wrote
+        // the result, and every later one returned at once
+        int r = 0;
+        while (r < rounds - 1 && cnt->unresolved[r]) ++r;
+        const node_t n = (((r + 1) & 1) ? node1 : node0)[(int64_t)blockIdx.x * PER + tid];
+        const bool ok = (n.y & RESOLVED) != 0;
+        n_stop[tid] = ok ? n.x : 0u;                     // a slot number is no cell to gather from
+        n_nc[tid] = n.z;
+        n_nd[tid] = n.w;
+        known[tid] = ok;
+    }
+    __syncthreads();
+    if (tid < PER && !known[tid]) atomicAdd(&s_cnt[1], 1u);
+
+    const float nan = __builtin_nanf("");
+    unsigned int stuck = 0, unreached = 0;
+    for (int i = tid; i < TC; i += NT) {
+        const int ly = i / TS, lx = i % TS;
+        if (ly >= th || lx >= tw) continue;
+        const size_t g = (size_t)(y0 + ly) * W + x0 + lx;
+        const uint16_t v = tg[i];
+        const uint32_t c = ct[i];
+        uint32_t nc = c & 0xFFFu, nd = (c >> 12) & 0xFFFu, stop;
+        if (v & T_EXIT) {
+            const int p = v & 0xFF;
+            stop = n_stop[p];
+            nc += n_nc[p];
+            nd += n_nd[p];
+            stuck += !known[p];
+        } else {
+            stop = (c & C_DRY) ? 0u : (uint32_t)((size_t)(y0 + v / TS) * W + x0 + v % TS) + 1u;
+        }
+        unreached += stop == 0u;
+        if (out_stop) out_stop[g] = stop;
+        if (out_nc) out_nc[g] = nc;
+        if (out_nd) out_nd[g] = nd;
+        if (out_dist)
+            out_dist[g] = stop ? __double2float_rn(__dadd_rn(__dmul_rn((double)nc, cs),
+                                                             __dmul_rn((double)nd, cs2)))
+                               : nan;
+        if (out_hand) out_hand[g] = stop ? __fsub_rn(dem[g], dem[stop - 1u]) : nan;
+    }
+    if (stuck) atomicAdd(&s_cnt[0], stuck);
+    if (unreached) atomicAdd(&s_cnt[2], unreached);
+    __syncthreads();
+    if (tid == 0) {
+        if (s_cnt[0]) atomicAdd(&cnt->stuck_cells, (unsigned long long)s_cnt[0]);
+        if (s_cnt[1]) atomicAdd(&cnt->stuck_slots, (unsigned long long)s_cnt[1]);
+        if (s_cnt[2]) atomicAdd(&cnt->unreached, (unsigned long long)s_cnt[2]);
+    }
+}
+
+int check_args(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *streams,
+               int stream_kind, uint32_t threshold, const float *dem, double cellsize,
+               const uint32_t *stop, const uint32_t *ncard, const uint32_t *ndiag,
+               const float *distance, const float *hand, int flags,
+               const hdem_flowtrace_stats *stats)
+{
+    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
+    if (int rc = hdem_check_raster(d8, d8, H, W)) return rc;
+    const int64_t cells = (int64_t)H * W;
+    HDEM_REQUIRE(cells <= (int64_t)UINT32_MAX, HDEM_ERR_BAD_ARG,
+                 "flow trace indices are uint32: %d x %d = %lld cells is more than 2^32 - 1", H, W,
+                 (long long)cells);
+    HDEM_REQUIRE(!flags, HDEM_ERR_BAD_ARG, "unknown flow trace flags 0x%x", flags);
+    HDEM_REQUIRE(stop || ncard || ndiag || distance || hand, HDEM_ERR_BAD_ARG,
+                 "no output wanted: give at least one of stop, ncard, ndiag, distance, hand");
+    HDEM_REQUIRE(!hand || dem, HDEM_ERR_BAD_ARG, "hand needs the dem it is measured on");
+    switch (stream_kind) {
+    case HDEM_FT_STREAMS_NONE:
+        HDEM_REQUIRE(!streams && !threshold, HDEM_ERR_BAD_ARG,
+                     "streams and threshold must be null and 0 with HDEM_FT_STREAMS_NONE");
+        break;
+    case HDEM_FT_STREAMS_MASK_U8:
+        HDEM_REQUIRE(streams, HDEM_ERR_BAD_ARG, "the stream mask is null");
+        HDEM_REQUIRE(!threshold, HDEM_ERR_BAD_ARG,
+                     "a uint8 stream mask takes no threshold (got %u)", threshold);
+        break;
+    case HDEM_FT_STREAMS_ACC_U32:
+        HDEM_REQUIRE(streams, HDEM_ERR_BAD_ARG, "the stream raster is null");
+        HDEM_REQUIRE(threshold >= 1, HDEM_ERR_BAD_ARG,
+                     "a uint32 stream raster needs a threshold >= 1");
+        break;
+    default:
+        HDEM_REQUIRE(false, HDEM_ERR_BAD_ARG, "unknown stream kind %d", stream_kind);
+    }
+    HDEM_REQUIRE(std::isfinite(cellsize) && cellsize > 0.0, HDEM_ERR_BAD_ARG,
+                 "cellsize must be finite and positive, got %g", cellsize);
+    HDEM_REQUIRE(!stats || stats->struct_size >= sizeof(uint32_t), HDEM_ERR_BAD_ARG,
+                 "hdem_flowtrace_stats.struct_size is %u: set it to sizeof(hdem_flowtrace_stats)",
+                 stats ? stats->struct_size : 0u);
+    return HDEM_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------
+extern "C" int hdem_flowtrace_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W,
+                                     const void *streams, int stream_kind, uint32_t threshold,
+                                     const float *dem, double cellsize, uint32_t *stop,
+                                     uint32_t *ncard, uint32_t *ndiag, float *distance,
+                                     float *hand, int flags, hdem_flowtrace_stats *stats)
+{
+    if (int rc = check_args(ctx, d8, H, W, streams, stream_kind, threshold, dem, cellsize, stop,
+                            ncard, ndiag, distance, hand, flags, stats))
+        return rc;
+    const int tiles_y = (H + TS - 1) / TS, tiles_x = (W + TS - 1) / TS;
+    const int64_t tiles = (int64_t)tiles_y * tiles_x;
+    const int64_t nslots = tiles * PER;
+    // (slots are 31-bit; only rasters a few cells wide and ~10^9 long get here)
+    HDEM_REQUIRE(nslots <= INT32_MAX, HDEM_ERR_BAD_ARG,
+                 "flow trace: %d x %d has %lld tiles of %d x %d, more than %d", H, W,
+                 (long long)tiles, TS, TS, INT32_MAX / PER);
+    HDEM_HIP_CHECK(hipSetDevice(ctx->device));
+
+    // what the caller's struct has room for is filled, and nothing beyond it
+    hdem_flowtrace_stats st = {};
+    const uint32_t st_size = stats ? std::min<uint32_t>(stats->struct_size, sizeof(st)) : 0;
+    st.struct_size = st_size;
+    auto publish = [&]() { if (stats) memcpy(stats, &st, st_size); };
+    publish();
+
+    // arena: counters | two node arrays, 16 B per slot each | counts u32 per cell | target
+    // u16 per cell
+    const size_t head = 512;
+    static_assert(sizeof(flowtrace_counters) <= head, "counters outgrew their block");
+    const size_t bytes = head + (size_t)nslots * 32 + (size_t)tiles * TC * 6;
+    char *ws = static_cast<char *>(hdem_arena(ctx, bytes));
+    if (!ws) return HDEM_ERR_OOM;
+    flowtrace_counters *cnt = reinterpret_cast<flowtrace_counters *>(ws);
+    node_t *node[2] = {reinterpret_cast<node_t *>(ws + head),
+                       reinterpret_cast<node_t *>(ws + head) + nslots};
+    uint32_t *counts = reinterpret_cast<uint32_t *>(node[1] + nslots);
+    uint16_t *target = reinterpret_cast<uint16_t *>(counts + (size_t)tiles * TC);
+
+    hipEvent_t ev[4] = {};
+    const bool phases = ctx->profiling && stats;
+    for (int k = 0; phases && k < 4; ++k) HDEM_HIP_CHECK(hipEventCreate(&ev[k]));
+    auto mark = [&](int k) { if (phases) (void)hipEventRecord(ev[k], ctx->stream); };
+
+    HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(flowtrace_counters), ctx->stream));
+    int rounds = 1;                               // ceil(log2 nslots) + 1
+    while ((1ll << (rounds - 1)) < nslots) ++rounds;
+    const int64_t forest_blocks = (nslots + NT - 1) / NT;
+    const int forest_grid = (int)std::min<int64_t>(forest_blocks, (int64_t)ctx->num_cus * 8);
+    const dim3 grid((unsigned)tiles);
+
+    mark(0);
+    if (stream_kind == HDEM_FT_STREAMS_NONE)
+        hipLaunchKernelGGL(flowtrace_tile_kernel<0>, grid, dim3(TNT), 0, ctx->stream, d8, streams,
+                           threshold, H, W, tiles_x, target, counts, node[0], cnt);
+    else if (stream_kind == HDEM_FT_STREAMS_MASK_U8)
+        hipLaunchKernelGGL(flowtrace_tile_kernel<1>, grid, dim3(TNT), 0, ctx->stream, d8, streams,
+                           threshold, H, W, tiles_x, target, counts, node[0], cnt);
+    else
+        hipLaunchKernelGGL(flowtrace_tile_kernel<2>, grid, dim3(TNT), 0, ctx->stream, d8, streams,
+                           threshold, H, W, tiles_x, target, counts, node[0], cnt);
+    mark(1);
+    for (int r = 0; r < rounds; ++r)
+        hipLaunchKernelGGL(flowtrace_forest_kernel, dim3(forest_grid), dim3(NT), 0, ctx->stream,
+                           nslots, r, node[r & 1], node[(r + 1) & 1], cnt);
+    mark(2);
+    const double cs2 = cellsize * std::sqrt(2.0);
+    hipLaunchKernelGGL(flowtrace_final_kernel, grid, dim3(NT), 0, ctx->stream, H, W, tiles_x,
+                       rounds, target, counts, node[0], node[1], dem, cellsize, cs2, stop, ncard,
+                       ndiag, distance, hand, cnt);
+    mark(3);
+    HDEM_HIP_CHECK(hipGetLastError());
+    flowtrace_counters host = {};
+    HDEM_HIP_CHECK(hipMemcpyAsync(&host, cnt, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+    HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+
+    st.stops = (int64_t)host.stops;
+    st.unreached = (int64_t)host.unreached;
+    st.exits = (int64_t)host.exits;
+    st.forest_rounds = 1;
+    while (st.forest_rounds < rounds && host.unresolved[st.forest_rounds - 1]) ++st.forest_rounds;
+    st.tile_h = TS;
+    st.tile_w = TS;
+    if (phases) {
+        (void)hipEventElapsedTime(&st.ms_tile, ev[0], ev[1]);
+        (void)hipEventElapsedTime(&st.ms_forest, ev[1], ev[2]);
+        (void)hipEventElapsedTime(&st.ms_final, ev[2], ev[3]);
+    }
+    publish();
+    for (int k = 0; phases && k < 4; ++k) (void)hipEventDestroy(ev[k]);
+    HDEM_REQUIRE(!host.bad, HDEM_ERR_BAD_ARG,
+                 "invalid D8 code in %llu cells: a code is 0 or one of 1, 2, 4, ..., 128",
+                 host.bad);
+    HDEM_REQUIRE(!host.stuck_cells && !host.stuck_slots, HDEM_ERR_BAD_ARG,
+                 "flow directions form a cycle: %llu cells never resolve (and %llu tile "
+                 "perimeter slots)",
+                 host.stuck_cells, host.stuck_slots);
+    return HDEM_OK;
+}
+
+extern "C" int hdem_flowtrace_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W,
+                                 const void *streams, int stream_kind, uint32_t threshold,
+                                 const float *dem, double cellsize, uint32_t *stop,
+                                 uint32_t *ncard, uint32_t *ndiag, float *distance, float *hand,
+                                 int flags, hdem_flowtrace_stats *stats)
+{
+    if (int rc = check_args(ctx, d8, H, W, streams, stream_kind, threshold, dem, cellsize, stop,
+                            ncard, ndiag, distance, hand, flags, stats))
+        return rc;
+    HDEM_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)H * W;
+    hdem_dbuf dd8, dstreams, ddem, dout[5];
+    if (int rc = dd8.alloc(ctx, n)) return rc;
+    if (int rc = hdem_memcpy_h2d(ctx, dd8.p, d8, n)) return rc;
+    if (streams) {
+        const size_t sb = n * (stream_kind == HDEM_FT_STREAMS_ACC_U32 ? sizeof(uint32_t) : 1);
+        if (int rc = dstreams.alloc(ctx, sb)) return rc;
+        if (int rc = hdem_memcpy_h2d(ctx, dstreams.p, streams, sb)) return rc;
+    }
+    if (dem) {
+        if (int rc = ddem.alloc(ctx, n * sizeof(float))) return rc;
+        if (int rc = hdem_memcpy_h2d(ctx, ddem.p, dem, n * sizeof(float))) return rc;
+    }
+    void *const host_out[5] = {stop, ncard, ndiag, distance, hand};
+    for (int k = 0; k < 5; ++k)
+        if (host_out[k])
+            if (int rc = dout[k].alloc(ctx, n * 4)) return rc;
+    const int rc = hdem_flowtrace_u8_dev(
+        ctx, (const uint8_t *)dd8.p, H, W, dstreams.p, stream_kind, threshold,
+        (const float *)ddem.p, cellsize, (uint32_t *)dout[0].p, (uint32_t *)dout[1].p,
+        (uint32_t *)dout[2].p, (float *)dout[3].p, (float *)dout[4].p, flags, stats);
+    if (rc) return rc;
+    for (int k = 0; k < 5; ++k)
+        if (host_out[k])
+            if (int rc2 = hdem_memcpy_d2h(ctx, host_out[k], dout[k].p, n * 4)) return rc2;
+    return HDEM_OK;
+}

@@ -24,8 +24,8 @@ construction, SURVEY section 2 #9 / 8e "not shardable"; no kernel is wanted):
 unchanged when ``filters`` resolves here.
 
 New operators (the reference has neither): ``SinkFill``,
-``D8FlowDirection``, ``FlowAccumulation`` and ``Watersheds``, shaped like every other
-``Filter``.
+``D8FlowDirection``, ``FlowAccumulation``, ``Watersheds``, ``FlowDistance``,
+``HeightAboveDrainage`` and the chain ``DemToHAND``, shaped like every other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -473,6 +473,147 @@ class Watersheds(Filter):  # pylint: disable=too-few-public-methods
         return out
 
 
+def _is_device_raster(operand):
+    return hasattr(operand, "ptr") and hasattr(operand, "to_host")
+
+
+class _FlowTrace(Filter):  # pylint: disable=too-few-public-methods
+    """What ``FlowDistance`` and ``HeightAboveDrainage`` share: the operands of one
+    ``hdem_flowtrace_u8`` call (streams, threshold, dem, cellsize), checked as far as they can
+    be before the codes are known, and the call on host arrays or device rasters."""
+
+    auto_device = True      # device form == host form for a uint8 code raster
+
+    def _set_operands(self, streams, threshold, dem, cellsize):
+        for name, operand, kinds in (("streams", streams, (np.bool_, np.uint8, np.uint32)),
+                                     ("dem", dem, (np.float32,))):
+            if operand is None:
+                continue
+            if not (isinstance(operand, np.ndarray) or _is_device_raster(operand)):
+                raise ValueError(f"{name} is a NumPy array or a DeviceRaster, got "
+                                 f"{type(operand)}")
+            if len(operand.shape) != 2:
+                raise ValueError(f"{name} is a 2-D raster, got {len(operand.shape)} dimensions")
+            if np.dtype(operand.dtype) not in [np.dtype(k) for k in kinds]:
+                raise ValueError(f"{name} has dtype {' or '.join(np.dtype(k).name for k in kinds)}"
+                                 f", got {operand.dtype}")
+        if isinstance(streams, np.ndarray) and streams.dtype == np.bool_:
+            streams = streams.view(np.uint8)
+        self.streams, self.threshold, self.dem, self.cellsize = streams, threshold, dem, cellsize
+        self.stats = {}
+        # everything but the shapes: a 1 x 1 stand-in for the codes
+        self._check(np.zeros((1, 1), np.uint8), shapes=False)
+
+    def _check(self, codes, want=("distance",), shapes=True):
+        class Like:  # pylint: disable=too-few-public-methods
+            def __init__(self, operand):
+                self.dtype = operand.dtype
+                self.shape = operand.shape if shapes else codes.shape
+        return backend.flowtrace_args(
+            codes, None if self.streams is None else Like(self.streams), self.threshold,
+            None if self.dem is None else Like(self.dem), self.cellsize, want)
+
+    def _trace(self, image_to_filter, want):
+        Filter.apply(self, image_to_filter)
+        self._check(image_to_filter, want)
+        operands = [o.to_host() if _is_device_raster(o) else o for o in (self.streams, self.dem)]
+        outs, self.stats = backend.flowtrace(image_to_filter, operands[0], self.threshold,
+                                             operands[1], self.cellsize, want)
+        return outs
+
+    def _trace_device(self, raster, want):
+        self._check(raster, want)
+        operands, mine = [], []
+        try:
+            for o in (self.streams, self.dem):
+                if isinstance(o, np.ndarray):
+                    o = backend.DeviceRaster.from_host(o, dtype=o.dtype, ctx=raster.ctx)
+                    mine.append(o)
+                operands.append(o)
+            outs, self.stats = backend.flowtrace_dev(raster, operands[0], self.threshold,
+                                                     operands[1], self.cellsize, want)
+        finally:
+            for o in mine:
+                o.free()
+        return outs
+
+
+class FlowDistance(_FlowTrace):  # pylint: disable=too-few-public-methods
+    """Downstream D8 flow length (new operator).  Input: a uint8 H x W raster of ESRI D8 codes
+    exactly as ``FlowAccumulation`` takes them.  Returns float32: the length of the cell's D8
+    path down to the first *stop*, ``ncard * cellsize + ndiag * cellsize * sqrt(2)`` evaluated
+    in float64 and rounded once, with ``ncard`` / ``ndiag`` the cardinal and diagonal steps.
+
+    ``FlowDistance()``: a stop is a terminal cell (code 0 or pointing outside the raster):
+    the distance to the outlet.  ``FlowDistance(streams)``: a stream cell is a stop too
+    (distance to streams); ``streams`` is a bool / uint8 mask of the codes' shape (non-zero =
+    stream), a uint32 raster with ``threshold`` (stream where ``>= threshold``: a
+    ``FlowAccumulation`` result goes in as it is), or a ``DeviceRaster`` of uint8 or uint32.
+    A cell whose path ends in a terminal cell that is no stream cell is unreached and reads
+    NaN, and so does that terminal cell.
+
+    ``ValueError`` for operands of another type, dtype or shape, ``threshold`` without a
+    uint32 raster, with a mask, or < 1, a ``cellsize`` that is not finite and positive (all
+    before the device is touched), a byte that is not a D8 code, codes that form a cycle (a
+    loop that holds a stream cell is legal) and more than 2^32 - 1 cells.  Exact, identical
+    from run to run.
+
+    Attributes
+    ----------
+    stats : dict
+        stops (stream and terminal cells), unreached (cells), exits, forest_rounds,
+        tile_h / tile_w of the last call; phase times when profiling is on.
+    """
+
+    def __init__(self, streams=None, *, threshold=None, cellsize=1.0):
+        self._set_operands(streams, threshold, None, cellsize)
+
+    def apply(self, image_to_filter):
+        return self._trace(image_to_filter, ("distance",))["distance"]
+
+    def apply_device(self, raster):
+        return self._trace_device(raster, ("distance",))["distance"]
+
+
+class HeightAboveDrainage(_FlowTrace):  # pylint: disable=too-few-public-methods
+    """Height above the nearest drainage, HAND (new operator).  Input: uint8 D8 codes as
+    ``FlowDistance`` takes them.  Returns float32 ``dem[c] - dem[s(c)]``, one float32
+    subtraction, ``s(c)`` the first stream cell on ``c``'s D8 path (``c`` included), and NaN
+    where the path ends without meeting one.  NaN in ``dem`` propagates by arithmetic.
+
+    ``dem``: float32 array or ``DeviceRaster`` of the codes' shape; ``streams``,
+    ``threshold``, ``cellsize`` and the errors as for ``FlowDistance``.  With
+    ``keep_partial_results=True`` the same call also leaves ``distance`` (the
+    ``FlowDistance(streams)`` raster) and ``drainage`` (uint32: 1 + flat index of ``s(c)``, 0
+    where unreached) -- host arrays after ``apply``, device rasters after ``apply_device``;
+    otherwise both are ``None``.
+    """
+
+    def __init__(self, *, dem, streams, threshold=None, cellsize=1.0,
+                 keep_partial_results=False):
+        if dem is None:
+            raise ValueError("HeightAboveDrainage needs the dem it is measured on")
+        if streams is None:
+            raise ValueError("HeightAboveDrainage needs streams (a mask, or a uint32 raster "
+                             "with a threshold)")
+        self._set_operands(streams, threshold, dem, cellsize)
+        self.keep_partial_results = keep_partial_results
+        self.distance = self.drainage = None
+
+    def _keep(self, outs):
+        self.distance, self.drainage = outs.get("distance"), outs.get("stop")
+        return outs["hand"]
+
+    def _want(self):
+        return ("stop", "distance", "hand") if self.keep_partial_results else ("hand",)
+
+    def apply(self, image_to_filter):
+        return self._keep(self._trace(image_to_filter, self._want()))
+
+    def apply_device(self, raster):
+        return self._keep(self._trace_device(raster, self._want()))
+
+
 class HydroConditioning(ComposedFilter):  # pylint: disable=too-few-public-methods
     """``SinkFill`` then ``D8FlowDirection`` as one device-resident chain (the
     pair BASELINE.json's metric is quoted on).  ``filled`` keeps the filled
@@ -552,6 +693,77 @@ class HydroConditioning(ComposedFilter):  # pylint: disable=too-few-public-metho
                     out[k] = (w_all[y0:y0 + h], d)
         fill.stats = stats or {}
         return out
+
+
+class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
+    """A float32 DEM to its height above the nearest drainage in one device-resident chain:
+    ``SinkFill(epsilon)`` and ``D8FlowDirection`` (one call, as in ``HydroConditioning``),
+    ``FlowAccumulation``, then ``HeightAboveDrainage`` relative to the **filled** DEM with
+    streams where the accumulation is ``>= threshold``.  Nothing is downloaded in between.
+
+    ``stats`` maps ``SinkFill``, ``FlowAccumulation`` and ``HeightAboveDrainage`` to the
+    stats of their stage.  With ``keep_partial_results=True`` the last call leaves
+    ``filled``, ``codes``, ``accumulation`` and ``distance`` (distance to the streams): host
+    arrays after ``apply``, device rasters (the caller's to free) after ``apply_device``;
+    otherwise they are ``None``.  ``epsilon > 0`` makes the D8 paths of the filled DEM descend
+    strictly, so that they cross what were flats and pits."""
+
+    def __init__(self, *, threshold, epsilon=1e-3, cellsize=1.0, keep_partial_results=False):
+        super().__init__()
+        # the checks of the trace's operands, on stand-ins of the types the chain makes
+        HeightAboveDrainage(dem=np.zeros((1, 1), np.float32),
+                            streams=np.zeros((1, 1), np.uint32), threshold=threshold,
+                            cellsize=cellsize)
+        self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection(), FlowAccumulation()]
+        self.threshold, self.cellsize = threshold, cellsize
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.filled = self.codes = self.accumulation = self.distance = None
+
+    def _check(self, dtype, ndim):
+        if dtype != np.float32:
+            raise ValueError(f"DemToHAND takes a float32 DEM, got {dtype}")
+        if ndim != 2:
+            raise ValueError(f"DemToHAND takes a 2-D raster, got {ndim} dimensions")
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        self._check(image_to_filter.dtype, image_to_filter.ndim)
+        with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z:
+            with self.apply_device(z) as hand:
+                out = hand.to_host()
+        if self.keep_partial_results:
+            for name in ("filled", "codes", "accumulation", "distance"):
+                with getattr(self, name) as raster:
+                    setattr(self, name, raster.to_host())
+        return out
+
+    def apply_device(self, raster):
+        self._check(raster.dtype, len(raster.shape))
+        fill, _, accumulate = self.filters
+        self.filled = self.codes = self.accumulation = self.distance = None
+        kept = []
+        filled, codes, fill.stats = backend.sinkfill_d8_dev(
+            raster, eps=fill.epsilon, max_rounds=fill.max_rounds)
+        kept += [filled, codes]
+        try:
+            acc, accumulate.stats = backend.flowacc_dev(codes)
+            kept.append(acc)
+            trace = HeightAboveDrainage(dem=filled, streams=acc, threshold=self.threshold,
+                                        cellsize=self.cellsize,
+                                        keep_partial_results=self.keep_partial_results)
+            hand = trace.apply_device(codes)
+            self.stats = {"SinkFill": fill.stats, "FlowAccumulation": accumulate.stats,
+                          "HeightAboveDrainage": trace.stats}
+            if self.keep_partial_results:
+                trace.drainage.free()
+                self.filled, self.codes, self.accumulation = kept
+                self.distance = trace.distance
+                kept = []
+            return hand
+        finally:
+            for r in kept:
+                r.free()
 
 
 # ---------------------------------------------------------------------------

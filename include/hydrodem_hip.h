@@ -471,6 +471,67 @@ int hdem_watershed_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W,
                           const uint32_t *seeds, int flags, uint32_t *out, uint32_t *outlets,
                           hdem_watershed_stats *stats);  /* device pointers */
 
+/* ---- A7  FlowDistance.apply / HeightAboveDrainage.apply  (new operators: D8 flow trace) --
+ * d8: uint8 ESRI codes exactly as hdem_flowacc_u8 takes them (0, or a code pointing outside
+ * the raster, is terminal; any byte that is not a code is invalid).
+ * A stop is a terminal cell or, when streams are given, a stream cell.  For every cell c the
+ * call follows c's D8 path, c included, to the first stop s(c) and counts the cardinal
+ * (E, S, W, N) and diagonal (SE, SW, NW, NE) steps taken, ncard(c) and ndiag(c); a stop has
+ * s = itself and both counts 0.
+ *   stream_kind == HDEM_FT_STREAMS_NONE     streams == NULL, threshold == 0: every path ends at
+ *       a terminal cell (distance to the outlet); no cell is unreached.
+ *   stream_kind == HDEM_FT_STREAMS_MASK_U8  streams is uint8 H x W, non-zero = stream;
+ *       threshold == 0.
+ *   stream_kind == HDEM_FT_STREAMS_ACC_U32  streams is uint32 H x W (a flow accumulation as
+ *       hdem_flowacc_u8 writes it), stream <=> streams[c] >= threshold, threshold >= 1.
+ * With streams, a cell whose stop is a terminal cell that is no stream cell is unreached, and
+ * so is that terminal cell.
+ * Outputs, all H x W, each may be NULL (not wanted), at least one must not be:
+ *   stop      uint32   1 + flat index (y * W + x) of s(c); 0 for an unreached cell
+ *   ncard     uint32   cardinal steps; for an unreached cell those to the terminal cell the
+ *   ndiag     uint32   diagonal steps    path ends in
+ *   distance  float32  (float)((double)ncard * cellsize + (double)ndiag * (cellsize * sqrt(2.0))),
+ *                      one rounding per operation, no fused multiply-add; NaN when unreached
+ *   hand      float32  dem[c] - dem[s(c)], one float32 subtraction; NaN when unreached.  Needs
+ *                      dem, float32 H x W; NaN in dem propagates by arithmetic.
+ * dem may be NULL when hand is.  cellsize must be finite and > 0.  flags must be 0.
+ * Exact, identical from run to run.  HDEM_ERR_BAD_ARG, in bounded time, for an invalid byte,
+ * for codes that form a cycle ("N cells never resolve"; a loop that holds a stream cell ends
+ * there and is legal), for the argument combinations excluded above and -- before any
+ * allocation or launch -- for H * W > 2^32 - 1.  On error the contents of the outputs are
+ * unspecified.
+ * Workspace: about 8.0 B per cell from the context's arena (6 B per cell, two arrays of
+ * 16-byte nodes per tile-perimeter slot).  The _dev form synchronises the context's stream to
+ * read its validity counters.  stats may be NULL; otherwise the caller sets
+ * stats->struct_size = sizeof(hdem_flowtrace_stats) first (56 bytes in this version; a shorter
+ * struct is filled as far as it goes).  The three phase times are filled only while profiling
+ * is on (hdem_profile_enable); the call has no kernel id. */
+#define HDEM_FT_STREAMS_NONE 0
+#define HDEM_FT_STREAMS_MASK_U8 1
+#define HDEM_FT_STREAMS_ACC_U32 2
+typedef struct hdem_flowtrace_stats {
+    uint32_t struct_size;   /* in: sizeof(hdem_flowtrace_stats), set by the caller          */
+    int32_t forest_rounds;  /* pointer-jumping launches of phase B that had work to do      */
+    int64_t stops;          /* stop cells: stream cells and terminal cells                  */
+    int64_t unreached;      /* cells whose path ends in a terminal cell that is no stream   */
+    int64_t exits;          /* cells that are no stop and drain into another tile           */
+    int32_t tile_h, tile_w;
+    float ms_tile;          /* phase A: in-tile pointer doubling (HIP events; profiling)    */
+    float ms_forest;        /* phase B: the forest of perimeter slots                       */
+    float ms_final;         /* phase C: outputs written                                     */
+    int32_t reserved;       /* 0                                                            */
+} hdem_flowtrace_stats;     /* sizeof == 56 */
+int hdem_flowtrace_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *streams,
+                      int stream_kind, uint32_t threshold, const float *dem, double cellsize,
+                      uint32_t *stop, uint32_t *ncard, uint32_t *ndiag, float *distance,
+                      float *hand, int flags,
+                      hdem_flowtrace_stats *stats);      /* host pointers, synchronous */
+int hdem_flowtrace_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *streams,
+                          int stream_kind, uint32_t threshold, const float *dem,
+                          double cellsize, uint32_t *stop, uint32_t *ncard, uint32_t *ndiag,
+                          float *distance, float *hand, int flags,
+                          hdem_flowtrace_stats *stats);  /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
