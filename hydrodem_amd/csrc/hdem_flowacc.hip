@@ -1,9 +1,9 @@
 // D8 flow accumulation (new operator; FlowAccumulation).
 //
 // acc[c] = number of cells whose D8 path passes through c, c itself included: the unique
-// solution of acc[c] = 1 + sum acc[d] over the neighbours d whose code points at c.  Codes
-// are ESRI (E=1, SE=2, S=4, SW=8, W=16, NW=32, N=64, NE=128); 0, or a code pointing outside
-// the raster, makes a cell terminal.  Integers: bit-exact whatever order the adds land in.
+// solution of acc[c] = 1 + sum acc[d] over the neighbours d whose code points at c.  The
+// codes, what makes a cell terminal, the tiles and their perimeter slots are those of
+// hdem_d8tile.h.  Integers: bit-exact whatever order the adds land in.
 //
 // A GPU form of Barnes' tiled accumulation (2017).  Four launches whatever the length of the
 // longest path, and no workgroup ever waits on another:
@@ -21,19 +21,14 @@
 //      writes acc.  Also counts what never completed (a cycle).
 // Every walk step completes one arrival on one node, so every loop is bounded by the
 // nodes it completes (and, explicitly, by the node count).
-#include "hdem_internal.h"
-
-#include <algorithm>
+#include "hdem_d8tile.h"
 
 namespace {
 
 constexpr int NT = 256;               // threads per forest workgroup
 constexpr int TNT = 512;              // threads per tile workgroup (8 cells each; 256: 1.6x
                                       // slower, the walks of a thread run one after another)
-constexpr int TS = 64;                // tile edge
-constexpr int TC = TS * TS;           // cells per tile (12-bit local index)
 constexpr int HS = TS + 2;            // staged tile with its one-cell halo
-constexpr int PER = 4 * TS - 4;       // perimeter slots per tile
 constexpr uint16_t EXIT = 0xFFFE;     // rl[]: receiver in a neighbouring tile
 constexpr uint16_t TERM = 0xFFFF;     // rl[]: terminal (code 0, leaves the raster, invalid, outside)
 constexpr uint8_t OUTSIDE = 0xFF;     // indeg[]: cell of a partial tile beyond the raster
@@ -46,33 +41,6 @@ struct flowacc_counters {
     unsigned long long stuck_exits;   // forest nodes whose donors never all arrived
     int max_hops;                     // longest B2 walk
 };
-
-// bit b of a code -> (dy, dx), packed (d + 1) in 4 bits per entry
-__device__ __forceinline__ int code_dy(int b) { return ((0x00012221u >> (4 * b)) & 3) - 1; }
-__device__ __forceinline__ int code_dx(int b) { return ((0x21000122u >> (4 * b)) & 3) - 1; }
-
-// perimeter slot of a frame cell: top row, bottom row, left column, right column
-__device__ __forceinline__ int perim_pos(int ly, int lx)
-{
-    return ly == 0 ? lx : ly == TS - 1 ? TS + lx : lx == 0 ? 2 * TS + ly - 1 : 3 * TS - 2 + ly - 1;
-}
-__device__ __forceinline__ void perim_cell(int p, int &ly, int &lx)
-{
-    if (p < TS) { ly = 0; lx = p; }
-    else if (p < 2 * TS) { ly = TS - 1; lx = p - TS; }
-    else if (p < 3 * TS - 2) { ly = p - 2 * TS + 1; lx = 0; }
-    else { ly = p - (3 * TS - 2) + 1; lx = TS - 1; }
-}
-
-// Slot of local frame position (ny, nx) that may lie one cell outside tile (ty, tx): the
-// perimeter slot of that cell in the tile that holds it.
-__device__ __forceinline__ int64_t slot_of(int ty, int tx, int tiles_x, int ny, int nx)
-{
-    const int sy = ny < 0 ? -1 : ny >= TS ? 1 : 0;
-    const int sx = nx < 0 ? -1 : nx >= TS ? 1 : 0;
-    const int64_t tile = (int64_t)(ty + sy) * tiles_x + (tx + sx);
-    return tile * PER + perim_pos(ny - sy * TS, nx - sx * TS);
-}
 
 template <bool FINAL>
 __global__ __launch_bounds__(TNT) void flowacc_tile_kernel(
@@ -87,10 +55,9 @@ __global__ __launch_bounds__(TNT) void flowacc_tile_kernel(
     __shared__ unsigned int s_cnt[3];       // invalid codes, stuck cells, stuck exits
 
     const int tid = threadIdx.x;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-    const int y0 = ty * TS, x0 = tx * TS;
-    const int th = min(TS, H - y0), tw = min(TS, W - x0);
-    const int64_t base = (int64_t)blockIdx.x * PER;
+    const d8_tile tile = d8_tile_of_block(tiles_x, H, W);
+    const int y0 = tile.y0, x0 = tile.x0;
+    const int64_t base = tile.base;
 
     if (tid < 3) s_cnt[tid] = 0;
     for (int i = tid; i < HS * HS; i += TNT) {
@@ -104,30 +71,21 @@ __global__ __launch_bounds__(TNT) void flowacc_tile_kernel(
     unsigned int bad = 0;
     for (int i = tid; i < TC; i += TNT) {
         const int ly = i / TS, lx = i % TS;
-        if (ly >= th || lx >= tw) {
+        if (!tile.inside(ly, lx)) {
             rl[i] = TERM;
             indeg[i] = OUTSIDE;
             continue;
         }
-        const int c = code[(ly + 1) * HS + lx + 1];
-        uint16_t r = TERM;
-        if (c & (c - 1)) {
-            ++bad;
-        } else if (c) {
-            const int b = __builtin_ctz(c);
-            const int ny = ly + code_dy(b), nx = lx + code_dx(b);
-            const int gy = y0 + ny, gx = x0 + nx;
-            if (gy >= 0 && gy < H && gx >= 0 && gx < W)
-                r = (ny >= 0 && ny < TS && nx >= 0 && nx < TS) ? (uint16_t)(ny * TS + nx) : EXIT;
-        }
-        rl[i] = r;
+        const d8_step s = d8_decode(code[(ly + 1) * HS + lx + 1], ly, lx, tile, H, W);
+        if (s.invalid) ++bad;
+        rl[i] = s.terminal ? TERM : s.in_tile() ? (uint16_t)(s.ny * TS + s.nx) : EXIT;
         int deg = 0;
         uint32_t seed = 1;
         for (int b = 0; b < 8; ++b) {
             const int ny = ly - code_dy(b), nx = lx - code_dx(b);   // a donor in direction b
             if (code[(ny + 1) * HS + nx + 1] != (1 << b)) continue;
             if (ny >= 0 && ny < TS && nx >= 0 && nx < TS) ++deg;
-            else if (FINAL) seed += (uint32_t)word[slot_of(ty, tx, tiles_x, ny, nx)];
+            else if (FINAL) seed += (uint32_t)word[slot_of(tile, tiles_x, ny, nx)];
         }
         indeg[i] = (uint8_t)deg;
         acc[i] = seed;
@@ -183,12 +141,12 @@ __global__ __launch_bounds__(TNT) void flowacc_tile_kernel(
     if (tid < PER) {
         perim_cell(tid, p_ly, p_lx);
         p_cell = p_ly * TS + p_lx;
-        p_in = p_ly < th && p_lx < tw;
+        p_in = tile.inside(p_ly, p_lx);
         const bool is_exit = p_in && rl[p_cell] == EXIT;
         int32_t to = -1;
         if (is_exit) {
             const int b = __builtin_ctz(code[(p_ly + 1) * HS + p_lx + 1]);
-            to = (int32_t)slot_of(ty, tx, tiles_x, p_ly + code_dy(b), p_lx + code_dx(b));
+            to = (int32_t)slot_of(tile, tiles_x, p_ly + code_dy(b), p_lx + code_dx(b));
         }
         word[base + tid] = is_exit ? (uint32_t)acc[p_cell] : 0u;
         indeg_b[base + tid] = 0;
@@ -296,17 +254,10 @@ extern "C" int hdem_flowacc_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int 
 {
     HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
     if (int rc = hdem_check_raster(d8, out, H, W)) return rc;
-    const int64_t cells = (int64_t)H * W;
-    HDEM_REQUIRE(cells <= (int64_t)UINT32_MAX, HDEM_ERR_BAD_ARG,
-                 "flow accumulation counts in uint32: %d x %d = %lld cells is more than 2^32 - 1",
-                 H, W, (long long)cells);
-    const int tiles_y = (H + TS - 1) / TS, tiles_x = (W + TS - 1) / TS;
-    const int64_t tiles = (int64_t)tiles_y * tiles_x;
-    const int64_t nslots = tiles * PER;
-    // (slots are int32; only rasters a few cells wide and ~10^9 long get here)
-    HDEM_REQUIRE(nslots <= INT32_MAX, HDEM_ERR_BAD_ARG,
-                 "flow accumulation: %d x %d has %lld tiles of %d x %d, more than %d", H, W,
-                 (long long)tiles, TS, TS, INT32_MAX / PER);
+    d8_grid g;
+    if (int rc = d8_grid_of("flow accumulation", H, W, &g)) return rc;
+    const int64_t cells = (int64_t)H * W, tiles = g.tiles, nslots = g.nslots;
+    const int tiles_x = g.tiles_x;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     if (stats) *stats = hdem_flowacc_stats{};
 
@@ -322,28 +273,26 @@ extern "C" int hdem_flowacc_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int 
     int32_t *tgt = link + nslots;
     int32_t *next = tgt + nslots;
 
-    hipEvent_t ev[4] = {};
-    const bool phases = ctx->profiling && stats;
-    for (int k = 0; phases && k < 4; ++k) HDEM_HIP_CHECK(hipEventCreate(&ev[k]));
-    auto mark = [&](int k) { if (phases) (void)hipEventRecord(ev[k], ctx->stream); };
+    d8_phase_timer phases(ctx, stats != nullptr);
+    if (int rc = phases.start()) return rc;
 
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(flowacc_counters), ctx->stream));
     const int64_t forest_blocks = (nslots + NT - 1) / NT;
     const int degree_blocks = (int)std::min<int64_t>(forest_blocks, (int64_t)ctx->num_cus * 8);
     {
         hdem_scoped_timer tm(ctx, HDEM_K_FLOWACC, cells);
-        mark(0);
+        phases.mark(0);
         hipLaunchKernelGGL(flowacc_tile_kernel<false>, dim3((unsigned)tiles), dim3(TNT), 0,
                            ctx->stream, d8, H, W, tiles_x, out, word, indeg_b, link, tgt, cnt);
-        mark(1);
+        phases.mark(1);
         hipLaunchKernelGGL(flowacc_forest_degree_kernel, dim3(degree_blocks), dim3(NT), 0,
                            ctx->stream, nslots, tgt, link, next, indeg_b, cnt);
         hipLaunchKernelGGL(flowacc_forest_walk_kernel, dim3((unsigned)forest_blocks), dim3(NT), 0,
                            ctx->stream, nslots, tgt, next, indeg_b, word, cnt);
-        mark(2);
+        phases.mark(2);
         hipLaunchKernelGGL(flowacc_tile_kernel<true>, dim3((unsigned)tiles), dim3(TNT), 0,
                            ctx->stream, d8, H, W, tiles_x, out, word, indeg_b, link, tgt, cnt);
-        mark(3);
+        phases.mark(3);
     }
     HDEM_HIP_CHECK(hipGetLastError());
     flowacc_counters host = {};
@@ -354,16 +303,9 @@ extern "C" int hdem_flowacc_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int 
         stats->max_hops = host.max_hops;
         stats->tile_h = TS;
         stats->tile_w = TS;
-        if (phases) {
-            (void)hipEventElapsedTime(&stats->ms_tile, ev[0], ev[1]);
-            (void)hipEventElapsedTime(&stats->ms_forest, ev[1], ev[2]);
-            (void)hipEventElapsedTime(&stats->ms_final, ev[2], ev[3]);
-        }
+        phases.read(&stats->ms_tile, &stats->ms_forest, &stats->ms_final);
     }
-    for (int k = 0; phases && k < 4; ++k) (void)hipEventDestroy(ev[k]);
-    HDEM_REQUIRE(!host.bad, HDEM_ERR_BAD_ARG,
-                 "invalid D8 code in %llu cells: a code is 0 or one of 1, 2, 4, ..., 128",
-                 host.bad);
+    if (int rc = d8_report_invalid(host.bad)) return rc;
     HDEM_REQUIRE(!host.stuck_cells && !host.stuck_exits, HDEM_ERR_BAD_ARG,
                  "flow directions form a cycle: %llu cells never drain (%llu of them inside "
                  "tiles, %llu tile exits)",
@@ -376,12 +318,10 @@ extern "C" int hdem_flowacc_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, u
 {
     HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
     if (int rc = hdem_check_raster(d8, out, H, W)) return rc;
-    const int64_t cells = (int64_t)H * W;
-    HDEM_REQUIRE(cells <= (int64_t)UINT32_MAX, HDEM_ERR_BAD_ARG,
-                 "flow accumulation counts in uint32: %d x %d = %lld cells is more than 2^32 - 1",
-                 H, W, (long long)cells);
+    d8_grid g;
+    if (int rc = d8_grid_of("flow accumulation", H, W, &g)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)cells;
+    const size_t n = (size_t)H * W;
     hdem_dbuf dd8, dout;
     if (int rc = dd8.alloc(ctx, n)) return rc;
     if (int rc = dout.alloc(ctx, n * sizeof(uint32_t))) return rc;

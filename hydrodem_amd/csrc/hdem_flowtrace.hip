@@ -7,8 +7,9 @@
 // *dry*: it and everything that ends in it are unreached (stop 0, distance and HAND NaN, the
 // counts still those to the terminal).  "First stop downstream" and "steps to it" compose
 // along a path, (stop, n) o (stop', n') = (stop', n + n'), so the scheme is that of
-// hdem_watershed.hip with a payload on every pointer: 64 x 64 tiles, 252 perimeter slots per
-// tile, a forest over the slots, pointer jumping, no atomics on the data path.
+// hdem_watershed.hip with a payload on every pointer: the codes, 64 x 64 tiles, 252 perimeter
+// slots per tile and a forest over the slots of hdem_d8tile.h, pointer jumping, no atomics on
+// the data path.
 //   A  (flowtrace_tile_kernel)   per tile: every cell's in-tile receiver, then Jacobi pointer
 //      doubling in LDS on 64-bit words (pointer | ncard << 16 | ndiag << 32; a path inside a
 //      tile has at most 4095 steps) until every cell points at a stop or at an *exit* (a
@@ -29,11 +30,9 @@
 //      the same counts which array holds the result.
 //   C  (flowtrace_final_kernel)  per tile, streaming: the tile's 252 resolved nodes in LDS,
 //      6 B per cell in, 4 B per cell and wanted output out.  HAND gathers dem[s(c)].
-#include "hdem_internal.h"
+#include "hdem_d8tile.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstring>
 
 namespace {
 
@@ -42,15 +41,9 @@ constexpr int TNT = 1024;             // threads per tile workgroup (4 cells eac
                                       // allows two workgroups per CU whatever their size: A at
                                       // 16384^2 takes 3.48 ms with 256, 2.17 with 512, 1.72
                                       // with 1024)
-constexpr int TS = 64;                // tile edge
-constexpr int TC = TS * TS;           // cells per tile (12-bit local index)
-constexpr int PER = 4 * TS - 4;       // perimeter slots per tile
-constexpr int DOUBLINGS = 12;         // 2^12 >= the longest path inside a tile (4095 steps)
 constexpr int JUMPS = 4;              // forest jumps per node and launch, all in the source
                                       // array (B at 16384^2, distance to the outlet: 1.01 ms
                                       // with 1, 0.71 with 2, 0.54 with 4)
-constexpr int MAX_ROUNDS = 32;        // forest launches: slots < 2^31
-constexpr uint16_t T_EXIT = 0x8000;   // per-cell target: perimeter slot of the exit reached
 constexpr uint32_t C_DRY = 1u << 31;  // per-cell counts word: the stop reached is a dry terminal
 constexpr uint32_t RESOLVED = 1u;     // node.y
 
@@ -64,42 +57,10 @@ constexpr uint8_t K_DRY = 3;          // terminal, streams given, no stream cell
 // 0; z = ncard; w = ndiag
 typedef uint4 node_t;
 
-struct flowtrace_counters {
+struct flowtrace_counters : d8_forest_counters {
     unsigned long long stops;         // stop cells (stream cells and terminal cells)
-    unsigned long long exits;         // exit cells (forest pointers of their own)
-    unsigned long long bad;           // cells holding an invalid byte
     unsigned long long unreached;     // cells whose path ends in a dry terminal
-    unsigned long long stuck_cells;   // cells that never reached a stop
-    unsigned long long stuck_slots;   // forest nodes that never resolved
-    unsigned long long unresolved[MAX_ROUNDS];   // forest nodes left after each round
 };
-
-// bit b of a code -> (dy, dx), packed (d + 1) in 4 bits per entry; odd bits are diagonal
-__device__ __forceinline__ int code_dy(int b) { return ((0x00012221u >> (4 * b)) & 3) - 1; }
-__device__ __forceinline__ int code_dx(int b) { return ((0x21000122u >> (4 * b)) & 3) - 1; }
-
-// perimeter slot of a frame cell: top row, bottom row, left column, right column
-__device__ __forceinline__ int perim_pos(int ly, int lx)
-{
-    return ly == 0 ? lx : ly == TS - 1 ? TS + lx : lx == 0 ? 2 * TS + ly - 1 : 3 * TS - 2 + ly - 1;
-}
-__device__ __forceinline__ void perim_cell(int p, int &ly, int &lx)
-{
-    if (p < TS) { ly = 0; lx = p; }
-    else if (p < 2 * TS) { ly = TS - 1; lx = p - TS; }
-    else if (p < 3 * TS - 2) { ly = p - 2 * TS + 1; lx = 0; }
-    else { ly = p - (3 * TS - 2) + 1; lx = TS - 1; }
-}
-
-// Slot of local frame position (ny, nx) that lies one cell outside tile (ty, tx): the
-// perimeter slot of that cell in the tile that holds it.
-__device__ __forceinline__ int64_t slot_of(int ty, int tx, int tiles_x, int ny, int nx)
-{
-    const int sy = ny < 0 ? -1 : ny >= TS ? 1 : 0;
-    const int sx = nx < 0 ? -1 : nx >= TS ? 1 : 0;
-    const int64_t tile = (int64_t)(ty + sy) * tiles_x + (tx + sx);
-    return tile * PER + perim_pos(ny - sy * TS, nx - sx * TS);
-}
 
 // LDS word of A: pointer in bits 0-15, ncard in 16-31, ndiag in 32-47.  A stop or an exit
 // holds (itself, 0, 0), so composing "a then b" is one addition of b to a's counts.
@@ -120,10 +81,8 @@ __global__ __launch_bounds__(TNT) void flowtrace_tile_kernel(
     __shared__ unsigned int s_cnt[4];            // invalid codes, stops, exits, stuck cells
 
     const int tid = threadIdx.x;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-    const int y0 = ty * TS, x0 = tx * TS;
-    const int th = min(TS, H - y0), tw = min(TS, W - x0);
-    const int64_t base = (int64_t)blockIdx.x * PER;
+    const d8_tile tile = d8_tile_of_block(tiles_x, H, W);
+    const int y0 = tile.y0, x0 = tile.x0;
 
     if (tid < 4) s_cnt[tid] = 0;
     __syncthreads();
@@ -135,29 +94,20 @@ __global__ __launch_bounds__(TNT) void flowtrace_tile_kernel(
         uint8_t k = K_STOP;
         uint64_t w = (uint64_t)i;
         int c = 0;
-        if (ly < th && lx < tw) {
+        if (tile.inside(ly, lx)) {
             const size_t g = (size_t)(y0 + ly) * W + x0 + lx;
             c = d8[g];
             bool stream = false;
             if (STREAMS == 1) stream = static_cast<const uint8_t *>(streams)[g] != 0;
             if (STREAMS == 2) stream = static_cast<const uint32_t *>(streams)[g] >= threshold;
-            bool terminal = true;
-            int ny = 0, nx = 0, b = 0;
-            if (c & (c - 1)) {
-                ++bad;
-            } else if (c) {
-                b = __builtin_ctz(c);
-                ny = ly + code_dy(b);
-                nx = lx + code_dx(b);
-                const int gy = y0 + ny, gx = x0 + nx;
-                terminal = !(gy >= 0 && gy < H && gx >= 0 && gx < W);
-            }
-            if (stream || terminal) {
+            const d8_step s = d8_decode(c, ly, lx, tile, H, W);
+            if (s.invalid) ++bad;
+            if (stream || s.terminal) {
                 k = (STREAMS == 0 || stream) ? K_STOP : K_DRY;
                 ++stops;
-            } else if (ny >= 0 && ny < TS && nx >= 0 && nx < TS) {
+            } else if (s.in_tile()) {
                 k = K_TRAVEL;
-                w = (uint64_t)(ny * TS + nx) | ((b & 1) ? 1ull << 32 : 1ull << 16);
+                w = (uint64_t)(s.ny * TS + s.nx) | ((s.b & 1) ? 1ull << 32 : 1ull << 16);
             } else {
                 k = K_EXIT;
             }
@@ -191,7 +141,7 @@ __global__ __launch_bounds__(TNT) void flowtrace_tile_kernel(
     unsigned int stuck = 0;
     for (int i = tid; i < TC; i += TNT) {
         const int ly = i / TS, lx = i % TS;
-        if (ly >= th || lx >= tw) continue;
+        if (!tile.inside(ly, lx)) continue;
         const uint64_t w = jmp[i];
         const uint32_t t = w_ptr(w);
         const uint8_t k = kind[t];
@@ -208,7 +158,7 @@ __global__ __launch_bounds__(TNT) void flowtrace_tile_kernel(
         int ly, lx;
         perim_cell(tid, ly, lx);
         node_t n = make_uint4(0u, RESOLVED, 0u, 0u);     // outside the raster: never read
-        if (ly < th && lx < tw) {
+        if (tile.inside(ly, lx)) {
             const int i = ly * TS + lx;
             const uint64_t w = jmp[i];
             const int t = (int)w_ptr(w);
@@ -222,15 +172,15 @@ __global__ __launch_bounds__(TNT) void flowtrace_tile_kernel(
                 n.x = 0u;
             } else if (k == K_EXIT) {
                 const int b = __builtin_ctz(code[t]);
-                n.x = (uint32_t)slot_of(ty, tx, tiles_x, t_ly + code_dy(b), t_lx + code_dx(b));
+                n.x = (uint32_t)slot_of(tile, tiles_x, t_ly + code_dy(b), t_lx + code_dx(b));
                 n.y = 0u;
                 if (b & 1) ++n.w; else ++n.z;            // the crossing step
             } else {
-                n = make_uint4((uint32_t)(base + tid), 0u, 0u, 0u);   // a cycle: never resolves
+                n = make_uint4((uint32_t)(tile.base + tid), 0u, 0u, 0u);   // a cycle: unresolved
             }
             if (kind[i] == K_EXIT) atomicAdd(&s_cnt[2], 1u);
         }
-        node[base + tid] = n;
+        node[tile.base + tid] = n;
     }
     __syncthreads();
     if (tid == 0) {
@@ -247,12 +197,8 @@ __global__ __launch_bounds__(NT) void flowtrace_forest_kernel(int64_t nslots, in
                                                               node_t *__restrict__ dst,
                                                               flowtrace_counters *__restrict__ cnt)
 {
-    if (round > 0 && __hip_atomic_load(&cnt->unresolved[round - 1], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT) == 0)
-        return;
     __shared__ unsigned int s_left;
-    if (threadIdx.x == 0) s_left = 0;
-    __syncthreads();
+    if (!d8_forest_begin(cnt, round, &s_left)) return;
     unsigned int left = 0;
     for (int64_t s = (int64_t)blockIdx.x * NT + threadIdx.x; s < nslots;
          s += (int64_t)gridDim.x * NT) {
@@ -264,10 +210,7 @@ __global__ __launch_bounds__(NT) void flowtrace_forest_kernel(int64_t nslots, in
         dst[s] = n;
         left += !(n.y & RESOLVED);
     }
-    for (int m = 32; m >= 1; m >>= 1) left += __shfl_xor(left, m);
-    if ((threadIdx.x & 63) == 0 && left) atomicAdd(&s_left, left);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_left) atomicAdd(&cnt->unresolved[round], (unsigned long long)s_left);
+    d8_forest_end(cnt, round, left, &s_left);
 }
 
 // C.  Every output pointer may be null (not wanted).  cs2 = cellsize * sqrt(2), in double.
@@ -284,9 +227,8 @@ __global__ __launch_bounds__(NT) void flowtrace_final_kernel(
     __shared__ unsigned int s_cnt[3];            // stuck cells, stuck slots, unreached cells
 
     const int tid = threadIdx.x;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-    const int y0 = ty * TS, x0 = tx * TS;
-    const int th = min(TS, H - y0), tw = min(TS, W - x0);
+    const d8_tile tile = d8_tile_of_block(tiles_x, H, W);
+    const int y0 = tile.y0, x0 = tile.x0;
     const uint16_t *tg = target + (size_t)blockIdx.x * TC;
     const uint32_t *ct = counts + (size_t)blockIdx.x * TC;
 
@@ -296,7 +238,7 @@ __global__ __launch_bounds__(NT) void flowtrace_final_kernel(
         // the result, and every later one returned at once
         int r = 0;
         while (r < rounds - 1 && cnt->unresolved[r]) ++r;
-        const node_t n = (((r + 1) & 1) ? node1 : node0)[(int64_t)blockIdx.x * PER + tid];
+        const node_t n = (((r + 1) & 1) ? node1 : node0)[tile.base + tid];
         const bool ok = (n.y & RESOLVED) != 0;
         n_stop[tid] = ok ? n.x : 0u;                     // a slot number is no cell to gather from
         n_nc[tid] = n.z;
@@ -310,7 +252,7 @@ __global__ __launch_bounds__(NT) void flowtrace_final_kernel(
     unsigned int stuck = 0, unreached = 0;
     for (int i = tid; i < TC; i += NT) {
         const int ly = i / TS, lx = i % TS;
-        if (ly >= th || lx >= tw) continue;
+        if (!tile.inside(ly, lx)) continue;
         const size_t g = (size_t)(y0 + ly) * W + x0 + lx;
         const uint16_t v = tg[i];
         const uint32_t c = ct[i];
@@ -344,18 +286,16 @@ __global__ __launch_bounds__(NT) void flowtrace_final_kernel(
     }
 }
 
+// also the tile grid: nothing is allocated for a raster that is refused
 int check_args(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *streams,
                int stream_kind, uint32_t threshold, const float *dem, double cellsize,
                const uint32_t *stop, const uint32_t *ncard, const uint32_t *ndiag,
                const float *distance, const float *hand, int flags,
-               const hdem_flowtrace_stats *stats)
+               const hdem_flowtrace_stats *stats, d8_grid *g)
 {
     HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
     if (int rc = hdem_check_raster(d8, d8, H, W)) return rc;
-    const int64_t cells = (int64_t)H * W;
-    HDEM_REQUIRE(cells <= (int64_t)UINT32_MAX, HDEM_ERR_BAD_ARG,
-                 "flow trace indices are uint32: %d x %d = %lld cells is more than 2^32 - 1", H, W,
-                 (long long)cells);
+    if (int rc = d8_grid_of("flow trace", H, W, g)) return rc;
     HDEM_REQUIRE(!flags, HDEM_ERR_BAD_ARG, "unknown flow trace flags 0x%x", flags);
     HDEM_REQUIRE(stop || ncard || ndiag || distance || hand, HDEM_ERR_BAD_ARG,
                  "no output wanted: give at least one of stop, ncard, ndiag, distance, hand");
@@ -397,24 +337,15 @@ extern "C" int hdem_flowtrace_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
                                      uint32_t *ncard, uint32_t *ndiag, float *distance,
                                      float *hand, int flags, hdem_flowtrace_stats *stats)
 {
+    d8_grid g;
     if (int rc = check_args(ctx, d8, H, W, streams, stream_kind, threshold, dem, cellsize, stop,
-                            ncard, ndiag, distance, hand, flags, stats))
+                            ncard, ndiag, distance, hand, flags, stats, &g))
         return rc;
-    const int tiles_y = (H + TS - 1) / TS, tiles_x = (W + TS - 1) / TS;
-    const int64_t tiles = (int64_t)tiles_y * tiles_x;
-    const int64_t nslots = tiles * PER;
-    // (slots are 31-bit; only rasters a few cells wide and ~10^9 long get here)
-    HDEM_REQUIRE(nslots <= INT32_MAX, HDEM_ERR_BAD_ARG,
-                 "flow trace: %d x %d has %lld tiles of %d x %d, more than %d", H, W,
-                 (long long)tiles, TS, TS, INT32_MAX / PER);
+    const int tiles_x = g.tiles_x;
+    const int64_t tiles = g.tiles, nslots = g.nslots;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
-
-    // what the caller's struct has room for is filled, and nothing beyond it
     hdem_flowtrace_stats st = {};
-    const uint32_t st_size = stats ? std::min<uint32_t>(stats->struct_size, sizeof(st)) : 0;
-    st.struct_size = st_size;
-    auto publish = [&]() { if (stats) memcpy(stats, &st, st_size); };
-    publish();
+    d8_publish(stats, st);
 
     // arena: counters | two node arrays, 16 B per slot each | counts u32 per cell | target
     // u16 per cell
@@ -429,19 +360,14 @@ extern "C" int hdem_flowtrace_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
     uint32_t *counts = reinterpret_cast<uint32_t *>(node[1] + nslots);
     uint16_t *target = reinterpret_cast<uint16_t *>(counts + (size_t)tiles * TC);
 
-    hipEvent_t ev[4] = {};
-    const bool phases = ctx->profiling && stats;
-    for (int k = 0; phases && k < 4; ++k) HDEM_HIP_CHECK(hipEventCreate(&ev[k]));
-    auto mark = [&](int k) { if (phases) (void)hipEventRecord(ev[k], ctx->stream); };
+    d8_phase_timer phases(ctx, stats != nullptr);
+    if (int rc = phases.start()) return rc;
 
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(flowtrace_counters), ctx->stream));
-    int rounds = 1;                               // ceil(log2 nslots) + 1
-    while ((1ll << (rounds - 1)) < nslots) ++rounds;
-    const int64_t forest_blocks = (nslots + NT - 1) / NT;
-    const int forest_grid = (int)std::min<int64_t>(forest_blocks, (int64_t)ctx->num_cus * 8);
+    const d8_forest_plan forest = d8_forest_plan_of(ctx, nslots, NT);
     const dim3 grid((unsigned)tiles);
 
-    mark(0);
+    phases.mark(0);
     if (stream_kind == HDEM_FT_STREAMS_NONE)
         hipLaunchKernelGGL(flowtrace_tile_kernel<0>, grid, dim3(TNT), 0, ctx->stream, d8, streams,
                            threshold, H, W, tiles_x, target, counts, node[0], cnt);
@@ -451,16 +377,16 @@ extern "C" int hdem_flowtrace_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
     else
         hipLaunchKernelGGL(flowtrace_tile_kernel<2>, grid, dim3(TNT), 0, ctx->stream, d8, streams,
                            threshold, H, W, tiles_x, target, counts, node[0], cnt);
-    mark(1);
-    for (int r = 0; r < rounds; ++r)
-        hipLaunchKernelGGL(flowtrace_forest_kernel, dim3(forest_grid), dim3(NT), 0, ctx->stream,
+    phases.mark(1);
+    for (int r = 0; r < forest.rounds; ++r)
+        hipLaunchKernelGGL(flowtrace_forest_kernel, dim3(forest.grid), dim3(NT), 0, ctx->stream,
                            nslots, r, node[r & 1], node[(r + 1) & 1], cnt);
-    mark(2);
+    phases.mark(2);
     const double cs2 = cellsize * std::sqrt(2.0);
     hipLaunchKernelGGL(flowtrace_final_kernel, grid, dim3(NT), 0, ctx->stream, H, W, tiles_x,
-                       rounds, target, counts, node[0], node[1], dem, cellsize, cs2, stop, ncard,
-                       ndiag, distance, hand, cnt);
-    mark(3);
+                       forest.rounds, target, counts, node[0], node[1], dem, cellsize, cs2, stop,
+                       ncard, ndiag, distance, hand, cnt);
+    phases.mark(3);
     HDEM_HIP_CHECK(hipGetLastError());
     flowtrace_counters host = {};
     HDEM_HIP_CHECK(hipMemcpyAsync(&host, cnt, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
@@ -469,25 +395,12 @@ extern "C" int hdem_flowtrace_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
     st.stops = (int64_t)host.stops;
     st.unreached = (int64_t)host.unreached;
     st.exits = (int64_t)host.exits;
-    st.forest_rounds = 1;
-    while (st.forest_rounds < rounds && host.unresolved[st.forest_rounds - 1]) ++st.forest_rounds;
+    st.forest_rounds = d8_forest_rounds(forest, host);
     st.tile_h = TS;
     st.tile_w = TS;
-    if (phases) {
-        (void)hipEventElapsedTime(&st.ms_tile, ev[0], ev[1]);
-        (void)hipEventElapsedTime(&st.ms_forest, ev[1], ev[2]);
-        (void)hipEventElapsedTime(&st.ms_final, ev[2], ev[3]);
-    }
-    publish();
-    for (int k = 0; phases && k < 4; ++k) (void)hipEventDestroy(ev[k]);
-    HDEM_REQUIRE(!host.bad, HDEM_ERR_BAD_ARG,
-                 "invalid D8 code in %llu cells: a code is 0 or one of 1, 2, 4, ..., 128",
-                 host.bad);
-    HDEM_REQUIRE(!host.stuck_cells && !host.stuck_slots, HDEM_ERR_BAD_ARG,
-                 "flow directions form a cycle: %llu cells never resolve (and %llu tile "
-                 "perimeter slots)",
-                 host.stuck_cells, host.stuck_slots);
-    return HDEM_OK;
+    phases.read(&st.ms_tile, &st.ms_forest, &st.ms_final);
+    d8_publish(stats, st);
+    return d8_report_forest(host);
 }
 
 extern "C" int hdem_flowtrace_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W,
@@ -496,8 +409,9 @@ extern "C" int hdem_flowtrace_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W,
                                  uint32_t *ncard, uint32_t *ndiag, float *distance, float *hand,
                                  int flags, hdem_flowtrace_stats *stats)
 {
+    d8_grid g;
     if (int rc = check_args(ctx, d8, H, W, streams, stream_kind, threshold, dem, cellsize, stop,
-                            ncard, ndiag, distance, hand, flags, stats))
+                            ncard, ndiag, distance, hand, flags, stats, &g))
         return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t n = (size_t)H * W;

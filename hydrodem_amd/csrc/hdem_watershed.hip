@@ -5,9 +5,9 @@
 //   outlet mode      label of a terminal cell = 1 + its flat index
 //   pour-point mode  label of a seeded cell = its seed, of an unseeded terminal cell = 0
 //   compact mode     outlet mode renumbered 1 ... K (K terminal cells), outlets[k-1] = index
-// Codes are those of hdem_flowacc.hip, and so is the structure: 64 x 64 tiles, 252 perimeter
-// slots per tile, a forest over the slots.  A label travels down -> up by pointer jumping:
-// plain loads and stores, no arrival counting.
+// The codes, what makes a cell terminal and the structure are those of hdem_d8tile.h: 64 x 64
+// tiles, 252 perimeter slots per tile, a forest over the slots.  A label travels down -> up by
+// pointer jumping: plain loads and stores, no arrival counting.
 //   A  (watershed_tile_kernel)   per tile: every cell's in-tile receiver, then 16-bit pointer
 //      doubling in LDS (<= 12 rounds, leaves when a round changes nothing) until every cell
 //      points at a stop or at an *exit* (an unseeded cell whose receiver lies in a
@@ -28,65 +28,24 @@
 //      schedule and nothing more.
 //   C  (watershed_final_kernel)  per tile, streaming: the tile's 252 resolved words in LDS,
 //      2 B per cell in, 4 B per cell out.  Counts what never resolved (a cycle).
-#include "hdem_internal.h"
-
-#include <algorithm>
-#include <cstring>
+#include "hdem_d8tile.h"
 
 namespace {
 
 constexpr int NT = 256;               // threads per forest / final workgroup
 constexpr int TNT = 512;              // threads per tile workgroup (8 cells each; A takes
                                       // 1.35x as long with 256 and 1.43x with 1024)
-constexpr int TS = 64;                // tile edge
-constexpr int TC = TS * TS;           // cells per tile (12-bit local index)
-constexpr int PER = 4 * TS - 4;       // perimeter slots per tile
-constexpr int DOUBLINGS = 12;         // 2^12 >= the longest path inside a tile (4095 steps)
 constexpr int JUMPS = 4;              // forest jumps per node and launch (B at 16384^2:
                                       // 0.47 ms with 1, 0.39 with 4, 0.49 with 16)
-constexpr int MAX_ROUNDS = 32;        // forest launches: slots < 2^31
 constexpr int SCAN_NT = 1024;
 constexpr uint16_t EXIT = 0xFFFE;     // rl[]: receiver in a neighbouring tile, cell not seeded
 constexpr uint16_t STOP = 0xFFFF;     // rl[]: terminal, seeded, or outside the raster
-constexpr uint16_t T_EXIT = 0x8000;   // per-cell target: perimeter slot of the exit reached
 constexpr uint16_t T_RANK = 0x4000;   // per-cell target, compact mode: a terminal's own rank
 constexpr uint64_t RESOLVED = 1ull << 32;
 
-struct watershed_counters {
+struct watershed_counters : d8_forest_counters {
     unsigned long long terminals;     // terminal cells
-    unsigned long long exits;         // exit cells (forest pointers of their own)
-    unsigned long long bad;           // cells holding an invalid byte
-    unsigned long long stuck_cells;   // cells that never reached a stop
-    unsigned long long stuck_slots;   // forest words that never resolved
-    unsigned long long unresolved[MAX_ROUNDS];   // forest words left after each round
 };
-
-// bit b of a code -> (dy, dx), packed (d + 1) in 4 bits per entry
-__device__ __forceinline__ int code_dy(int b) { return ((0x00012221u >> (4 * b)) & 3) - 1; }
-__device__ __forceinline__ int code_dx(int b) { return ((0x21000122u >> (4 * b)) & 3) - 1; }
-
-// perimeter slot of a frame cell: top row, bottom row, left column, right column
-__device__ __forceinline__ int perim_pos(int ly, int lx)
-{
-    return ly == 0 ? lx : ly == TS - 1 ? TS + lx : lx == 0 ? 2 * TS + ly - 1 : 3 * TS - 2 + ly - 1;
-}
-__device__ __forceinline__ void perim_cell(int p, int &ly, int &lx)
-{
-    if (p < TS) { ly = 0; lx = p; }
-    else if (p < 2 * TS) { ly = TS - 1; lx = p - TS; }
-    else if (p < 3 * TS - 2) { ly = p - 2 * TS + 1; lx = 0; }
-    else { ly = p - (3 * TS - 2) + 1; lx = TS - 1; }
-}
-
-// Slot of local frame position (ny, nx) that lies one cell outside tile (ty, tx): the
-// perimeter slot of that cell in the tile that holds it.
-__device__ __forceinline__ int64_t slot_of(int ty, int tx, int tiles_x, int ny, int nx)
-{
-    const int sy = ny < 0 ? -1 : ny >= TS ? 1 : 0;
-    const int sx = nx < 0 ? -1 : nx >= TS ? 1 : 0;
-    const int64_t tile = (int64_t)(ty + sy) * tiles_x + (tx + sx);
-    return tile * PER + perim_pos(ny - sy * TS, nx - sx * TS);
-}
 
 __device__ __forceinline__ uint64_t word_load(const uint64_t *p)
 {
@@ -111,10 +70,8 @@ __global__ __launch_bounds__(TNT) void watershed_tile_kernel(
     __shared__ unsigned int s_cnt[4];            // invalid codes, terminals, exits, stuck cells
 
     const int tid = threadIdx.x;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-    const int y0 = ty * TS, x0 = tx * TS;
-    const int th = min(TS, H - y0), tw = min(TS, W - x0);
-    const int64_t base = (int64_t)blockIdx.x * PER;
+    const d8_tile tile = d8_tile_of_block(tiles_x, H, W);
+    const int y0 = tile.y0, x0 = tile.x0;
 
     if (tid < 4) s_cnt[tid] = 0;
     __syncthreads();
@@ -126,23 +83,14 @@ __global__ __launch_bounds__(TNT) void watershed_tile_kernel(
         uint16_t r = STOP;
         int c = 0;
         bool terminal = false;
-        if (ly < th && lx < tw) {
+        if (tile.inside(ly, lx)) {
             const size_t g = (size_t)(y0 + ly) * W + x0 + lx;
             c = d8[g];
-            terminal = true;
-            if (c & (c - 1)) {
-                ++bad;
-            } else if (c) {
-                const int b = __builtin_ctz(c);
-                const int ny = ly + code_dy(b), nx = lx + code_dx(b);
-                const int gy = y0 + ny, gx = x0 + nx;
-                if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-                    terminal = false;
-                    if (!seeds || seeds[g] == 0)
-                        r = (ny >= 0 && ny < TS && nx >= 0 && nx < TS) ? (uint16_t)(ny * TS + nx)
-                                                                        : EXIT;
-                }
-            }
+            const d8_step s = d8_decode(c, ly, lx, tile, H, W);
+            if (s.invalid) ++bad;
+            terminal = s.terminal;
+            if (!terminal && (!seeds || seeds[g] == 0))
+                r = s.in_tile() ? (uint16_t)(s.ny * TS + s.nx) : EXIT;
         }
         code[i] = (uint8_t)c;
         rl[i] = r;
@@ -163,7 +111,7 @@ __global__ __launch_bounds__(TNT) void watershed_tile_kernel(
         // a terminal's own target word carries its rank in the tile
         for (int i = tid; i < TC; i += TNT) {
             const int ly = i / TS, lx = i % TS;
-            if (ly >= th || lx >= tw || rl[i] != STOP) continue;
+            if (!tile.inside(ly, lx) || rl[i] != STOP) continue;
             uint32_t before = 0;
             for (int k = 0; k < i / 64; ++k) before += wave_terms[k];
             target[(size_t)blockIdx.x * TC + i] = T_RANK | (uint16_t)(before + jump[1][i]);
@@ -191,7 +139,7 @@ __global__ __launch_bounds__(TNT) void watershed_tile_kernel(
     unsigned int stuck = 0;
     for (int i = tid; i < TC; i += TNT) {
         const int ly = i / TS, lx = i % TS;
-        if (ly >= th || lx >= tw) continue;
+        if (!tile.inside(ly, lx)) continue;
         const uint16_t t = jmp[i];
         const uint16_t k = rl[t];
         if (k < EXIT) ++stuck;                       // still travelling: a cycle inside the tile
@@ -206,7 +154,7 @@ __global__ __launch_bounds__(TNT) void watershed_tile_kernel(
         int ly, lx;
         perim_cell(tid, ly, lx);
         uint64_t w = RESOLVED;                       // outside the raster: never read
-        if (ly < th && lx < tw) {
+        if (tile.inside(ly, lx)) {
             const int i = ly * TS + lx;
             const int t = jmp[i];
             const uint16_t k = rl[t];
@@ -216,13 +164,13 @@ __global__ __launch_bounds__(TNT) void watershed_tile_kernel(
                 w = RESOLVED | (seeds ? seeds[g] : (uint32_t)g + 1u);
             } else if (k == EXIT) {
                 const int b = __builtin_ctz(code[t]);
-                w = (uint64_t)slot_of(ty, tx, tiles_x, t_ly + code_dy(b), t_lx + code_dx(b));
+                w = (uint64_t)slot_of(tile, tiles_x, t_ly + code_dy(b), t_lx + code_dx(b));
             } else {
-                w = (uint64_t)(base + tid);          // a cycle: points at itself, never resolves
+                w = (uint64_t)(tile.base + tid);     // a cycle: points at itself, never resolves
             }
             if (rl[i] == EXIT) atomicAdd(&s_cnt[2], 1u);
         }
-        word[base + tid] = w;
+        word[tile.base + tid] = w;
     }
     __syncthreads();
     if (tid == 0) {
@@ -266,12 +214,8 @@ __global__ __launch_bounds__(NT) void watershed_forest_kernel(int64_t nslots, in
                                                               uint64_t *__restrict__ word,
                                                               watershed_counters *__restrict__ cnt)
 {
-    if (round > 0 && __hip_atomic_load(&cnt->unresolved[round - 1], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT) == 0)
-        return;
     __shared__ unsigned int s_left;
-    if (threadIdx.x == 0) s_left = 0;
-    __syncthreads();
+    if (!d8_forest_begin(cnt, round, &s_left)) return;
     unsigned int left = 0;
     for (int64_t s = (int64_t)blockIdx.x * NT + threadIdx.x; s < nslots;
          s += (int64_t)gridDim.x * NT) {
@@ -282,10 +226,7 @@ __global__ __launch_bounds__(NT) void watershed_forest_kernel(int64_t nslots, in
         }
         left += !(w & RESOLVED);
     }
-    for (int m = 32; m >= 1; m >>= 1) left += __shfl_xor(left, m);
-    if ((threadIdx.x & 63) == 0 && left) atomicAdd(&s_left, left);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_left) atomicAdd(&cnt->unresolved[round], (unsigned long long)s_left);
+    d8_forest_end(cnt, round, left, &s_left);
 }
 
 // C.  MODE 0: outlet, 1: pour points, 2: compact.
@@ -301,21 +242,20 @@ __global__ __launch_bounds__(NT) void watershed_final_kernel(
     __shared__ unsigned int s_cnt[2];            // stuck cells, stuck slots
 
     const int tid = threadIdx.x;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-    const int y0 = ty * TS, x0 = tx * TS;
-    const int th = min(TS, H - y0), tw = min(TS, W - x0);
+    const d8_tile tile = d8_tile_of_block(tiles_x, H, W);
+    const int y0 = tile.y0, x0 = tile.x0;
     const uint16_t *tg = target + (size_t)blockIdx.x * TC;
 
     if (tid < 2) s_cnt[tid] = 0;
     if (tid < PER) {
-        const uint64_t w = word[(int64_t)blockIdx.x * PER + tid];
+        const uint64_t w = word[tile.base + tid];
         uint32_t l = (uint32_t)w;
         const bool ok = (w & RESOLVED) != 0;
         if (MODE == 2 && ok) {
             // the outlet's flat index -> its tile and its rank there
             int ly, lx;
             perim_cell(tid, ly, lx);
-            if (ly < th && lx < tw) {
+            if (tile.inside(ly, lx)) {
                 const uint32_t g = l - 1u;
                 const int gy = (int)(g / (uint32_t)W), gx = (int)(g % (uint32_t)W);
                 const size_t t = (size_t)(gy / TS) * tiles_x + gx / TS;
@@ -331,7 +271,7 @@ __global__ __launch_bounds__(NT) void watershed_final_kernel(
     unsigned int stuck = 0;
     for (int i = tid; i < TC; i += NT) {
         const int ly = i / TS, lx = i % TS;
-        if (ly >= th || lx >= tw) continue;
+        if (!tile.inside(ly, lx)) continue;
         const size_t g = (size_t)(y0 + ly) * W + x0 + lx;
         uint16_t v = tg[i];
         uint32_t l;
@@ -358,15 +298,13 @@ __global__ __launch_bounds__(NT) void watershed_final_kernel(
     }
 }
 
+// also the tile grid: nothing is allocated for a raster that is refused
 int check_args(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const uint32_t *seeds, int flags,
-               uint32_t *out, uint32_t *outlets, hdem_watershed_stats *stats)
+               uint32_t *out, uint32_t *outlets, hdem_watershed_stats *stats, d8_grid *g)
 {
     HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
     if (int rc = hdem_check_raster(d8, out, H, W)) return rc;
-    const int64_t cells = (int64_t)H * W;
-    HDEM_REQUIRE(cells <= (int64_t)UINT32_MAX, HDEM_ERR_BAD_ARG,
-                 "watershed labels are uint32: %d x %d = %lld cells is more than 2^32 - 1", H, W,
-                 (long long)cells);
+    if (int rc = d8_grid_of("watersheds", H, W, g)) return rc;
     HDEM_REQUIRE(!(flags & ~HDEM_WS_COMPACT), HDEM_ERR_BAD_ARG, "unknown watershed flags 0x%x",
                  flags);
     const bool compact = (flags & HDEM_WS_COMPACT) != 0;
@@ -389,23 +327,14 @@ extern "C" int hdem_watershed_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
                                      const uint32_t *seeds, int flags, uint32_t *out,
                                      uint32_t *outlets, hdem_watershed_stats *stats)
 {
-    if (int rc = check_args(ctx, d8, H, W, seeds, flags, out, outlets, stats)) return rc;
+    d8_grid g;
+    if (int rc = check_args(ctx, d8, H, W, seeds, flags, out, outlets, stats, &g)) return rc;
     const bool compact = (flags & HDEM_WS_COMPACT) != 0;
-    const int tiles_y = (H + TS - 1) / TS, tiles_x = (W + TS - 1) / TS;
-    const int64_t tiles = (int64_t)tiles_y * tiles_x;
-    const int64_t nslots = tiles * PER;
-    // (slots are 31-bit; only rasters a few cells wide and ~10^9 long get here)
-    HDEM_REQUIRE(nslots <= INT32_MAX, HDEM_ERR_BAD_ARG,
-                 "watersheds: %d x %d has %lld tiles of %d x %d, more than %d", H, W,
-                 (long long)tiles, TS, TS, INT32_MAX / PER);
+    const int tiles_x = g.tiles_x;
+    const int64_t tiles = g.tiles, nslots = g.nslots;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
-
-    // what the caller's struct has room for is filled, and nothing beyond it
     hdem_watershed_stats st = {};
-    const uint32_t st_size = stats ? std::min<uint32_t>(stats->struct_size, sizeof(st)) : 0;
-    st.struct_size = st_size;
-    auto publish = [&]() { if (stats) memcpy(stats, &st, st_size); };
-    publish();
+    d8_publish(stats, st);
 
     // arena: counters | word u64 per slot | tile offsets u32 per tile | target u16 per cell
     const size_t head = 512;
@@ -418,19 +347,14 @@ extern "C" int hdem_watershed_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
     uint32_t *tile_offset = reinterpret_cast<uint32_t *>(word + nslots);
     uint16_t *target = reinterpret_cast<uint16_t *>(tile_offset + tiles);
 
-    hipEvent_t ev[4] = {};
-    const bool phases = ctx->profiling && stats;
-    for (int k = 0; phases && k < 4; ++k) HDEM_HIP_CHECK(hipEventCreate(&ev[k]));
-    auto mark = [&](int k) { if (phases) (void)hipEventRecord(ev[k], ctx->stream); };
+    d8_phase_timer phases(ctx, stats != nullptr);
+    if (int rc = phases.start()) return rc;
 
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(watershed_counters), ctx->stream));
-    int rounds = 1;                               // ceil(log2 nslots) + 1
-    while ((1ll << (rounds - 1)) < nslots) ++rounds;
-    const int64_t forest_blocks = (nslots + NT - 1) / NT;
-    const int forest_grid = (int)std::min<int64_t>(forest_blocks, (int64_t)ctx->num_cus * 8);
+    const d8_forest_plan forest = d8_forest_plan_of(ctx, nslots, NT);
     const dim3 grid((unsigned)tiles);
 
-    mark(0);
+    phases.mark(0);
     if (compact) {
         hipLaunchKernelGGL(watershed_tile_kernel<true>, grid, dim3(TNT), 0, ctx->stream, d8, seeds,
                            H, W, tiles_x, target, word, tile_offset, cnt);
@@ -440,11 +364,11 @@ extern "C" int hdem_watershed_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
         hipLaunchKernelGGL(watershed_tile_kernel<false>, grid, dim3(TNT), 0, ctx->stream, d8,
                            seeds, H, W, tiles_x, target, word, tile_offset, cnt);
     }
-    mark(1);
-    for (int r = 0; r < rounds; ++r)
-        hipLaunchKernelGGL(watershed_forest_kernel, dim3(forest_grid), dim3(NT), 0, ctx->stream,
+    phases.mark(1);
+    for (int r = 0; r < forest.rounds; ++r)
+        hipLaunchKernelGGL(watershed_forest_kernel, dim3(forest.grid), dim3(NT), 0, ctx->stream,
                            nslots, r, word, cnt);
-    mark(2);
+    phases.mark(2);
     if (compact)
         hipLaunchKernelGGL(watershed_final_kernel<2>, grid, dim3(NT), 0, ctx->stream, seeds, H, W,
                            tiles_x, target, word, tile_offset, out, outlets, cnt);
@@ -454,7 +378,7 @@ extern "C" int hdem_watershed_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
     else
         hipLaunchKernelGGL(watershed_final_kernel<0>, grid, dim3(NT), 0, ctx->stream, seeds, H, W,
                            tiles_x, target, word, tile_offset, out, outlets, cnt);
-    mark(3);
+    phases.mark(3);
     HDEM_HIP_CHECK(hipGetLastError());
     watershed_counters host = {};
     HDEM_HIP_CHECK(hipMemcpyAsync(&host, cnt, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
@@ -462,32 +386,20 @@ extern "C" int hdem_watershed_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
 
     st.basins = (int64_t)host.terminals;
     st.exits = (int64_t)host.exits;
-    st.forest_rounds = 1;
-    while (st.forest_rounds < rounds && host.unresolved[st.forest_rounds - 1]) ++st.forest_rounds;
+    st.forest_rounds = d8_forest_rounds(forest, host);
     st.tile_h = TS;
     st.tile_w = TS;
-    if (phases) {
-        (void)hipEventElapsedTime(&st.ms_tile, ev[0], ev[1]);
-        (void)hipEventElapsedTime(&st.ms_forest, ev[1], ev[2]);
-        (void)hipEventElapsedTime(&st.ms_final, ev[2], ev[3]);
-    }
-    publish();
-    for (int k = 0; phases && k < 4; ++k) (void)hipEventDestroy(ev[k]);
-    HDEM_REQUIRE(!host.bad, HDEM_ERR_BAD_ARG,
-                 "invalid D8 code in %llu cells: a code is 0 or one of 1, 2, 4, ..., 128",
-                 host.bad);
-    HDEM_REQUIRE(!host.stuck_cells && !host.stuck_slots, HDEM_ERR_BAD_ARG,
-                 "flow directions form a cycle: %llu cells never resolve (and %llu tile "
-                 "perimeter slots)",
-                 host.stuck_cells, host.stuck_slots);
-    return HDEM_OK;
+    phases.read(&st.ms_tile, &st.ms_forest, &st.ms_final);
+    d8_publish(stats, st);
+    return d8_report_forest(host);
 }
 
 extern "C" int hdem_watershed_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W,
                                  const uint32_t *seeds, int flags, uint32_t *out,
                                  uint32_t *outlets, hdem_watershed_stats *stats)
 {
-    if (int rc = check_args(ctx, d8, H, W, seeds, flags, out, outlets, stats)) return rc;
+    d8_grid g;
+    if (int rc = check_args(ctx, d8, H, W, seeds, flags, out, outlets, stats, &g)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t n = (size_t)H * W;
     hdem_dbuf dd8, dseeds, dout, doutlets;
@@ -506,10 +418,7 @@ extern "C" int hdem_watershed_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W,
     const int rc = hdem_watershed_u8_dev(ctx, (const uint8_t *)dd8.p, H, W,
                                          (const uint32_t *)dseeds.p, flags, (uint32_t *)dout.p,
                                          (uint32_t *)doutlets.p, &st);
-    if (stats) {
-        st.struct_size = std::min<uint32_t>(stats->struct_size, sizeof(st));
-        memcpy(stats, &st, st.struct_size);
-    }
+    d8_publish(stats, st);
     if (rc) return rc;
     if (outlets)
         if (int rc2 = hdem_memcpy_d2h(ctx, outlets, doutlets.p, (size_t)st.basins * sizeof(uint32_t)))

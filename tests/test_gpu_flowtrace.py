@@ -32,7 +32,8 @@ import pytest
 import hdem_synth
 import hydrodem_amd as hd
 from hydrodem_amd import backend
-from test_flowacc import acc_kahn, random_acyclic_codes, terminal_mask
+from test_flowacc import (CODE_OFFSETS, acc_kahn, random_acyclic_codes, receivers,
+                          terminal_mask)
 from test_flowtrace import distance_of, hand_of, trace_doubling, trace_holds
 from test_gpu_flowacc import path_codes, snake, spiral
 from test_gpu_watersheds import RANDOM_SHAPES, rim_codes
@@ -197,6 +198,54 @@ def test_codes_pointing_outside_the_raster_are_terminal():
     assert np.array_equal(got["stop"], index1((h, w)))
     assert not got["ncard"].any() and not got["ndiag"].any() and not got["distance"].any()
     assert stats["stops"] == h * w
+
+
+def border_rotation_codes(h, w, k):
+    """Every inner cell steps towards the centre cell (code 0 there), so the inner paths cross
+    the tiles and never touch the border; border cell j, counted clockwise from the top left
+    corner, holds entry (j + k) % 9 of (0, E, SE, ..., NE).  Over k = 0 ... 8 every border
+    cell, the corners included, holds every code once: those that leave the raster, those
+    that run along the border, those that point inwards, and 0.  Neighbours on the border
+    hold directions 45 degrees apart, never opposite ones: no cycles."""
+    yy, xx = np.indices((h, w))
+    sy, sx = np.sign(h // 2 - yy), np.sign(w // 2 - xx)
+    codes = np.zeros((h, w), np.uint8)
+    for code, (dy, dx) in CODE_OFFSETS:
+        codes[(sy == dy) & (sx == dx)] = code
+    ring = ([(0, x) for x in range(w)] + [(y, w - 1) for y in range(1, h)]
+            + [(h - 1, x) for x in range(w - 2, -1, -1)] + [(y, 0) for y in range(h - 2, 0, -1)])
+    ys, xs = np.array(ring).T
+    table = np.array((0, E, SE, S, SW, W_, NW, N, NE), np.uint8)
+    codes[ys, xs] = table[(np.arange(len(ring)) + k) % 9]
+    return codes
+
+
+@pytest.mark.parametrize("k", range(9))
+def test_the_three_operators_agree_on_which_cells_are_terminal(k):
+    """Flow accumulation, watersheds and the flow trace share one decoder of a cell's code.
+    The terminal cells that each of them implies are compared with each other and with
+    ``terminal_mask`` on rasters with partial tiles in both axes."""
+    h, w = 2 * 64 + 2, 3 * 64 + 5
+    codes = border_rotation_codes(h, w, k)
+    terminal = terminal_mask(codes)
+    assert terminal[0, 0] == (k not in (1, 2, 3)) and terminal[h // 2, w // 2]   # E, SE, S stay
+    # flow accumulation: acc = 1 + what the donors bring holds in every cell exactly when the
+    # cells whose count enters no other cell's are those without a receiver
+    acc = hd.FlowAccumulation().apply(codes)
+    rec = receivers(codes)
+    inflow = np.zeros(h * w, np.int64)
+    np.add.at(inflow, rec[rec >= 0], acc.ravel()[rec >= 0].astype(np.int64))
+    assert np.array_equal(acc.ravel(), 1 + inflow)
+    assert int(acc[terminal].sum()) == h * w             # every cell ends in one of them
+    assert np.array_equal(rec.reshape(h, w) < 0, terminal)
+    # watersheds, outlet mode: a terminal cell, and no other, carries its own label
+    label = hd.Watersheds().apply(codes)
+    assert np.array_equal(label == index1((h, w)), terminal)
+    # the flow trace without streams: a terminal cell, and no other, is its own stop
+    got, stats = trace(codes)
+    own = (got["stop"] == index1((h, w))) & (got["ncard"] + got["ndiag"] == 0)
+    assert np.array_equal(own, terminal)
+    assert stats["stops"] == int(terminal.sum())
 
 
 # ---------------------------------------------------------------------------

@@ -11,37 +11,24 @@ tests/test_flowacc.py is timed once at 4096^2 on the host.
 """
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import hdem_synth  # noqa: E402
-from hydrodem_amd import backend  # noqa: E402
-
-TILE, PER = 64, 252
+from d8_inputs import TILE, PER, filled_codes, tiles_of
+from hydrodem_amd import backend
 
 
 def modelled_bytes_per_cell(h, w):
     """Codes read twice with their halo, acc written once, and the perimeter slots
     (A writes 20 B, B1 ~16, B2 ~12, C ~16 per slot: 64 B)."""
-    tiles = -(-h // TILE) * -(-w // TILE)
     halo = (TILE + 2) ** 2 / TILE ** 2
-    return 2 * halo + 4 + tiles * PER * 64 / (h * w)
+    return 2 * halo + 4 + tiles_of(h, w) * PER * 64 / (h * w)
 
 
 def run(size, variant, reps, warmup):
     ctx = backend.context()
-    z = hdem_synth.synth_dem(size, size, variant=variant)
-    with backend.DeviceRaster.from_host(z) as dz:
-        del z
-        filled, codes, _ = backend.sinkfill_d8_dev(dz, eps=1e-3)
-    filled.free()
+    codes = filled_codes(size, variant)
     out = backend.DeviceRaster.empty(codes.shape, np.uint32, ctx)
     rows = []
     try:
@@ -70,17 +57,11 @@ def run(size, variant, reps, warmup):
 
 def host_reference(size=4096):
     from test_flowacc import acc_kahn
-    ctx = backend.context()
-    z = hdem_synth.synth_dem(size, size)
-    with backend.DeviceRaster.from_host(z) as dz:
-        filled, codes, _ = backend.sinkfill_d8_dev(dz, eps=1e-3)
-        filled.free()
-        with codes:
-            host_codes = codes.to_host()
+    with filled_codes(size) as codes:
+        host_codes = codes.to_host()
     t = time.perf_counter()
     acc_kahn(host_codes)
     ms = (time.perf_counter() - t) * 1e3
-    del ctx
     return {"size": size, "variant": "rough", "host_numpy_kahn_ms": round(ms, 1)}
 
 

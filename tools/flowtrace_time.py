@@ -22,20 +22,14 @@ on the same host arrays.
 """
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from d8_inputs import PER, filled_dem_and_codes, pour_seeds, tiles_of
+import hydrodem_amd as hd
+from hydrodem_amd import backend
 
-import hdem_synth  # noqa: E402
-import hydrodem_amd as hd  # noqa: E402
-from hydrodem_amd import backend  # noqa: E402
-
-TILE, PER = 64, 252
 THRESHOLDS = {4096: 1000}            # 10 000 elsewhere
 ALL = ("stop", "ncard", "ndiag", "distance", "hand")
 
@@ -46,17 +40,9 @@ def modelled_bytes_per_cell(h, w, streams, outputs, hand, launches):
     every node (the jumps on top hit the cache or do not happen); C reads 6 B per cell and
     the nodes and writes 4 B per output, and HAND reads the cell's own elevation (the
     gathered one is counted as a cache hit: neighbours share their stream cell)."""
-    slots = -(-h // TILE) * -(-w // TILE) * PER * 16 / (h * w)
+    slots = tiles_of(h, w) * PER * 16 / (h * w)
     return (1 + (4 if streams else 0) + 6 + slots, 2 * slots * launches, 6 + slots + 4 * outputs
             + (4 if hand else 0))
-
-
-def filled_dem_and_codes(size, variant="rough"):
-    z = hdem_synth.synth_dem(size, size, variant=variant)
-    with backend.DeviceRaster.from_host(z) as dz:
-        del z
-        filled, codes, _ = backend.sinkfill_d8_dev(dz, eps=1e-3)
-    return filled, codes
 
 
 def median_phases(rows):
@@ -70,12 +56,7 @@ def run(size, reps, warmup, copy_gbs):
     acc, _ = backend.flowacc_dev(codes)
     cut = {False: None, True: threshold}
     cells = size * size
-    rng = np.random.default_rng(size)
-    host_seeds = np.zeros(cells, np.uint32)
-    where = rng.choice(cells, size=cells // 10000, replace=False)
-    host_seeds[where] = np.arange(1, where.size + 1, dtype=np.uint32)
-    seeds = backend.DeviceRaster.from_host(host_seeds.reshape(size, size), dtype=np.uint32)
-    del host_seeds
+    seeds = pour_seeds(size)
     results = []
     try:
         ctx.profile(True)

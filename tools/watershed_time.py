@@ -15,37 +15,19 @@ is timed once at 4096^2 on the host.
 """
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import hdem_synth  # noqa: E402
-from hydrodem_amd import backend  # noqa: E402
-
-TILE, PER = 64, 252
+from d8_inputs import PER, filled_codes, pour_seeds, tiles_of
+from hydrodem_amd import backend
 
 
 def modelled_bytes_per_cell(h, w, pour):
     """A reads the codes (and the seeds), writes 2 B per cell and 8 B per slot; B reads and
     writes the slot words about three times; C reads 2 B per cell and the slot words and
     writes the labels."""
-    tiles = -(-h // TILE) * -(-w // TILE)
-    return 1 + 2 + 2 + 4 + (4 if pour else 0) + tiles * PER * 8 * 5 / (h * w)
-
-
-def filled_codes(size, variant):
-    z = hdem_synth.synth_dem(size, size, variant=variant)
-    with backend.DeviceRaster.from_host(z) as dz:
-        del z
-        filled, codes, _ = backend.sinkfill_d8_dev(dz, eps=1e-3)
-    filled.free()
-    return codes
+    return 1 + 2 + 2 + 4 + (4 if pour else 0) + tiles_of(h, w) * PER * 8 * 5 / (h * w)
 
 
 def time_mode(codes, out, seeds, compact, reps, warmup):
@@ -63,12 +45,7 @@ def run(size, variant, reps, warmup):
     codes = filled_codes(size, variant)
     out = backend.DeviceRaster.empty(codes.shape, np.uint32, ctx)
     cells = size * size
-    rng = np.random.default_rng(size)
-    host_seeds = np.zeros(cells, np.uint32)
-    where = rng.choice(cells, size=cells // 10000, replace=False)
-    host_seeds[where] = np.arange(1, where.size + 1, dtype=np.uint32)
-    seeds = backend.DeviceRaster.from_host(host_seeds.reshape(size, size), dtype=np.uint32)
-    del host_seeds
+    seeds = pour_seeds(size)
     results = []
     try:
         ctx.profile(True)
@@ -101,8 +78,7 @@ def run(size, variant, reps, warmup):
 
 def host_reference(size=4096):
     from test_watersheds import labels_doubling
-    codes = filled_codes(size, "rough")
-    with codes:
+    with filled_codes(size) as codes:
         host_codes = codes.to_host()
     t = time.perf_counter()
     labels_doubling(host_codes)
