@@ -22,7 +22,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      GrovesCorrection, GrovesCorrectionsIter,
                                      PostProcessingFinal, SinkFill,
                                      D8FlowDirection, FlowAccumulation, Watersheds,
-                                     FlowDistance, HeightAboveDrainage,
+                                     FlowDistance, HeightAboveDrainage, ResolveFlats,
                                      HydroConditioning, DemToHAND,
                                      ExpandFilter, IsolatedPoints, BlanksFourier,
                                      DetectBlanksFourier, MaskFourier, FourierInitial,

@@ -111,6 +111,25 @@ class FlowTraceStats(ctypes.Structure):
                 if k not in ("struct_size", "reserved")}
 
 
+class ResolveFlatsStats(ctypes.Structure):
+    """``hdem_resolve_flats_stats``; ``struct_size`` is set on construction, as the C ABI asks."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("rounds", ctypes.c_int32),
+                ("flat_cells", ctypes.c_int64), ("unresolved", ctypes.c_int64),
+                ("tile_visits", ctypes.c_int64), ("max_distance", ctypes.c_uint32),
+                ("active_tiles", ctypes.c_int32),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_classify", ctypes.c_float), ("ms_relax", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_
+                if k not in ("struct_size", "reserved")}
+
+
 # HDEM_FT_STREAMS_*
 FT_STREAMS_NONE, FT_STREAMS_MASK_U8, FT_STREAMS_ACC_U32 = 0, 1, 2
 # outputs of the flow trace, in the order of the C ABI's pointers
@@ -193,6 +212,10 @@ SIGNATURES = {
                           _vp, _vp, _vp, _vp, _vp, _i, _c.POINTER(FlowTraceStats)],
     "hdem_flowtrace_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _vp, _c.c_double,
                               _vp, _vp, _vp, _vp, _vp, _i, _c.POINTER(FlowTraceStats)],
+    "hdem_resolve_flats_u8": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i,
+                              _c.POINTER(ResolveFlatsStats)],
+    "hdem_resolve_flats_u8_dev": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i,
+                                  _c.POINTER(ResolveFlatsStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 
@@ -679,6 +702,46 @@ def flowtrace_dev(codes, streams=None, threshold=None, dem=None, cellsize=1.0,
     return outs, st.as_dict()
 
 
+def resolve_flats_args(codes, dem):
+    """The checks of the flat resolution that need no device: ``codes`` and ``dem`` are
+    anything with ``dtype`` and ``shape`` (NumPy arrays or device rasters)."""
+    if np.dtype(codes.dtype) != np.uint8:
+        raise ValueError(f"flat resolution takes uint8 D8 codes, got {codes.dtype}")
+    shape = tuple(codes.shape)
+    if len(shape) != 2:
+        raise ValueError(f"flat resolution takes a 2-D raster, got {len(shape)} dimensions")
+    if dem is None:
+        raise ValueError("flat resolution needs the dem the codes were made on")
+    if np.dtype(dem.dtype) != np.float32:
+        raise ValueError(f"the dem is float32, got {dem.dtype}")
+    if tuple(dem.shape) != shape:
+        raise ValueError(f"the dem is {tuple(dem.shape)}, the codes {shape}")
+
+
+def resolve_flats_dev(codes, dem, want_distance=False, out=None):
+    """D8 directions across the flats of ``dem`` (``hdem_resolve_flats_u8_dev``): the uint8
+    codes with every flat cell pointed along a shortest equal-elevation path to where its
+    flat drains, the uint32 distance raster (``None`` unless ``want_distance``) and the
+    stats dict.  ``out`` may be ``codes`` itself.  Synchronises once per relaxation round."""
+    resolve_flats_args(codes, dem)
+    c = codes.ctx
+    mine = out is None
+    out = out or DeviceRaster.empty(codes.shape, np.uint8, c)
+    dist = None
+    st = ResolveFlatsStats()
+    try:
+        if want_distance:
+            dist = DeviceRaster.empty(codes.shape, np.uint32, c)
+        c.check(c.lib.hdem_resolve_flats_u8_dev(
+            c.handle, codes.ptr, dem.ptr, codes.shape[0], codes.shape[1], out.ptr,
+            dist.ptr if dist is not None else None, 0, ctypes.byref(st)))
+    except Exception:
+        for r in ([out] if mine else []) + ([dist] if dist is not None else []):
+            r.free()
+        raise
+    return out, dist, st.as_dict()
+
+
 def sinkfill_dev(z, eps=0.0, max_rounds=0, out=None, flags=FILL_INIT):
     _need(z, np.float32)
     out = out or DeviceRaster.empty(z.shape, np.float32, z.ctx)
@@ -1079,6 +1142,24 @@ def flowtrace(codes, streams=None, threshold=None, dem=None, cellsize=1.0, want=
         *[outs[n].ctypes.data if n in outs else None for n, _ in FT_OUTPUTS], 0,
         ctypes.byref(st)))
     return outs, st.as_dict()
+
+
+def resolve_flats(codes, dem, want_distance=False):
+    """D8 directions across flats of host arrays (``hdem_resolve_flats_u8``; see
+    :func:`resolve_flats_dev`): the codes, the distances or ``None``, the stats dict."""
+    for name, a in (("codes", codes), ("dem", dem)):
+        if a is not None and not isinstance(a, np.ndarray):
+            raise ValueError(f"{name} is a NumPy array, got {type(a)}")
+    resolve_flats_args(codes, dem)
+    codes, dem = np.ascontiguousarray(codes), np.ascontiguousarray(dem)
+    c = context()
+    out = host_empty(codes.shape, np.uint8)
+    dist = host_empty(codes.shape, np.uint32) if want_distance else None
+    st = ResolveFlatsStats()
+    c.check(c.lib.hdem_resolve_flats_u8(
+        c.handle, codes.ctypes.data, dem.ctypes.data, codes.shape[0], codes.shape[1],
+        out.ctypes.data, dist.ctypes.data if want_distance else None, 0, ctypes.byref(st)))
+    return out, dist, st.as_dict()
 
 
 def sinkfill(z, eps=0.0, max_rounds=0, return_stats=False):

@@ -24,7 +24,7 @@ construction, SURVEY section 2 #9 / 8e "not shardable"; no kernel is wanted):
 unchanged when ``filters`` resolves here.
 
 New operators (the reference has neither): ``SinkFill``,
-``D8FlowDirection``, ``FlowAccumulation``, ``Watersheds``, ``FlowDistance``,
+``D8FlowDirection``, ``ResolveFlats``, ``FlowAccumulation``, ``Watersheds``, ``FlowDistance``,
 ``HeightAboveDrainage`` and the chain ``DemToHAND``, shaped like every other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
@@ -614,15 +614,107 @@ class HeightAboveDrainage(_FlowTrace):  # pylint: disable=too-few-public-methods
         return self._keep(self._trace_device(raster, self._want()))
 
 
+class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods
+    """D8 directions across flats (new operator).  Input: a uint8 H x W raster of ESRI D8 codes
+    as ``D8FlowDirection`` returns them, and -- at construction -- the float32 ``dem`` they
+    were made on (array or ``DeviceRaster``, NaN = nodata).  ``D8FlowDirection`` only routes
+    strictly downhill, so every cell of a flat, and of a depression filled with
+    ``epsilon=0``, has code 0.  Returns uint8 codes in which those cells point along a
+    shortest path of equal elevation to where their flat drains.  "Equal" is float ``==``:
+    -0.0 equals 0.0 and NaN equals nothing.
+
+    *Drains*: non-NaN cells with a code != 0, on the raster ring or with a NaN neighbour.
+    *Flat cells*: every other non-NaN cell.  ``dist[c]`` of a flat cell is the length of the
+    shortest 8-connected path from ``c`` through flat cells of ``c``'s elevation to a drain of
+    that elevation.  A flat cell with a finite distance gets the code of the first neighbour
+    in D8 window order (NW, N, NE, W, E, SW, S, SE) that has its elevation and distance
+    ``dist[c] - 1`` (drains count as 0); every other cell keeps its code, so a flat that
+    cannot drain -- a pit of an unfilled DEM -- stays 0 and is counted in
+    ``stats["unresolved"]``.
+
+    The distance strictly decreases along the new codes: the result is acyclic whenever the
+    input is.  On a DEM filled with ``epsilon=0`` no cell is unresolved, and the only interior
+    cells left at 0 are nodata cells and their neighbours, which the fill treats as outlets.
+    The elevations are not touched, and nothing depends on an ``epsilon`` that float32 could
+    absorb.  Exact integers, identical from run to run.
+
+    ``ValueError`` for a ``dem`` that is missing, of another type, dtype or dimension (at
+    construction), codes that are not a 2-D uint8 raster of the dem's shape (before the
+    device is touched), a byte that is not a D8 code and more than 2^32 - 1 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        flat_cells, unresolved, max_distance, rounds (relaxation rounds that had work),
+        active_tiles, tile_visits, tile_h / tile_w of the last call; phase times when
+        profiling is on.
+    distance : numpy.ndarray, DeviceRaster or None
+        with ``keep_partial_results=True`` the uint32 distances of the last call (0 outside
+        the flats, 0xFFFFFFFF where unresolved): a host array after ``apply``, a device
+        raster (the caller's to free) after ``apply_device``.
+    """
+
+    auto_device = True      # device form == host form for a uint8 code raster
+
+    def __init__(self, *, dem, keep_partial_results=False):
+        if dem is None:
+            raise ValueError("ResolveFlats needs the dem the codes were made on")
+        if not (isinstance(dem, np.ndarray) or _is_device_raster(dem)):
+            raise ValueError(f"dem is a NumPy array or a DeviceRaster, got {type(dem)}")
+        if len(dem.shape) != 2:
+            raise ValueError(f"dem is a 2-D raster, got {len(dem.shape)} dimensions")
+        if np.dtype(dem.dtype) != np.float32:
+            raise ValueError(f"dem has dtype float32, got {dem.dtype}")
+        self.dem = dem
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.distance = None
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        backend.resolve_flats_args(image_to_filter, self.dem)
+        dem = self.dem.to_host() if _is_device_raster(self.dem) else self.dem
+        out, self.distance, self.stats = backend.resolve_flats(
+            image_to_filter, dem, self.keep_partial_results)
+        return out
+
+    def apply_device(self, raster):
+        backend.resolve_flats_args(raster, self.dem)
+        dem, mine = self.dem, isinstance(self.dem, np.ndarray)
+        if mine:
+            dem = backend.DeviceRaster.from_host(dem, dtype=np.float32, ctx=raster.ctx)
+        try:
+            out, self.distance, self.stats = backend.resolve_flats_dev(
+                raster, dem, self.keep_partial_results)
+        finally:
+            if mine:
+                dem.free()
+        return out
+
+
+def _check_flats(flats):
+    if flats not in ("keep", "resolve"):
+        raise ValueError(f"flats is 'keep' or 'resolve', got {flats!r}")
+    return flats
+
+
 class HydroConditioning(ComposedFilter):  # pylint: disable=too-few-public-methods
     """``SinkFill`` then ``D8FlowDirection`` as one device-resident chain (the
     pair BASELINE.json's metric is quoted on).  ``filled`` keeps the filled
-    DEM of the last ``apply``; the return value is the D8 grid."""
+    DEM of the last ``apply``; the return value is the D8 grid.
 
-    def __init__(self, *, epsilon=0.0):
+    ``flats="resolve"`` appends ``ResolveFlats`` on the filled DEM, still on the device with
+    no download in between: with ``epsilon=0`` the flats the fill makes then drain, and the
+    elevations stay those of the exact fill.  ``resolve_stats`` holds that stage's stats.
+    The default ``flats="keep"`` leaves code 0 on flats.  ``apply_batch``, the canvas form,
+    has no resolution stage: with ``flats="resolve"`` it raises ``ValueError``."""
+
+    def __init__(self, *, epsilon=0.0, flats="keep"):
         super().__init__()
         self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection()]
+        self.flats = _check_flats(flats)
         self.filled = None
+        self.resolve_stats = {}
 
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
@@ -632,6 +724,9 @@ class HydroConditioning(ComposedFilter):  # pylint: disable=too-few-public-metho
             filled, codes, fill.stats = backend.sinkfill_d8_dev(
                 z, eps=fill.epsilon, max_rounds=fill.max_rounds)
             with filled, codes:
+                if self.flats == "resolve":
+                    _, _, self.resolve_stats = backend.resolve_flats_dev(codes, filled,
+                                                                         out=codes)
                 self.filled = filled.to_host()
                 return codes.to_host()
 
@@ -645,7 +740,11 @@ class HydroConditioning(ComposedFilter):  # pylint: disable=too-few-public-metho
         only the D8 codes of each raster's ring are put back to 0 afterwards (on the canvas
         they have neighbours).  The arrays returned are views of the downloaded canvases (one
         pair of canvases per width).  Bit-equal to ``apply`` raster by raster
-        (``tests/test_gpu_parity.py::test_batch_of_rasters_fills_like_each_alone``)."""
+        (``tests/test_gpu_parity.py::test_batch_of_rasters_fills_like_each_alone``).
+        ``flats="resolve"`` is not available here: ``ValueError``."""
+        if self.flats != "keep":
+            raise ValueError("apply_batch does not resolve flats: use apply raster by raster "
+                             "with flats='resolve'")
         rasters = [np.asarray(r, dtype=np.float32) for r in rasters]
         for r in rasters:
             Filter.apply(self, r)
@@ -706,10 +805,18 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
     ``filled``, ``codes``, ``accumulation`` and ``distance`` (distance to the streams): host
     arrays after ``apply``, device rasters (the caller's to free) after ``apply_device``;
     otherwise they are ``None``.  ``epsilon > 0`` makes the D8 paths of the filled DEM descend
-    strictly, so that they cross what were flats and pits."""
+    strictly, so that they cross what were flats and pits.
 
-    def __init__(self, *, threshold, epsilon=1e-3, cellsize=1.0, keep_partial_results=False):
+    ``flats="resolve"`` runs ``ResolveFlats`` on the filled DEM between the D8 and the
+    accumulation, and the resolved codes feed every later stage (``codes`` keeps them,
+    ``stats["ResolveFlats"]`` that stage's stats).  ``epsilon=0.0, flats="resolve"`` is the
+    exact route: the paths cross the filled depressions on elevations no gradient has
+    raised.  The default ``flats="keep"`` changes nothing."""
+
+    def __init__(self, *, threshold, epsilon=1e-3, cellsize=1.0, keep_partial_results=False,
+                 flats="keep"):
         super().__init__()
+        self.flats = _check_flats(flats)
         # the checks of the trace's operands, on stand-ins of the types the chain makes
         HeightAboveDrainage(dem=np.zeros((1, 1), np.float32),
                             streams=np.zeros((1, 1), np.uint32), threshold=threshold,
@@ -747,6 +854,9 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
             raster, eps=fill.epsilon, max_rounds=fill.max_rounds)
         kept += [filled, codes]
         try:
+            resolve_stats = None
+            if self.flats == "resolve":
+                _, _, resolve_stats = backend.resolve_flats_dev(codes, filled, out=codes)
             acc, accumulate.stats = backend.flowacc_dev(codes)
             kept.append(acc)
             trace = HeightAboveDrainage(dem=filled, streams=acc, threshold=self.threshold,
@@ -755,6 +865,8 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
             hand = trace.apply_device(codes)
             self.stats = {"SinkFill": fill.stats, "FlowAccumulation": accumulate.stats,
                           "HeightAboveDrainage": trace.stats}
+            if resolve_stats is not None:
+                self.stats["ResolveFlats"] = resolve_stats
             if self.keep_partial_results:
                 trace.drainage.free()
                 self.filled, self.codes, self.accumulation = kept

@@ -532,6 +532,61 @@ int hdem_flowtrace_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const 
                           float *distance, float *hand, int flags,
                           hdem_flowtrace_stats *stats);  /* device pointers */
 
+/* ---- A8  ResolveFlats.apply  (new operator: D8 directions across flats) --
+ * d8: uint8 ESRI codes as hdem_d8_f32 writes them; dem: the float32 H x W raster they were
+ * made on, NaN = nodata.  hdem_d8_f32 only routes strictly downhill, so every cell of a flat
+ * (all of a filled depression after an epsilon = 0 sink fill) has code 0.  This call points
+ * the cells of a flat towards the nearest way out of it.  "Equal" is float ==: -0.0 equals
+ * 0.0, NaN equals nothing.
+ *   drains S   non-NaN cells with a code != 0, or on the one-cell raster ring, or with a NaN
+ *              8-neighbour
+ *   flat   F   every other non-NaN cell (interior, code 0, no nodata neighbour)
+ *   dist[c]    c in F: the length k >= 1 of the shortest 8-connected path c = p0, ..., pk with
+ *              every dem[pi] == dem[c], p0 ... p(k-1) in F and pk in S; infinite when there is
+ *              no such path (a pit of an unfilled DEM)
+ *   out[c]     c in F with finite dist: the code of the first neighbour n in D8 window order
+ *              (NW, N, NE, W, E, SW, S, SE) with dem[n] == dem[c] and dist[n] == dist[c] - 1,
+ *              cells of S counting as 0; every other cell: d8[c]
+ * dist strictly decreases along the new codes, so out is acyclic whenever d8 is.  It is the
+ * unique solution of dist[c] = 1 + min over equal neighbours (0 in S, else dist), which the
+ * call checks at every flat cell before it returns.  After an epsilon = 0 fill no cell is
+ * unresolved and the interior cells left at 0 are the nodata cells and their neighbours.
+ * Rasters of H < 3 or W < 3 have no flat cell: out = d8.
+ * dist (may be NULL): uint32 H x W, 0 outside F, k at resolved cells, 0xFFFFFFFF at unresolved
+ * ones.  out may be d8 itself (in place); no other overlap between the rasters is allowed.
+ * flags must be 0.  Exact integers, identical from run to run and independent of the schedule.
+ * HDEM_ERR_BAD_ARG for a byte that is not 0 or a power of two (the text of the other D8
+ * operators), for unknown flags and -- before any allocation or launch -- for
+ * H * W > 2^32 - 1; HDEM_ERR_NOT_CONVERGED if the check of the local equation fails.  On error
+ * the contents of out and dist are unspecified.
+ * Workspace from the context's arena: 4 B per cell (the distances) when dist is NULL, else
+ * nothing per cell -- dist is worked in; 12 B per 64 x 64 tile either way.  The _dev form
+ * synchronises the context's stream once per relaxation round (it reads how many tiles the
+ * next round has).  stats may be NULL; otherwise the caller sets
+ * stats->struct_size = sizeof(hdem_resolve_flats_stats) first (64 bytes in this version; a
+ * shorter struct is filled as far as it goes).  The three phase times are filled only while
+ * profiling is on (hdem_profile_enable); the call has no kernel id. */
+typedef struct hdem_resolve_flats_stats {
+    uint32_t struct_size;   /* in: sizeof(hdem_resolve_flats_stats), set by the caller      */
+    int32_t rounds;         /* relaxation rounds that had work (launches of tile visits)    */
+    int64_t flat_cells;     /* cells of F                                                   */
+    int64_t unresolved;     /* cells of F with no path to a drain                           */
+    int64_t tile_visits;    /* tiles relaxed, summed over the rounds                        */
+    uint32_t max_distance;  /* the largest finite dist                                      */
+    int32_t active_tiles;   /* tiles that hold a cell of F: the visits of the first round   */
+    int32_t tile_h, tile_w;
+    float ms_classify;      /* F and S told apart (HIP events; profiling only)              */
+    float ms_relax;         /* the rounds, host reads included                              */
+    float ms_final;         /* codes written, result checked                                */
+    int32_t reserved;       /* 0                                                            */
+} hdem_resolve_flats_stats; /* sizeof == 64 */
+int hdem_resolve_flats_u8(hdem_ctx *ctx, const uint8_t *d8, const float *dem, int H, int W,
+                          uint8_t *out, uint32_t *dist, int flags,
+                          hdem_resolve_flats_stats *stats);      /* host pointers, synchronous */
+int hdem_resolve_flats_u8_dev(hdem_ctx *ctx, const uint8_t *d8, const float *dem, int H, int W,
+                              uint8_t *out, uint32_t *dist, int flags,
+                              hdem_resolve_flats_stats *stats);  /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
