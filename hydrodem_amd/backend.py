@@ -7,6 +7,7 @@ There is deliberately no CPU implementation behind it -- when the library or
 a GPU is missing every operator raises :class:`BackendError`.
 """
 
+import contextlib
 import ctypes
 import importlib.util
 import os
@@ -48,7 +49,23 @@ class KernelStat(ctypes.Structure):
                 ("units", ctypes.c_int64)]
 
 
-class FillStats(ctypes.Structure):
+class _Stats(ctypes.Structure):
+    """What the stats structs of the C ABI share: their fields as a dict."""
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_
+                if k not in ("struct_size", "reserved")}
+
+
+class _SizedStats(_Stats):
+    """A stats struct that opens with ``struct_size``, set on construction as the C ABI asks."""
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = ctypes.sizeof(self)
+
+
+class FillStats(_Stats):
     _fields_ = [("rounds", ctypes.c_int32), ("converged", ctypes.c_int32),
                 ("tile_visits", ctypes.c_int64), ("tiles", ctypes.c_int64),
                 ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
@@ -59,42 +76,28 @@ class FillStats(ctypes.Structure):
                 ("flat_unchanged", ctypes.c_int32),
                 ("deferred_visits", ctypes.c_int64), ("deferred_unchanged", ctypes.c_int64)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class FlowAccStats(ctypes.Structure):
+class FlowAccStats(_Stats):
     _fields_ = [("exits", ctypes.c_int64), ("max_hops", ctypes.c_int32),
                 ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
                 ("ms_tile", ctypes.c_float), ("ms_forest", ctypes.c_float),
                 ("ms_final", ctypes.c_float)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class WatershedStats(ctypes.Structure):
-    """``hdem_watershed_stats``; ``struct_size`` is set on construction, as the C ABI asks."""
+class WatershedStats(_SizedStats):
+    """``hdem_watershed_stats``."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("forest_rounds", ctypes.c_int32),
                 ("basins", ctypes.c_int64), ("exits", ctypes.c_int64),
                 ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
                 ("ms_tile", ctypes.c_float), ("ms_forest", ctypes.c_float),
                 ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
-    def __init__(self):
-        super().__init__()
-        self.struct_size = ctypes.sizeof(self)
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_
-                if k not in ("struct_size", "reserved")}
-
 
 WS_COMPACT = 1      # HDEM_WS_COMPACT
 
 
-class FlowTraceStats(ctypes.Structure):
-    """``hdem_flowtrace_stats``; ``struct_size`` is set on construction, as the C ABI asks."""
+class FlowTraceStats(_SizedStats):
+    """``hdem_flowtrace_stats``."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("forest_rounds", ctypes.c_int32),
                 ("stops", ctypes.c_int64), ("unreached", ctypes.c_int64),
                 ("exits", ctypes.c_int64),
@@ -102,17 +105,9 @@ class FlowTraceStats(ctypes.Structure):
                 ("ms_tile", ctypes.c_float), ("ms_forest", ctypes.c_float),
                 ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
-    def __init__(self):
-        super().__init__()
-        self.struct_size = ctypes.sizeof(self)
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_
-                if k not in ("struct_size", "reserved")}
-
-
-class ResolveFlatsStats(ctypes.Structure):
-    """``hdem_resolve_flats_stats``; ``struct_size`` is set on construction, as the C ABI asks."""
+class ResolveFlatsStats(_SizedStats):
+    """``hdem_resolve_flats_stats``."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("rounds", ctypes.c_int32),
                 ("flat_cells", ctypes.c_int64), ("unresolved", ctypes.c_int64),
                 ("tile_visits", ctypes.c_int64), ("max_distance", ctypes.c_uint32),
@@ -120,14 +115,6 @@ class ResolveFlatsStats(ctypes.Structure):
                 ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
                 ("ms_classify", ctypes.c_float), ("ms_relax", ctypes.c_float),
                 ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
-
-    def __init__(self):
-        super().__init__()
-        self.struct_size = ctypes.sizeof(self)
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_
-                if k not in ("struct_size", "reserved")}
 
 
 # HDEM_FT_STREAMS_*
@@ -552,6 +539,23 @@ class DeviceRaster:
             self.free()
         except Exception:  # pylint: disable=broad-except
             pass
+
+
+def is_device_raster(x):
+    """A :class:`DeviceRaster`, or anything that quacks like one."""
+    return hasattr(x, "ptr") and hasattr(x, "to_host")
+
+
+@contextlib.contextmanager
+def on_device(operand, dtype=None, ctx=None):
+    """``operand`` as a device raster for the length of a call.  A device raster (and ``None``,
+    an operand left out) is handed through and stays its owner's; a host array is uploaded
+    as ``dtype`` on ``ctx`` and freed on the way out."""
+    if operand is None or is_device_raster(operand):
+        yield operand
+        return
+    with DeviceRaster.from_host(operand, dtype=dtype, ctx=ctx) as raster:
+        yield raster
 
 
 # ---------------------------------------------------------------------------

@@ -83,8 +83,7 @@ extern "C" int hdem_copy_rate_dev(hdem_ctx *ctx, const void *src, void *dst, siz
 extern "C" int hdem_blockmax_f32_dev(hdem_ctx *ctx, const float *z, int H, int W, int b,
                                      float *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(z, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, z, out, H, W)) return rc;
     HDEM_REQUIRE(b >= 4 && b <= 256 && (b & (b - 1)) == 0, HDEM_ERR_BAD_ARG,
                  "block size must be a power of two in 4..256, got %d", b);
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));

@@ -188,6 +188,16 @@ inline void d8_publish(Stats *stats, Stats st)
     memcpy(stats, &st, st.struct_size);
 }
 
+// A stats struct that is passed holds at least its struct_size; `name` is the struct's.
+template <class Stats>
+inline int d8_check_stats(const Stats *stats, const char *name)
+{
+    HDEM_REQUIRE(!stats || stats->struct_size >= sizeof(uint32_t), HDEM_ERR_BAD_ARG,
+                 "%s.struct_size is %u: set it to sizeof(%s)", name,
+                 stats ? stats->struct_size : 0u, name);
+    return HDEM_OK;
+}
+
 // The pointer-jumping forest: ceil(log2 nslots) + 1 launches (a round at least halves every
 // chain) of `grid` workgroups of nt threads, grid-stride.
 struct d8_forest_plan {

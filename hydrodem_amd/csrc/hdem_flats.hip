@@ -273,16 +273,11 @@ __global__ __launch_bounds__(NT) void flats_final_kernel(
 int check_args(hdem_ctx *ctx, const uint8_t *d8, const float *dem, int H, int W,
                const uint8_t *out, int flags, const hdem_resolve_flats_stats *stats, d8_grid *g)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(d8, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, d8, out, H, W)) return rc;
     HDEM_REQUIRE(dem, HDEM_ERR_BAD_ARG, "flat resolution needs the dem the codes were made on");
     if (int rc = d8_grid_of("flat resolution", H, W, g)) return rc;
     HDEM_REQUIRE(!flags, HDEM_ERR_BAD_ARG, "unknown flat resolution flags 0x%x", flags);
-    HDEM_REQUIRE(!stats || stats->struct_size >= sizeof(uint32_t), HDEM_ERR_BAD_ARG,
-                 "hdem_resolve_flats_stats.struct_size is %u: set it to "
-                 "sizeof(hdem_resolve_flats_stats)",
-                 stats ? stats->struct_size : 0u);
-    return HDEM_OK;
+    return d8_check_stats(stats, "hdem_resolve_flats_stats");
 }
 
 }  // namespace
@@ -378,19 +373,15 @@ extern "C" int hdem_resolve_flats_u8(hdem_ctx *ctx, const uint8_t *d8, const flo
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t n = (size_t)H * W;
     hdem_dbuf dd8, ddem, ddist;
-    if (int rc = dd8.alloc(ctx, n)) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, dd8.p, d8, n)) return rc;
-    if (int rc = ddem.alloc(ctx, n * sizeof(float))) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, ddem.p, dem, n * sizeof(float))) return rc;
+    if (int rc = dd8.upload(ctx, d8, n)) return rc;
+    if (int rc = ddem.upload(ctx, dem, n * sizeof(float))) return rc;
     if (dist)
         if (int rc = ddist.alloc(ctx, n * sizeof(uint32_t))) return rc;
     // the codes are resolved in place on the device
-    const int rc = hdem_resolve_flats_u8_dev(ctx, (const uint8_t *)dd8.p, (const float *)ddem.p, H,
-                                             W, (uint8_t *)dd8.p, (uint32_t *)ddist.p, flags,
-                                             stats);
-    if (rc) return rc;
-    if (int rc2 = hdem_memcpy_d2h(ctx, out, dd8.p, n)) return rc2;
-    if (dist)
-        if (int rc2 = hdem_memcpy_d2h(ctx, dist, ddist.p, n * sizeof(uint32_t))) return rc2;
-    return HDEM_OK;
+    if (int rc = hdem_resolve_flats_u8_dev(ctx, dd8.as<const uint8_t>(), ddem.as<const float>(), H,
+                                           W, dd8.as<uint8_t>(), ddist.as<uint32_t>(), flags,
+                                           stats))
+        return rc;
+    if (int rc = dd8.download(out, n)) return rc;
+    return dist ? ddist.download(dist, n * sizeof(uint32_t)) : HDEM_OK;
 }

@@ -252,8 +252,7 @@ __global__ __launch_bounds__(NT) void flowacc_forest_walk_kernel(
 extern "C" int hdem_flowacc_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, uint32_t *out,
                                    hdem_flowacc_stats *stats)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(d8, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, d8, out, H, W)) return rc;
     d8_grid g;
     if (int rc = d8_grid_of("flow accumulation", H, W, &g)) return rc;
     const int64_t cells = (int64_t)H * W, tiles = g.tiles, nslots = g.nslots;
@@ -316,17 +315,16 @@ extern "C" int hdem_flowacc_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int 
 extern "C" int hdem_flowacc_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, uint32_t *out,
                                hdem_flowacc_stats *stats)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(d8, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, d8, out, H, W)) return rc;
     d8_grid g;
     if (int rc = d8_grid_of("flow accumulation", H, W, &g)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)H * W;
+    const size_t n = (size_t)H * W, bytes = n * sizeof(uint32_t);
     hdem_dbuf dd8, dout;
-    if (int rc = dd8.alloc(ctx, n)) return rc;
-    if (int rc = dout.alloc(ctx, n * sizeof(uint32_t))) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, dd8.p, d8, n)) return rc;
-    if (int rc = hdem_flowacc_u8_dev(ctx, (const uint8_t *)dd8.p, H, W, (uint32_t *)dout.p, stats))
+    if (int rc = dd8.upload(ctx, d8, n)) return rc;
+    if (int rc = dout.alloc(ctx, bytes)) return rc;
+    if (int rc = hdem_flowacc_u8_dev(ctx, dd8.as<const uint8_t>(), H, W, dout.as<uint32_t>(),
+                                     stats))
         return rc;
-    return hdem_memcpy_d2h(ctx, out, dout.p, n * sizeof(uint32_t));
+    return dout.download(out, bytes);
 }

@@ -293,8 +293,7 @@ int check_args(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *strea
                const float *distance, const float *hand, int flags,
                const hdem_flowtrace_stats *stats, d8_grid *g)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(d8, d8, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, d8, d8, H, W)) return rc;
     if (int rc = d8_grid_of("flow trace", H, W, g)) return rc;
     HDEM_REQUIRE(!flags, HDEM_ERR_BAD_ARG, "unknown flow trace flags 0x%x", flags);
     HDEM_REQUIRE(stop || ncard || ndiag || distance || hand, HDEM_ERR_BAD_ARG,
@@ -320,10 +319,7 @@ int check_args(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *strea
     }
     HDEM_REQUIRE(std::isfinite(cellsize) && cellsize > 0.0, HDEM_ERR_BAD_ARG,
                  "cellsize must be finite and positive, got %g", cellsize);
-    HDEM_REQUIRE(!stats || stats->struct_size >= sizeof(uint32_t), HDEM_ERR_BAD_ARG,
-                 "hdem_flowtrace_stats.struct_size is %u: set it to sizeof(hdem_flowtrace_stats)",
-                 stats ? stats->struct_size : 0u);
-    return HDEM_OK;
+    return d8_check_stats(stats, "hdem_flowtrace_stats");
 }
 
 }  // namespace
@@ -416,28 +412,21 @@ extern "C" int hdem_flowtrace_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W,
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t n = (size_t)H * W;
     hdem_dbuf dd8, dstreams, ddem, dout[5];
-    if (int rc = dd8.alloc(ctx, n)) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, dd8.p, d8, n)) return rc;
-    if (streams) {
-        const size_t sb = n * (stream_kind == HDEM_FT_STREAMS_ACC_U32 ? sizeof(uint32_t) : 1);
-        if (int rc = dstreams.alloc(ctx, sb)) return rc;
-        if (int rc = hdem_memcpy_h2d(ctx, dstreams.p, streams, sb)) return rc;
-    }
-    if (dem) {
-        if (int rc = ddem.alloc(ctx, n * sizeof(float))) return rc;
-        if (int rc = hdem_memcpy_h2d(ctx, ddem.p, dem, n * sizeof(float))) return rc;
-    }
+    const size_t sb = n * (stream_kind == HDEM_FT_STREAMS_ACC_U32 ? sizeof(uint32_t) : 1);
+    if (int rc = dd8.upload(ctx, d8, n)) return rc;
+    if (int rc = dstreams.upload(ctx, streams, sb)) return rc;
+    if (int rc = ddem.upload(ctx, dem, n * sizeof(float))) return rc;
     void *const host_out[5] = {stop, ncard, ndiag, distance, hand};
     for (int k = 0; k < 5; ++k)
         if (host_out[k])
             if (int rc = dout[k].alloc(ctx, n * 4)) return rc;
     const int rc = hdem_flowtrace_u8_dev(
-        ctx, (const uint8_t *)dd8.p, H, W, dstreams.p, stream_kind, threshold,
-        (const float *)ddem.p, cellsize, (uint32_t *)dout[0].p, (uint32_t *)dout[1].p,
-        (uint32_t *)dout[2].p, (float *)dout[3].p, (float *)dout[4].p, flags, stats);
+        ctx, dd8.as<const uint8_t>(), H, W, dstreams.p, stream_kind, threshold,
+        ddem.as<const float>(), cellsize, dout[0].as<uint32_t>(), dout[1].as<uint32_t>(),
+        dout[2].as<uint32_t>(), dout[3].as<float>(), dout[4].as<float>(), flags, stats);
     if (rc) return rc;
     for (int k = 0; k < 5; ++k)
         if (host_out[k])
-            if (int rc2 = hdem_memcpy_d2h(ctx, host_out[k], dout[k].p, n * 4)) return rc2;
+            if (int rc2 = dout[k].download(host_out[k], n * 4)) return rc2;
     return HDEM_OK;
 }

@@ -795,22 +795,6 @@ __global__ __launch_bounds__(NT) void transpose_abs_kernel(const float2 *__restr
     }
 }
 
-inline dim3 grid2(int w, int h) { return dim3((unsigned)((w + NT - 1) / NT), (unsigned)h); }
-
-int check_window(int window, int h, int w)
-{
-    // SlidingWindow.window_size setter (sliding_window.py:150-156): same order of checks
-    if (window > h || window > w) {
-        hdem_set_error("Window size: %d cannot be higher than grid dimensions: (%d, %d)", window, h, w);
-        return HDEM_ERR_WINDOW_HIGH;
-    }
-    if (window % 2 != 1) {
-        hdem_set_error("Window size: %d cannot be an even number", window);
-        return HDEM_ERR_WINDOW_EVEN;
-    }
-    return HDEM_OK;
-}
-
 // One BlanksFourier pass on a device quadrant: q_out <- q with the peaks zeroed (NULL: not
 // needed), found / total as in detect_kernel.
 // occ_mark / occ_skip: ((h + 31) / 32) x ((w + 31) / 32) bytes, see the kernel; either may be NULL.
@@ -849,9 +833,8 @@ int blanks_pass(hdem_ctx *ctx, const float *q, int h, int w, float *q_out, uint8
 extern "C" int hdem_blanks_fourier_f32_dev(hdem_ctx *ctx, float *q, int h, int w, int window,
                                            uint8_t *found)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(q, found, h, w)) return rc;
-    if (int rc = check_window(window, h, w)) return rc;
+    if (int rc = hdem_check_call(ctx, q, found, h, w)) return rc;
+    if (int rc = hdem_check_window(window, h, w)) return rc;
     // (the inner window left out is 5 x 5; a block of 256 columns keeps `window - 1` of them
     // as context)
     HDEM_REQUIRE(window >= 7 && window <= 201, HDEM_ERR_BAD_ARG,
@@ -868,10 +851,9 @@ extern "C" int hdem_blanks_fourier_f32_dev(hdem_ctx *ctx, float *q, int h, int w
 extern "C" int hdem_isolated_points_u8_dev(hdem_ctx *ctx, const uint8_t *mask, int h, int w,
                                            int window, uint8_t *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(mask, out, h, w)) return rc;
+    if (int rc = hdem_check_call(ctx, mask, out, h, w)) return rc;
     HDEM_REQUIRE(mask != out, HDEM_ERR_BAD_ARG, "isolated points cannot run in place");
-    if (int rc = check_window(window, h, w)) return rc;
+    if (int rc = hdem_check_window(window, h, w)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     {
         hdem_scoped_timer tm(ctx, HDEM_K_FOURIER_MASK, (int64_t)h * w);
@@ -887,10 +869,9 @@ extern "C" int hdem_isolated_points_u8_dev(hdem_ctx *ctx, const uint8_t *mask, i
 extern "C" int hdem_expand_u8_dev(hdem_ctx *ctx, const uint8_t *mask, int h, int w, int window,
                                   uint8_t *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(mask, out, h, w)) return rc;
+    if (int rc = hdem_check_call(ctx, mask, out, h, w)) return rc;
     HDEM_REQUIRE(mask != out, HDEM_ERR_BAD_ARG, "expand cannot run in place");
-    if (int rc = check_window(window, h, w)) return rc;
+    if (int rc = hdem_check_window(window, h, w)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     HDEM_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)h * w, ctx->stream));
     {
@@ -912,8 +893,7 @@ extern "C" int hdem_expand_u8_dev(hdem_ctx *ctx, const uint8_t *mask, int h, int
 
 extern "C" int hdem_fft2_c2c_f32_dev(hdem_ctx *ctx, float *data, int H, int W, int inverse)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(data, data, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, data, data, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     if (int rc = ensure_plans(ctx, H, W)) return rc;
     return run_fft(ctx, inverse != 0, (float2 *)data);
@@ -925,8 +905,7 @@ extern "C" int hdem_fft2_c2c_f32_dev(hdem_ctx *ctx, float *data, int H, int W, i
 // buffer are made for the call and released behind it.
 extern "C" int hdem_fft2_c2c_f64_dev(hdem_ctx *ctx, double *data, int H, int W, int inverse)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(data, data, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, data, data, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     if (int rc = load_rocfft()) return rc;
     const size_t lengths[2] = {(size_t)W, (size_t)H};
@@ -960,8 +939,7 @@ extern "C" int hdem_fft2_c2c_f64_dev(hdem_ctx *ctx, double *data, int H, int W, 
 extern "C" int hdem_fourier_destripe_f32_dev(hdem_ctx *ctx, const float *dem, int H, int W,
                                              float *out, uint8_t *mask)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(dem, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, dem, out, H, W)) return rc;
     const quad_geom g = make_geom(H, W);
     // what the reference's window constructors would raise on the quadrants
     if (g.qh < 1 || g.qw < 1) {
@@ -969,15 +947,15 @@ extern "C" int hdem_fourier_destripe_f32_dev(hdem_ctx *ctx, const float *dem, in
                        g.qh > 0 ? g.qh : 0, g.qw > 0 ? g.qw : 0);
         return HDEM_ERR_WINDOW_HIGH;
     }
-    if (int rc = check_window(55, g.qh, g.qw)) return rc;
+    if (int rc = hdem_check_window(55, g.qh, g.qw)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     if (int rc = ensure_plans(ctx, H, W)) return rc;
     hipStream_t st = ctx->stream;
     const size_t n = (size_t)H * W, qn = (size_t)g.qh * g.qw;
     // one allocation, carved up: spectrum | quadrant and its copy without the first pass's
     // peaks | 4 byte masks | partial sums + mean
-    const size_t qn8 = (qn + 15) / 16 * 16;     // (keeps every view 16-byte aligned)
-    const size_t occ_bytes = ((size_t)((g.qh + 31) / 32) * ((g.qw + 31) / 32) + 15) / 16 * 16;
+    const size_t qn8 = hdem_round16(qn);        // (keeps every view 16-byte aligned)
+    const size_t occ_bytes = hdem_round16((size_t)((g.qh + 31) / 32) * ((g.qw + 31) / 32));
     const size_t bytes = n * sizeof(float2) + 2 * qn8 * sizeof(float) + 4 * qn8 + occ_bytes +
                          (SUM_BLOCKS + 1) * sizeof(double);
     hdem_fourier_state *fs = ctx->fourier;
@@ -1004,8 +982,8 @@ extern "C" int hdem_fourier_destripe_f32_dev(hdem_ctx *ctx, const float *dem, in
     if (int rc = run_r2c(ctx, out, (float2 *)F.p)) return rc;
     if (W > 2) {
         hdem_scoped_timer tm(ctx, HDEM_K_FOURIER_POINT, (int64_t)n);
-        hipLaunchKernelGGL(fill_right_half_kernel, grid2(W - W / 2 - 1, H), dim3(NT), 0, st,
-                           (float2 *)F.p, H, W);
+        hipLaunchKernelGGL(fill_right_half_kernel, hdem_grid2(W - W / 2 - 1, H, NT), dim3(NT), 0,
+                           st, (float2 *)F.p, H, W);
     }
     if (mask) HDEM_HIP_CHECK(hipMemsetAsync(mask, 0, n, st));
     // both quadrants are detected on the untouched spectrum, then both are applied
@@ -1013,7 +991,7 @@ extern "C" int hdem_fourier_destripe_f32_dev(hdem_ctx *ctx, const float *dem, in
         uint8_t *e = (uint8_t *)(second ? exp2.p : exp.p);
         {
             hdem_scoped_timer tm(ctx, HDEM_K_FOURIER_POINT, (int64_t)qn);
-            hipLaunchKernelGGL(quadrant_abs_kernel, grid2(g.qw, g.qh), dim3(NT), 0, st,
+            hipLaunchKernelGGL(quadrant_abs_kernel, hdem_grid2(g.qw, g.qh, NT), dim3(NT), 0, st,
                                (const float2 *)F.p, g, second, (float *)q.p);
         }
         HDEM_HIP_CHECK(hipMemsetAsync(det.p, 0, qn, st));
@@ -1084,20 +1062,18 @@ extern "C" int hdem_fourier_destripe_f32_dev(hdem_ctx *ctx, const float *dem, in
 extern "C" int hdem_fourier_destripe_f32(hdem_ctx *ctx, const float *dem, int H, int W, float *out,
                                          uint8_t *mask)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(dem, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, dem, out, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t n = (size_t)H * W;
     hdem_dbuf d_in, d_out, d_mask;
-    if (int rc = d_in.alloc(ctx, n * sizeof(float))) return rc;
+    if (int rc = d_in.upload(ctx, dem, n * sizeof(float))) return rc;
     if (int rc = d_out.alloc(ctx, n * sizeof(float))) return rc;
     if (mask)
         if (int rc = d_mask.alloc(ctx, n)) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, d_in.p, dem, n * sizeof(float))) return rc;
-    if (int rc = hdem_fourier_destripe_f32_dev(ctx, (const float *)d_in.p, H, W, (float *)d_out.p,
-                                               mask ? (uint8_t *)d_mask.p : nullptr))
+    if (int rc = hdem_fourier_destripe_f32_dev(ctx, d_in.as<const float>(), H, W, d_out.as<float>(),
+                                               d_mask.as<uint8_t>()))
         return rc;
     if (mask)
-        if (int rc = hdem_memcpy_d2h(ctx, mask, d_mask.p, n)) return rc;
-    return hdem_memcpy_d2h(ctx, out, d_out.p, n * sizeof(float));
+        if (int rc = d_mask.download(mask, n)) return rc;
+    return d_out.download(out, n * sizeof(float));
 }

@@ -488,17 +488,13 @@ int launch_pass(hdem_ctx *ctx, const float *img, const uint8_t *groves, int H, i
     return HDEM_OK;
 }
 
-// window validation, same two failure classes and the same order of checks as
-// the SlidingWindow constructor (sliding_window.py:150-156)
+// the shared window rule between what only these kernels ask of a window
 int check_window(int ws, int H, int W)
 {
     HDEM_REQUIRE(ws > 0, HDEM_ERR_BAD_ARG, "window size must be positive, got %d", ws);
     HDEM_REQUIRE(ws != 1, HDEM_ERR_BAD_ARG,
                  "window size 1 is degenerate (the reference's closed form is 0/0)");
-    HDEM_REQUIRE(ws <= H && ws <= W, HDEM_ERR_WINDOW_HIGH,
-                 "Window size: %d cannot be higher than grid dimensions: (%d, %d)", ws, H, W);
-    HDEM_REQUIRE(ws % 2 == 1, HDEM_ERR_WINDOW_EVEN,
-                 "Window size: %d cannot be an even number", ws);
+    if (int rc = hdem_check_window(ws, H, W)) return rc;
     HDEM_REQUIRE(ws <= WS_MAX, HDEM_ERR_BAD_ARG,
                  "window size %d not supported by the HIP kernel (max %d)", ws, WS_MAX);
     return HDEM_OK;
@@ -510,8 +506,7 @@ extern "C" int hdem_groves_f32_dev(hdem_ctx *ctx, const float *img, const uint8_
                                    int H, int W, int ws, float thr, int iters,
                                    float *scratch, float *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(img, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, img, out, H, W)) return rc;
     HDEM_REQUIRE(groves, HDEM_ERR_BAD_ARG, "groves mask is null");
     HDEM_REQUIRE(iters >= 1, HDEM_ERR_BAD_ARG, "iterations must be >= 1, got %d", iters);
     HDEM_REQUIRE(img != out, HDEM_ERR_BAD_ARG, "groves cannot run in place");
@@ -535,8 +530,7 @@ extern "C" int hdem_groves_f32_dev(hdem_ctx *ctx, const float *img, const uint8_
 extern "C" int hdem_quadratic_f32_dev(hdem_ctx *ctx, const float *dem, int H, int W, int ws,
                                       float *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(dem, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, dem, out, H, W)) return rc;
     HDEM_REQUIRE(dem != out, HDEM_ERR_BAD_ARG, "quadratic filter cannot run in place");
     if (int rc = check_window(ws, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
@@ -550,39 +544,34 @@ extern "C" int hdem_quadratic_f32_dev(hdem_ctx *ctx, const float *dem, int H, in
 extern "C" int hdem_quadratic_f32(hdem_ctx *ctx, const float *dem, int H, int W, int ws,
                                   float *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(dem, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, dem, out, H, W)) return rc;
     if (int rc = check_window(ws, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     size_t bytes = (size_t)H * W * sizeof(float);
     hdem_dbuf din, dout;
-    if (int rc = din.alloc(ctx, bytes)) return rc;
+    if (int rc = din.upload(ctx, dem, bytes)) return rc;
     if (int rc = dout.alloc(ctx, bytes)) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, din.p, dem, bytes)) return rc;
-    if (int rc = hdem_quadratic_f32_dev(ctx, (const float *)din.p, H, W, ws, (float *)dout.p))
+    if (int rc = hdem_quadratic_f32_dev(ctx, din.as<const float>(), H, W, ws, dout.as<float>()))
         return rc;
-    return hdem_memcpy_d2h(ctx, out, dout.p, bytes);
+    return dout.download(out, bytes);
 }
 
 extern "C" int hdem_groves_f32(hdem_ctx *ctx, const float *img, const uint8_t *groves, int H,
                                int W, int ws, float thr, int iters, float *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(img, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, img, out, H, W)) return rc;
     HDEM_REQUIRE(groves, HDEM_ERR_BAD_ARG, "groves mask is null");
     HDEM_REQUIRE(iters >= 1, HDEM_ERR_BAD_ARG, "iterations must be >= 1, got %d", iters);
     if (int rc = check_window(ws, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     size_t n = (size_t)H * W, bytes = n * sizeof(float);
     hdem_dbuf din, dout, dscr, dg;
-    if (int rc = din.alloc(ctx, bytes)) return rc;
+    if (int rc = din.upload(ctx, img, bytes)) return rc;
+    if (int rc = dg.upload(ctx, groves, n)) return rc;
     if (int rc = dout.alloc(ctx, bytes)) return rc;
     if (iters > 1) if (int rc = dscr.alloc(ctx, bytes)) return rc;
-    if (int rc = dg.alloc(ctx, n)) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, din.p, img, bytes)) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, dg.p, groves, n)) return rc;
-    if (int rc = hdem_groves_f32_dev(ctx, (const float *)din.p, (const uint8_t *)dg.p, H, W,
-                                     ws, thr, iters, (float *)dscr.p, (float *)dout.p))
+    if (int rc = hdem_groves_f32_dev(ctx, din.as<const float>(), dg.as<const uint8_t>(), H, W, ws,
+                                     thr, iters, dscr.as<float>(), dout.as<float>()))
         return rc;
-    return hdem_memcpy_d2h(ctx, out, dout.p, bytes);
+    return dout.download(out, bytes);
 }

@@ -144,8 +144,37 @@ static inline int hdem_check_raster(const void *in, const void *out, int H,
     return HDEM_OK;
 }
 
+// How an entry point that takes a context and an input / output raster pair opens.
+static inline int hdem_check_call(const hdem_ctx *ctx, const void *in, const void *out, int H,
+                                  int W)
+{
+    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
+    return hdem_check_raster(in, out, H, W);
+}
+
+// The SlidingWindow constructor's rule (sliding_window.py:150-156): too high is tested
+// before even, with its two messages.
+static inline int hdem_check_window(int window, int H, int W)
+{
+    HDEM_REQUIRE(window <= H && window <= W, HDEM_ERR_WINDOW_HIGH,
+                 "Window size: %d cannot be higher than grid dimensions: (%d, %d)", window, H, W);
+    HDEM_REQUIRE(window % 2 == 1, HDEM_ERR_WINDOW_EVEN,
+                 "Window size: %d cannot be an even number", window);
+    return HDEM_OK;
+}
+
+// Arena views stay 16-byte aligned.
+static inline size_t hdem_round16(size_t n) { return (n + 15) / 16 * 16; }
+
+// One thread per cell of a row, nt threads per block, one block row per raster row.
+static inline dim3 hdem_grid2(int w, int h, int nt)
+{
+    return dim3((unsigned)((w + nt - 1) / nt), (unsigned)h);
+}
+
 // Host-pointer wrapper helper: a device buffer from the context's block cache that hands
-// itself back (hdem_malloc / hdem_free).
+// itself back (hdem_malloc / hdem_free).  upload: a buffer holding a copy of `host`; a null
+// `host` (an operand the caller left out) leaves the buffer null.
 struct hdem_dbuf {
     hdem_ctx *ctx = nullptr;
     void *p = nullptr;
@@ -155,6 +184,14 @@ struct hdem_dbuf {
         ctx = c;
         return hdem_malloc(c, bytes, &p);
     }
+    int upload(hdem_ctx *c, const void *host, size_t bytes)
+    {
+        if (!host) return HDEM_OK;
+        if (int rc = alloc(c, bytes)) return rc;
+        return hdem_memcpy_h2d(c, p, host, bytes);
+    }
+    int download(void *host, size_t bytes) const { return hdem_memcpy_d2h(ctx, host, p, bytes); }
+    template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
 // ---------------------------------------------------------------------------

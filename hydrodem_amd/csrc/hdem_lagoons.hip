@@ -16,8 +16,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int MAX_STRUCT = 7;
 
-inline dim3 grid2(int w, int h) { return dim3((unsigned)((w + NT - 1) / NT), (unsigned)h); }
-
 // CorrectNANValues.apply (:287-317), window 3: an interior cell < 0 becomes the mean of
 // its 8 neighbours that are >= 0 (NaN fails the test), summed in float32 the way
 // NumPy's add.reduce does for n <= 8 -- sequentially from 0 below 8 values, as the
@@ -347,21 +345,6 @@ __global__ __launch_bounds__(NT) void erode_cross4_kernel(const uint8_t *__restr
         mid & up & dn & ((mid << 8) | left) & ((mid >> 8) | (right << 24));
 }
 
-// 4 cells per lane for the byte <-> float point kernels (16-byte load, 4-byte store)
-__global__ __launch_bounds__(NT) void nonzero_kernel(const float *__restrict__ in, size_t n,
-                                                     uint8_t *__restrict__ out)
-{
-    const size_t i = ((size_t)blockIdx.x * NT + threadIdx.x) * 4;
-    if (i + 4 <= n) {
-        const hdem_f4 v = hdem_ld4u(in + i);
-        // NaN != 0 is true, as bool(nan) is
-        *(unsigned *)(out + i) = (unsigned)(v[0] != 0.0f) | ((unsigned)(v[1] != 0.0f) << 8) |
-                                 ((unsigned)(v[2] != 0.0f) << 16) | ((unsigned)(v[3] != 0.0f) << 24);
-    } else {
-        for (size_t k = i; k < n; ++k) out[k] = in[k] != 0.0f;
-    }
-}
-
 // img * mask (ProductFilter with the byte mask of ExpandFilter)
 __device__ __forceinline__ int reflect(int i, int n)
 {   // scipy mode='reflect': d c b a | a b c d | d c b a
@@ -434,19 +417,6 @@ __global__ __launch_bounds__(NT) void grey_dilation_kernel(const T *__restrict__
             m = v > m ? v : m;
         }
         out[(size_t)y * w + x] = m;
-    }
-}
-
-__global__ __launch_bounds__(NT) void positive_kernel(const float *__restrict__ in, size_t n,
-                                                      uint8_t *__restrict__ out)
-{
-    const size_t i = ((size_t)blockIdx.x * NT + threadIdx.x) * 4;
-    if (i + 4 <= n) {
-        const hdem_f4 v = hdem_ld4u(in + i);
-        *(unsigned *)(out + i) = (unsigned)(v[0] > 0.0f) | ((unsigned)(v[1] > 0.0f) << 8) |
-                                 ((unsigned)(v[2] > 0.0f) << 16) | ((unsigned)(v[3] > 0.0f) << 24);
-    } else {
-        for (size_t k = i; k < n; ++k) out[k] = in[k] > 0.0f;
     }
 }
 
@@ -587,20 +557,6 @@ __global__ __launch_bounds__(NT) void tidy_fused_kernel(const float *__restrict_
     }
 }
 
-int window_ok(int window, int h, int w)
-{
-    if (window > h || window > w) {
-        hdem_set_error("Window size: %d cannot be higher than grid dimensions: (%d, %d)", window,
-                       h, w);
-        return HDEM_ERR_WINDOW_HIGH;
-    }
-    if (window % 2 != 1) {
-        hdem_set_error("Window size: %d cannot be an even number", window);
-        return HDEM_ERR_WINDOW_EVEN;
-    }
-    return HDEM_OK;
-}
-
 int make_struct(const uint8_t *structure, int sh, int sw, morph_struct *st)
 {
     HDEM_REQUIRE(sh >= 1 && sw >= 1 && sh <= MAX_STRUCT && sw <= MAX_STRUCT && (sh & 1) && (sw & 1),
@@ -624,11 +580,11 @@ int erode_n(hdem_ctx *ctx, const uint8_t *in, int h, int w, const morph_struct &
         hdem_scoped_timer tm(ctx, HDEM_K_LAGOON, (int64_t)h * w);
         const bool cross = st.sh == 3 && st.sw == 3 && !memcmp(st.bits, CROSS, 9);
         if (cross && w % 4 == 0 && ((uintptr_t)src | (uintptr_t)dst) % 4 == 0)
-            hipLaunchKernelGGL(erode_cross4_kernel, grid2(w / 4, h), dim3(NT), 0, ctx->stream, src,
-                               h, w, dst);
+            hipLaunchKernelGGL(erode_cross4_kernel, hdem_grid2(w / 4, h, NT), dim3(NT), 0,
+                               ctx->stream, src, h, w, dst);
         else
-            hipLaunchKernelGGL(morph_kernel, grid2(w, h), dim3(NT), 0, ctx->stream, src, h, w, st,
-                               0, dst);
+            hipLaunchKernelGGL(morph_kernel, hdem_grid2(w, h, NT), dim3(NT), 0, ctx->stream, src,
+                               h, w, st, 0, dst);
         src = dst;
     }
     HDEM_HIP_CHECK(hipGetLastError());
@@ -643,11 +599,10 @@ int erode_n(hdem_ctx *ctx, const uint8_t *in, int h, int w, const morph_struct &
 extern "C" int hdem_correct_nan_f32_dev(hdem_ctx *ctx, const float *dem, int H, int W, int window,
                                         float *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(dem, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, dem, out, H, W)) return rc;
     HDEM_REQUIRE(dem != out, HDEM_ERR_BAD_ARG, "the NaN correction cannot run in place");
     HDEM_REQUIRE(window >= 3, HDEM_ERR_BAD_ARG, "window must be >= 3, got %d", window);
-    if (int rc = window_ok(window, H, W)) return rc;
+    if (int rc = hdem_check_window(window, H, W)) return rc;
     // (NumPy's sum changes shape again at 128 values: windows up to 11)
     HDEM_REQUIRE(window <= 11, HDEM_ERR_BAD_ARG, "NaN correction window must be 3..11, got %d",
                  window);
@@ -655,11 +610,11 @@ extern "C" int hdem_correct_nan_f32_dev(hdem_ctx *ctx, const float *dem, int H, 
     {
         hdem_scoped_timer tm(ctx, HDEM_K_LAGOON, (int64_t)H * W);
         if (window == 3)
-            hipLaunchKernelGGL(correct_nan_kernel, grid2((W + 3) / 4, H), dim3(NT), 0, ctx->stream,
-                               dem, H, W, out);
+            hipLaunchKernelGGL(correct_nan_kernel, hdem_grid2((W + 3) / 4, H, NT), dim3(NT), 0,
+                               ctx->stream, dem, H, W, out);
         else
-            hipLaunchKernelGGL(correct_nan_ws_kernel, grid2(W, H), dim3(NT), 0, ctx->stream, dem, H,
-                               W, window / 2, out);
+            hipLaunchKernelGGL(correct_nan_ws_kernel, hdem_grid2(W, H, NT), dim3(NT), 0,
+                               ctx->stream, dem, H, W, window / 2, out);
     }
     HDEM_HIP_CHECK(hipGetLastError());
     return HDEM_OK;
@@ -668,10 +623,9 @@ extern "C" int hdem_correct_nan_f32_dev(hdem_ctx *ctx, const float *dem, int H, 
 extern "C" int hdem_majority_f32_dev(hdem_ctx *ctx, const float *img, int H, int W, int window,
                                      float *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(img, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, img, out, H, W)) return rc;
     HDEM_REQUIRE(img != out, HDEM_ERR_BAD_ARG, "the majority filter cannot run in place");
-    if (int rc = window_ok(window, H, W)) return rc;
+    if (int rc = hdem_check_window(window, H, W)) return rc;
     HDEM_REQUIRE(window >= 3 && window <= MMAX, HDEM_ERR_BAD_ARG,
                  "majority window must be 3..%d, got %d", MMAX, window);
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
@@ -702,8 +656,7 @@ extern "C" int hdem_binary_erosion_u8_dev(hdem_ctx *ctx, const uint8_t *mask, in
                                           const uint8_t *structure, int sh, int sw, int iterations,
                                           uint8_t *tmp, uint8_t *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(mask, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, mask, out, H, W)) return rc;
     HDEM_REQUIRE(iterations >= 1, HDEM_ERR_BAD_ARG, "iterations must be >= 1, got %d", iterations);
     HDEM_REQUIRE(mask != out && (iterations == 1 || (tmp && tmp != out && tmp != mask)),
                  HDEM_ERR_BAD_ARG, "erosion needs distinct in / tmp / out buffers");
@@ -719,8 +672,7 @@ extern "C" int hdem_binary_closing_u8_dev(hdem_ctx *ctx, const uint8_t *mask, in
                                           const uint8_t *structure, int sh, int sw, uint8_t *tmp,
                                           uint8_t *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(mask, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, mask, out, H, W)) return rc;
     HDEM_REQUIRE(tmp && mask != out && tmp != out && tmp != mask, HDEM_ERR_BAD_ARG,
                  "closing needs distinct in / tmp / out buffers");
     morph_struct st;
@@ -730,9 +682,9 @@ extern "C" int hdem_binary_closing_u8_dev(hdem_ctx *ctx, const uint8_t *mask, in
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     {
         hdem_scoped_timer tm(ctx, HDEM_K_LAGOON, (int64_t)H * W * 2);
-        hipLaunchKernelGGL(morph_kernel, grid2(W, H), dim3(NT), 0, ctx->stream, mask, H, W, st, 1,
-                           tmp);
-        hipLaunchKernelGGL(morph_kernel, grid2(W, H), dim3(NT), 0, ctx->stream,
+        hipLaunchKernelGGL(morph_kernel, hdem_grid2(W, H, NT), dim3(NT), 0, ctx->stream, mask, H,
+                           W, st, 1, tmp);
+        hipLaunchKernelGGL(morph_kernel, hdem_grid2(W, H, NT), dim3(NT), 0, ctx->stream,
                            (const uint8_t *)tmp, H, W, st, 0, out);
     }
     HDEM_HIP_CHECK(hipGetLastError());
@@ -742,8 +694,7 @@ extern "C" int hdem_binary_closing_u8_dev(hdem_ctx *ctx, const uint8_t *mask, in
 template <typename T>
 static int grey_dilation_dev(hdem_ctx *ctx, const T *img, int H, int W, int sy, int sx, T *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(img, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, img, out, H, W)) return rc;
     HDEM_REQUIRE(img != out, HDEM_ERR_BAD_ARG, "grey dilation cannot run in place");
     HDEM_REQUIRE(sy >= 1 && sx >= 1 && (sy & 1) && (sx & 1) && sy <= 31 && sx <= 31,
                  HDEM_ERR_BAD_ARG, "grey dilation size must be odd and <= 31, got (%d, %d)", sy, sx);
@@ -772,8 +723,6 @@ extern "C" int hdem_grey_dilation_f64_dev(hdem_ctx *ctx, const double *img, int 
                                           int sx, double *out)
 { return grey_dilation_dev<double>(ctx, img, H, W, sy, sx, out); }
 
-static size_t round16(size_t n) { return (n + 15) / 16 * 16; }
-
 static int tidying(hdem_ctx *ctx, const float *img, int H, int W, float *out, uint8_t *positive)
 {
     hdem_scoped_timer tm(ctx, HDEM_K_LAGOON, (int64_t)H * W);
@@ -786,10 +735,9 @@ static int tidying(hdem_ctx *ctx, const float *img, int H, int W, float *out, ui
 extern "C" int hdem_tidying_lagoons_f32_dev(hdem_ctx *ctx, const float *img, int H, int W,
                                             float *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(img, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, img, out, H, W)) return rc;
     HDEM_REQUIRE(img != out, HDEM_ERR_BAD_ARG, "tidying cannot run in place");
-    if (int rc = window_ok(7, H, W)) return rc;
+    if (int rc = hdem_check_window(7, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     return tidying(ctx, img, H, W, out, nullptr);
 }
@@ -800,11 +748,10 @@ extern "C" int hdem_tidying_lagoons_f32_dev(hdem_ctx *ctx, const float *img, int
 extern "C" int hdem_lagoons_detection_f32_dev(hdem_ctx *ctx, const float *hsheds, int H, int W,
                                               float *fixed, float *values, uint8_t *mask)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(hsheds, mask, H, W)) return rc;
-    if (int rc = window_ok(11, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, hsheds, mask, H, W)) return rc;
+    if (int rc = hdem_check_window(11, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)H * W, fbytes = round16(n * sizeof(float));
+    const size_t n = (size_t)H * W, fbytes = hdem_round16(n * sizeof(float));
     char *scratch = (char *)hdem_arena(ctx, 3 * fbytes);
     if (!scratch) return HDEM_ERR_OOM;
     float *major = (float *)scratch;

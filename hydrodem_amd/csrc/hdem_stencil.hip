@@ -384,8 +384,7 @@ int hdem_certify_d8_launch(hdem_ctx *ctx, const float *z, const float *w, int H,
 
 extern "C" int hdem_d8_f32_dev(hdem_ctx *ctx, const float *z, int H, int W, uint8_t *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(z, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, z, out, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     int tx, nt = tiles_of(H, W, TH, &tx);
     int vec = (W % 4 == 0) && ((uintptr_t)out % 4 == 0);
@@ -400,23 +399,20 @@ extern "C" int hdem_d8_f32_dev(hdem_ctx *ctx, const float *z, int H, int W, uint
 
 extern "C" int hdem_d8_f32(hdem_ctx *ctx, const float *z, int H, int W, uint8_t *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(z, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, z, out, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     size_t n = (size_t)H * W;
     hdem_dbuf dz, dout;
-    if (int rc = dz.alloc(ctx, n * sizeof(float))) return rc;
+    if (int rc = dz.upload(ctx, z, n * sizeof(float))) return rc;
     if (int rc = dout.alloc(ctx, n)) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, dz.p, z, n * sizeof(float))) return rc;
-    if (int rc = hdem_d8_f32_dev(ctx, (const float *)dz.p, H, W, (uint8_t *)dout.p)) return rc;
-    return hdem_memcpy_d2h(ctx, out, dout.p, n);
+    if (int rc = hdem_d8_f32_dev(ctx, dz.as<const float>(), H, W, dout.as<uint8_t>())) return rc;
+    return dout.download(out, n);
 }
 
 template <typename T>
 static int boxmean_dev(hdem_ctx *ctx, const T *x, int H, int W, int do_round, T *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(x, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, x, out, H, W)) return rc;
     HDEM_REQUIRE((const void *)x != (const void *)out, HDEM_ERR_BAD_ARG,
                  "box mean cannot run in place");
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
@@ -433,16 +429,14 @@ static int boxmean_dev(hdem_ctx *ctx, const T *x, int H, int W, int do_round, T 
 template <typename T>
 static int boxmean_host(hdem_ctx *ctx, const T *x, int H, int W, int do_round, T *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(x, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, x, out, H, W)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     size_t bytes = (size_t)H * W * sizeof(T);
     hdem_dbuf dx, dout;
-    if (int rc = dx.alloc(ctx, bytes)) return rc;
+    if (int rc = dx.upload(ctx, x, bytes)) return rc;
     if (int rc = dout.alloc(ctx, bytes)) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, dx.p, x, bytes)) return rc;
-    if (int rc = boxmean_dev<T>(ctx, (const T *)dx.p, H, W, do_round, (T *)dout.p)) return rc;
-    return hdem_memcpy_d2h(ctx, out, dout.p, bytes);
+    if (int rc = boxmean_dev<T>(ctx, dx.as<const T>(), H, W, do_round, dout.as<T>())) return rc;
+    return dout.download(out, bytes);
 }
 
 extern "C" int hdem_boxmean3_f32_dev(hdem_ctx *c, const float *x, int H, int W, int r, float *o)
@@ -458,29 +452,26 @@ template <typename T>
 static int convolve_host(hdem_ctx *ctx, const T *x, int H, int W, const double *weights, int kh,
                          int kw, T *out)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(x, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, x, out, H, W)) return rc;
     HDEM_REQUIRE(weights, HDEM_ERR_BAD_ARG, "weights is null");
     HDEM_REQUIRE(kh > 0 && kw > 0 && kh <= 15 && kw <= 15, HDEM_ERR_BAD_ARG,
                  "weights shape %d x %d not supported (1..15 per axis)", kh, kw);
     HDEM_REQUIRE(kh % 2 == 1 && kw % 2 == 1, HDEM_ERR_WINDOW_EVEN,
                  "weights shape %d x %d must be odd on both axes", kh, kw);
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
-    size_t n = (size_t)H * W;
+    size_t n = (size_t)H * W, bytes = n * sizeof(T);
     hdem_dbuf dx, dout, dw;
-    if (int rc = dx.alloc(ctx, n * sizeof(T))) return rc;
-    if (int rc = dout.alloc(ctx, n * sizeof(T))) return rc;
-    if (int rc = dw.alloc(ctx, sizeof(double) * kh * kw)) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, dx.p, x, n * sizeof(T))) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, dw.p, weights, sizeof(double) * kh * kw)) return rc;
+    if (int rc = dx.upload(ctx, x, bytes)) return rc;
+    if (int rc = dw.upload(ctx, weights, sizeof(double) * kh * kw)) return rc;
+    if (int rc = dout.alloc(ctx, bytes)) return rc;
     {
         hdem_scoped_timer tm(ctx, HDEM_K_CONVOLVE, (int64_t)n);
         hipLaunchKernelGGL(convolve_kernel<T>, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0,
-                           ctx->stream, (const T *)dx.p, H, W, (const double *)dw.p, kh, kw,
-                           (T *)dout.p);
+                           ctx->stream, dx.as<const T>(), H, W, dw.as<const double>(), kh, kw,
+                           dout.as<T>());
     }
     HDEM_HIP_CHECK(hipGetLastError());
-    return hdem_memcpy_d2h(ctx, out, dout.p, n * sizeof(T));
+    return dout.download(out, bytes);
 }
 
 extern "C" int hdem_convolve_f32(hdem_ctx *ctx, const float *x, int H, int W,
@@ -498,13 +489,13 @@ static int around_host(hdem_ctx *ctx, const T *x, int64_t n, T *out)
     HDEM_REQUIRE(ctx && x && out, HDEM_ERR_BAD_ARG, "null argument");
     HDEM_REQUIRE(n > 0, HDEM_ERR_BAD_ARG, "n must be positive");
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * sizeof(T);
     hdem_dbuf dx;
-    if (int rc = dx.alloc(ctx, (size_t)n * sizeof(T))) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, dx.p, x, (size_t)n * sizeof(T))) return rc;
+    if (int rc = dx.upload(ctx, x, bytes)) return rc;
     hipLaunchKernelGGL(around_kernel<T>, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0,
-                       ctx->stream, (const T *)dx.p, n, (T *)dx.p);
+                       ctx->stream, dx.as<const T>(), n, dx.as<T>());
     HDEM_HIP_CHECK(hipGetLastError());
-    return hdem_memcpy_d2h(ctx, out, dx.p, (size_t)n * sizeof(T));
+    return dx.download(out, bytes);
 }
 
 extern "C" int hdem_around_f32(hdem_ctx *c, const float *x, int64_t n, float *o)

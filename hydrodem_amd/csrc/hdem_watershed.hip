@@ -302,8 +302,7 @@ __global__ __launch_bounds__(NT) void watershed_final_kernel(
 int check_args(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const uint32_t *seeds, int flags,
                uint32_t *out, uint32_t *outlets, hdem_watershed_stats *stats, d8_grid *g)
 {
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(d8, out, H, W)) return rc;
+    if (int rc = hdem_check_call(ctx, d8, out, H, W)) return rc;
     if (int rc = d8_grid_of("watersheds", H, W, g)) return rc;
     HDEM_REQUIRE(!(flags & ~HDEM_WS_COMPACT), HDEM_ERR_BAD_ARG, "unknown watershed flags 0x%x",
                  flags);
@@ -312,10 +311,7 @@ int check_args(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const uint32_t *s
                  "compact labels number the outlets: they cannot be combined with pour points");
     HDEM_REQUIRE(compact == (outlets != nullptr), HDEM_ERR_BAD_ARG,
                  "outlets must be given with HDEM_WS_COMPACT and only then");
-    HDEM_REQUIRE(!stats || stats->struct_size >= sizeof(uint32_t), HDEM_ERR_BAD_ARG,
-                 "hdem_watershed_stats.struct_size is %u: set it to sizeof(hdem_watershed_stats)",
-                 stats ? stats->struct_size : 0u);
-    return HDEM_OK;
+    return d8_check_stats(stats, "hdem_watershed_stats");
 }
 
 }  // namespace
@@ -401,27 +397,22 @@ extern "C" int hdem_watershed_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W,
     d8_grid g;
     if (int rc = check_args(ctx, d8, H, W, seeds, flags, out, outlets, stats, &g)) return rc;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)H * W;
+    const size_t n = (size_t)H * W, bytes = n * sizeof(uint32_t);
     hdem_dbuf dd8, dseeds, dout, doutlets;
-    if (int rc = dd8.alloc(ctx, n)) return rc;
-    if (int rc = dout.alloc(ctx, n * sizeof(uint32_t))) return rc;
-    if (int rc = hdem_memcpy_h2d(ctx, dd8.p, d8, n)) return rc;
-    if (seeds) {
-        if (int rc = dseeds.alloc(ctx, n * sizeof(uint32_t))) return rc;
-        if (int rc = hdem_memcpy_h2d(ctx, dseeds.p, seeds, n * sizeof(uint32_t))) return rc;
-    }
+    if (int rc = dd8.upload(ctx, d8, n)) return rc;
+    if (int rc = dseeds.upload(ctx, seeds, bytes)) return rc;
+    if (int rc = dout.alloc(ctx, bytes)) return rc;
     if (outlets)
-        if (int rc = doutlets.alloc(ctx, n * sizeof(uint32_t))) return rc;
+        if (int rc = doutlets.alloc(ctx, bytes)) return rc;
     // the basin count is needed here whether the caller asked for stats or not
     hdem_watershed_stats st = {};
     st.struct_size = sizeof(st);
-    const int rc = hdem_watershed_u8_dev(ctx, (const uint8_t *)dd8.p, H, W,
-                                         (const uint32_t *)dseeds.p, flags, (uint32_t *)dout.p,
-                                         (uint32_t *)doutlets.p, &st);
+    const int rc = hdem_watershed_u8_dev(ctx, dd8.as<const uint8_t>(), H, W,
+                                         dseeds.as<const uint32_t>(), flags, dout.as<uint32_t>(),
+                                         doutlets.as<uint32_t>(), &st);
     d8_publish(stats, st);
     if (rc) return rc;
     if (outlets)
-        if (int rc2 = hdem_memcpy_d2h(ctx, outlets, doutlets.p, (size_t)st.basins * sizeof(uint32_t)))
-            return rc2;
-    return hdem_memcpy_d2h(ctx, out, dout.p, n * sizeof(uint32_t));
+        if (int rc2 = doutlets.download(outlets, (size_t)st.basins * sizeof(uint32_t))) return rc2;
+    return dout.download(out, bytes);
 }

@@ -57,6 +57,15 @@ from ..sliding_window import (SlidingWindow, CircularWindow,  # noqa: F401
 from .. import backend
 
 
+def _check_raster(name, raster, dtype, takes):
+    """``raster`` (a host array or a device raster) is 2-D and of ``dtype``, or a ValueError
+    in the words of the operator ``name``, which ``takes`` that kind of raster."""
+    if raster.dtype != dtype:
+        raise ValueError(f"{name} takes {takes}, got {raster.dtype}")
+    if len(raster.shape) != 2:
+        raise ValueError(f"{name} takes a 2-D raster, got {len(raster.shape)} dimensions")
+
+
 class QuadraticFilter(Filter):  # pylint: disable=too-few-public-methods
     """Least-squares quadratic smoothing over a ``window_size`` square window;
     the ring of ``window_size // 2`` cells is returned unchanged
@@ -154,8 +163,7 @@ class GrovesCorrection(ComposedFilter):  # pylint: disable=too-few-public-method
         groves_class, window, thr = self._params()
         if not self._is_mask(groves_class):
             raise NotImplementedError("the fused groves kernel takes a 0 / 1 class raster")
-        with backend.DeviceRaster.from_host(backend.mask_bytes(groves_class),
-                                            dtype=np.uint8, ctx=raster.ctx) as g:
+        with backend.on_device(backend.mask_bytes(groves_class), np.uint8, raster.ctx) as g:
             out = backend.groves_dev(raster, g, window, thr, 1)
             raster.ctx.synchronize()
         return out
@@ -201,8 +209,7 @@ class GrovesCorrectionsIter(ComposedFilter):  # pylint: disable=too-few-public-m
         if params is None:
             return ComposedFilter.apply_device(self, raster)
         groves_class, window, thr = params
-        with backend.DeviceRaster.from_host(backend.mask_bytes(groves_class),
-                                            dtype=np.uint8, ctx=raster.ctx) as g:
+        with backend.on_device(backend.mask_bytes(groves_class), np.uint8, raster.ctx) as g:
             out = backend.groves_dev(raster, g, window, thr, len(self.filters))
             raster.ctx.synchronize()
         return out
@@ -321,21 +328,14 @@ class FlowAccumulation(Filter):  # pylint: disable=too-few-public-methods
     def __init__(self):
         self.stats = {}
 
-    @staticmethod
-    def _check(dtype, ndim):
-        if dtype != np.uint8:
-            raise ValueError(f"FlowAccumulation takes uint8 D8 codes, got {dtype}")
-        if ndim != 2:
-            raise ValueError(f"FlowAccumulation takes a 2-D raster, got {ndim} dimensions")
-
     def apply(self, image_to_filter):
         super().apply(image_to_filter)
-        self._check(image_to_filter.dtype, image_to_filter.ndim)
+        _check_raster("FlowAccumulation", image_to_filter, np.uint8, "uint8 D8 codes")
         out, self.stats = backend.flowacc(image_to_filter, return_stats=True)
         return out
 
     def apply_device(self, raster):
-        self._check(raster.dtype, len(raster.shape))
+        _check_raster("FlowAccumulation", raster, np.uint8, "uint8 D8 codes")
         out, self.stats = backend.flowacc_dev(raster)
         return out
 
@@ -392,7 +392,7 @@ class Watersheds(Filter):  # pylint: disable=too-few-public-methods
         self._seeds = self._points = None
         if pour_points is None:
             return
-        if hasattr(pour_points, "ptr") and hasattr(pour_points, "to_host"):   # DeviceRaster
+        if backend.is_device_raster(pour_points):
             if pour_points.dtype != np.uint32 or len(pour_points.shape) != 2:
                 raise ValueError("a device seeds raster is 2-D uint32, got "
                                  f"{pour_points.dtype} {tuple(pour_points.shape)}")
@@ -441,16 +441,9 @@ class Watersheds(Filter):  # pylint: disable=too-few-public-methods
             raise ValueError(f"seeds are {tuple(self._seeds.shape)}, the codes {tuple(shape)}")
         return self._seeds
 
-    @staticmethod
-    def _check(dtype, ndim):
-        if dtype != np.uint8:
-            raise ValueError(f"Watersheds takes uint8 D8 codes, got {dtype}")
-        if ndim != 2:
-            raise ValueError(f"Watersheds takes a 2-D raster, got {ndim} dimensions")
-
     def apply(self, image_to_filter):
         super().apply(image_to_filter)
-        self._check(image_to_filter.dtype, image_to_filter.ndim)
+        _check_raster("Watersheds", image_to_filter, np.uint8, "uint8 D8 codes")
         seeds = self._host_seeds(image_to_filter.shape)
         if seeds is not None and not isinstance(seeds, np.ndarray):
             seeds = seeds.to_host()
@@ -459,22 +452,11 @@ class Watersheds(Filter):  # pylint: disable=too-few-public-methods
         return out
 
     def apply_device(self, raster):
-        self._check(raster.dtype, len(raster.shape))
-        seeds = self._host_seeds(raster.shape)
-        mine = isinstance(seeds, np.ndarray)
-        if mine:
-            seeds = backend.DeviceRaster.from_host(seeds, dtype=np.uint32, ctx=raster.ctx)
-        try:
+        _check_raster("Watersheds", raster, np.uint8, "uint8 D8 codes")
+        with backend.on_device(self._host_seeds(raster.shape), np.uint32, raster.ctx) as seeds:
             out, self.outlets, self.stats = backend.watershed_dev(raster, seeds,
                                                                   self.labels == "compact")
-        finally:
-            if mine:
-                seeds.free()
         return out
-
-
-def _is_device_raster(operand):
-    return hasattr(operand, "ptr") and hasattr(operand, "to_host")
 
 
 class _FlowTrace(Filter):  # pylint: disable=too-few-public-methods
@@ -489,7 +471,7 @@ class _FlowTrace(Filter):  # pylint: disable=too-few-public-methods
                                      ("dem", dem, (np.float32,))):
             if operand is None:
                 continue
-            if not (isinstance(operand, np.ndarray) or _is_device_raster(operand)):
+            if not (isinstance(operand, np.ndarray) or backend.is_device_raster(operand)):
                 raise ValueError(f"{name} is a NumPy array or a DeviceRaster, got "
                                  f"{type(operand)}")
             if len(operand.shape) != 2:
@@ -516,25 +498,18 @@ class _FlowTrace(Filter):  # pylint: disable=too-few-public-methods
     def _trace(self, image_to_filter, want):
         Filter.apply(self, image_to_filter)
         self._check(image_to_filter, want)
-        operands = [o.to_host() if _is_device_raster(o) else o for o in (self.streams, self.dem)]
+        operands = [o.to_host() if backend.is_device_raster(o) else o
+                    for o in (self.streams, self.dem)]
         outs, self.stats = backend.flowtrace(image_to_filter, operands[0], self.threshold,
                                              operands[1], self.cellsize, want)
         return outs
 
     def _trace_device(self, raster, want):
         self._check(raster, want)
-        operands, mine = [], []
-        try:
-            for o in (self.streams, self.dem):
-                if isinstance(o, np.ndarray):
-                    o = backend.DeviceRaster.from_host(o, dtype=o.dtype, ctx=raster.ctx)
-                    mine.append(o)
-                operands.append(o)
-            outs, self.stats = backend.flowtrace_dev(raster, operands[0], self.threshold,
-                                                     operands[1], self.cellsize, want)
-        finally:
-            for o in mine:
-                o.free()
+        with backend.on_device(self.streams, ctx=raster.ctx) as streams, \
+                backend.on_device(self.dem, ctx=raster.ctx) as dem:
+            outs, self.stats = backend.flowtrace_dev(raster, streams, self.threshold, dem,
+                                                     self.cellsize, want)
         return outs
 
 
@@ -659,7 +634,7 @@ class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods
     def __init__(self, *, dem, keep_partial_results=False):
         if dem is None:
             raise ValueError("ResolveFlats needs the dem the codes were made on")
-        if not (isinstance(dem, np.ndarray) or _is_device_raster(dem)):
+        if not (isinstance(dem, np.ndarray) or backend.is_device_raster(dem)):
             raise ValueError(f"dem is a NumPy array or a DeviceRaster, got {type(dem)}")
         if len(dem.shape) != 2:
             raise ValueError(f"dem is a 2-D raster, got {len(dem.shape)} dimensions")
@@ -673,22 +648,16 @@ class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
         backend.resolve_flats_args(image_to_filter, self.dem)
-        dem = self.dem.to_host() if _is_device_raster(self.dem) else self.dem
+        dem = self.dem.to_host() if backend.is_device_raster(self.dem) else self.dem
         out, self.distance, self.stats = backend.resolve_flats(
             image_to_filter, dem, self.keep_partial_results)
         return out
 
     def apply_device(self, raster):
         backend.resolve_flats_args(raster, self.dem)
-        dem, mine = self.dem, isinstance(self.dem, np.ndarray)
-        if mine:
-            dem = backend.DeviceRaster.from_host(dem, dtype=np.float32, ctx=raster.ctx)
-        try:
+        with backend.on_device(self.dem, np.float32, raster.ctx) as dem:
             out, self.distance, self.stats = backend.resolve_flats_dev(
                 raster, dem, self.keep_partial_results)
-        finally:
-            if mine:
-                dem.free()
         return out
 
 
@@ -827,15 +796,9 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
         self.stats = {}
         self.filled = self.codes = self.accumulation = self.distance = None
 
-    def _check(self, dtype, ndim):
-        if dtype != np.float32:
-            raise ValueError(f"DemToHAND takes a float32 DEM, got {dtype}")
-        if ndim != 2:
-            raise ValueError(f"DemToHAND takes a 2-D raster, got {ndim} dimensions")
-
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
-        self._check(image_to_filter.dtype, image_to_filter.ndim)
+        _check_raster("DemToHAND", image_to_filter, np.float32, "a float32 DEM")
         with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z:
             with self.apply_device(z) as hand:
                 out = hand.to_host()
@@ -846,7 +809,7 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
         return out
 
     def apply_device(self, raster):
-        self._check(raster.dtype, len(raster.shape))
+        _check_raster("DemToHAND", raster, np.float32, "a float32 DEM")
         fill, _, accumulate = self.filters
         self.filled = self.codes = self.accumulation = self.distance = None
         kept = []

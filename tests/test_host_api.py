@@ -37,6 +37,17 @@ def test_library_exports_every_declared_symbol():
     assert declared == bound, declared ^ bound
 
 
+@pytest.mark.parametrize("name", [n for n in backend.SIGNATURES
+                                  if n not in ("hdem_device_count", "hdem_init", "hdem_shutdown")])
+def test_every_entry_point_refuses_a_null_context(name):
+    """The prologue every entry point shares, where no device exists: a null context is
+    BAD_ARG with a text, whatever else is passed (0, 0.0 or NULL by the argument's type)."""
+    lib = backend.load_library()
+    rc = getattr(lib, name)(*[t() for t in backend.SIGNATURES[name]])
+    assert rc == backend.BAD_ARG
+    assert lib.hdem_last_error() in (b"ctx is null", b"null argument")
+
+
 def test_library_loads_without_gpu_and_fails_loudly():
     lib = backend.load_library()
     assert lib.hdem_version() >= 100
