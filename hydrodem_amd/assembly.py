@@ -14,9 +14,11 @@ branches with the element-wise filters and smooth the sum:
 Called like that -- unchanged, through the drop-in package -- every ``apply`` is a host
 array in, a host array out.  :func:`final_dem` is the same sequence of the same filter
 objects on device rasters (``apply_device``): each input goes up once, the eight
-operators run in HBM, the result comes down once.  The arithmetic is the reference's
-(float64 where the pipeline holds float64), so the result is bit for bit the reference's
-(`tests/golden/assembly.npz`).
+operators run in HBM, the result comes down once.  The arithmetic and the types are the
+reference's: the masks count as the int64 grids the orchestration holds there (``mask * 1``,
+the XOR of the clip), so the complement is int64 and both products are float64 whatever
+the elevations' float type (float32 * int64 promotes).  The result is bit for bit the
+reference's (`tests/golden/assembly.npz`, tests/test_gpu_elementwise.py).
 """
 
 import numpy as np
@@ -27,6 +29,7 @@ from .filters.simple_filters import AdditionFilter, ProductFilter, SubtractionFi
 
 
 def _mask(a):
+    """A 0 / 1 grid of any type as the bytes that stand for the reference's int64 mask."""
     a = np.asarray(a)
     return a.astype(np.uint8) if a.dtype != np.uint8 else a
 
@@ -41,8 +44,9 @@ def final_dem(srtm, mask_lagoons, hsheds_nan_fixed, lagoons_values, rivers, ctx=
     """``final_dem`` of `hydro_dem_process.py:147-149` from the results of the three
     branches: ``srtm`` (`image_srtm.py:199`), ``lagoons.mask_lagoons`` /
     ``.hsheds_nan_fixed`` / ``.lagoons_values`` (`custom_filters.py:656-660`) and ``rivers``
-    (`image_hsheds.py:203-205`), host arrays.  Returns the host array the reference
-    returns (the elevations' float type); with ``keep_terms`` also the three terms."""
+    (`image_hsheds.py:203-205`), host arrays; the masks are 0 / 1 grids (bool, uint8 or
+    int64) and are read as int64.  Returns the host array the reference returns (float64,
+    also for float32 elevations); with ``keep_terms`` also the three terms."""
     up = lambda a: backend.DeviceRaster.from_host(a, ctx=ctx)      # noqa: E731
     rasters = []
 

@@ -768,35 +768,99 @@ def blockmax_dev(z, block, out=None):
     return out
 
 
-def elementwise_dev(op, image, operand, out_dtype=None, out=None):
-    """``op(image, operand)`` cell by cell on device rasters (``hdem_elementwise_dev``);
-    ``operand`` is a :class:`DeviceRaster` of the same shape or a scalar.  Result type:
-    ``out_dtype`` or, like NumPy on the stored types, uint8 for comparisons / NONZERO and
-    for a product of two masks, float64 as soon as one side is float64, else float32."""
+def logical_type(dtype):
+    """The NumPy type a raster of ``dtype`` stands for in the element-wise algebra: a uint8
+    raster is the device form of NumPy's bool / int64 masks and counts as int64."""
+    dtype = np.dtype(dtype)
+    return np.dtype(np.int64) if dtype == np.uint8 else dtype
+
+
+def elementwise_work_type(image_dtype, operand):
+    """The type NumPy would do ``ufunc(image, operand)`` in: ``np.result_type`` of the
+    logical types.  ``operand`` is a dtype (a raster's logical type) or a scalar; a Python
+    scalar is weak (it takes the image's float width), a NumPy scalar or 0-d array counts
+    with its own type.  One of float32, float64 and int64."""
+    if isinstance(operand, (np.dtype, type)):
+        other = logical_type(operand)
+    elif isinstance(operand, (np.generic, np.ndarray)):
+        other = operand.dtype
+    elif isinstance(operand, (bool, int, float)):
+        other = operand
+    else:
+        raise ValueError(f"element-wise operand {type(operand).__name__} is neither a "
+                         "raster nor a real scalar")
+    work = np.result_type(logical_type(image_dtype), other)
+    if work not in (np.float32, np.float64, np.int64):
+        raise ValueError(f"element-wise operators work in float32, float64 or int64, "
+                         f"not {work}")
+    return work
+
+
+def elementwise_dev(op, image, operand, out_dtype=None, out=None, operand_type=None):
+    """``op(image, operand)`` cell by cell on device rasters (``hdem_elementwise_dev``), with
+    the values and the result type of the NumPy ufunc on the *logical* types
+    (:func:`logical_type`: a uint8 raster stands for an int64 mask).
+
+    ``operand`` is a :class:`DeviceRaster` of the same shape or a scalar; ``operand_type``
+    names the NumPy type an operand raster stands for where that is not its own (a bool
+    array that went up as bytes).  The work type is ``np.result_type`` of the two
+    (:func:`elementwise_work_type`): float32 with int64 is float64, a Python scalar takes
+    the raster's float width, an ``np.float64`` scalar makes float64.  The kernel computes
+    in double, so a scalar that NumPy would round to float32 is rounded here before it is
+    passed; the double result of two float32 values, rounded once on the store, is then the
+    float32 result (the product is exact in double; 53 >= 2 * 24 + 2 bits make the second
+    rounding of a sum or difference harmless).
+
+    Result type: ``out.dtype``, ``out_dtype``, or uint8 for comparisons / NONZERO and the
+    work type for the arithmetic.  An int64 result is stored as uint8 only for a uint8
+    image times the scalar 0 or 1 (``mask * 1``); nothing says of two uint8 rasters that
+    they hold masks, so their product is int64.  Integers are exact within +-2^53.
+
+    A given type is where the double result is stored, once.  A float64 ``out_dtype`` --
+    or a float64 ``out``, which means the same here -- is therefore NumPy's
+    ``ufunc(..., dtype=float64)``: float32 values are combined in double and a Python
+    scalar stays unrounded.  It is not NumPy's ``out=``, which would work in float32 and
+    widen afterwards; the kernel has no float32 rounding in front of a wider store.  A
+    type narrower than the work type is one cast of the result, as NumPy's ``out=`` does.
+    ``out`` and ``out_dtype`` together must name the same type."""
     c = image.ctx
     raster = operand if isinstance(operand, DeviceRaster) else None
     if raster is not None and raster.shape != image.shape:
         raise ValueError(f"operand shape {raster.shape} != image shape {image.shape}")
     if image.dtype not in _EW_TYPES or (raster is not None and raster.dtype not in _EW_TYPES):
         raise ValueError("element-wise operators take float32, float64, uint8 or int64 rasters")
-    if out_dtype is None:
-        kinds = [image.dtype] + ([raster.dtype] if raster is not None else [])
+    if raster is not None:
+        work = elementwise_work_type(
+            image.dtype, np.dtype(raster.dtype if operand_type is None else operand_type))
+    else:
+        work = elementwise_work_type(image.dtype, operand)
+    if out is not None:
+        if out_dtype is not None and np.dtype(out_dtype) != out.dtype:
+            raise ValueError(f"out is a {out.dtype} raster, out_dtype says {np.dtype(out_dtype)}")
+        out_dtype = out.dtype
+    elif out_dtype is None:
         if op in (EW_GT, EW_LT, EW_NONZERO):
             out_dtype = np.uint8
-        elif any(k == np.float64 for k in kinds):
-            out_dtype = np.float64
-        elif op == EW_MUL and all(k == np.uint8 for k in kinds) and \
-                (raster is not None or float(operand) in (0.0, 1.0)):
+        elif op == EW_MUL and work == np.int64 and image.dtype == np.uint8 and \
+                raster is None and operand in (0, 1):
             out_dtype = np.uint8
         else:
-            out_dtype = np.float32
-    out = out or DeviceRaster.empty(image.shape, out_dtype, c)
+            out_dtype = work
+    scalar = 0.0
+    if raster is None:
+        # np.multiply(a, s, dtype=float64) would take the Python scalar unrounded
+        narrow = work == np.float32 and np.dtype(out_dtype) != np.float64
+        scalar = float(np.float32(operand)) if narrow else float(operand)
+    if out is None:
+        out = DeviceRaster.empty(image.shape, out_dtype, c)
+    elif out.shape != image.shape or out.dtype not in _EW_TYPES:
+        raise ValueError(f"out is {out.dtype} {out.shape}, the image has shape {image.shape}")
     n = int(np.prod(image.shape))
     c.check(c.lib.hdem_elementwise_dev(
         c.handle, int(op), image.ptr, _EW_TYPES[image.dtype],
         raster.ptr if raster is not None else None,
         _EW_TYPES[raster.dtype] if raster is not None else 0,
-        0.0 if raster is not None else float(operand), n, out.ptr, _EW_TYPES[out.dtype]))
+        scalar, n, out.ptr, _EW_TYPES[out.dtype]))
     return out
 
 
@@ -1207,6 +1271,10 @@ def convolve(x, weights):
 
 
 def around(x):
+    """``np.around(x)``: float32 and float64 on the device (other floats as float64); an
+    integer or bool array has nothing to round and comes back as ``np.around`` returns it."""
+    if np.asarray(x).dtype.kind in "iub":
+        return np.around(x)
     c = context()
     if np.asarray(x).dtype == np.float32:
         a, fn = np.ascontiguousarray(x, dtype=np.float32), c.lib.hdem_around_f32

@@ -5,10 +5,17 @@
 // two products, then the three-term sum in front of PostProcessingFinal, `:148-149`).
 //
 // One kernel: out[i] = op(image[i], operand[i] or scalar).  Rasters are float32, float64,
-// uint8 (masks) or int64 (what NumPy makes of `mask * 1`; exact below 2^53); the arithmetic is done in double -- what NumPy does for the float64 rasters
-// the pipeline holds at that point (float32 * int64 promotes), exact for float32 and mask
-// inputs -- and stored in the type the caller asks for.  HBM-bound: 4 cells per lane, one
-// vector load per operand.
+// uint8 (masks) or int64 (what NumPy makes of `mask * 1`; exact below 2^53).  The
+// arithmetic is done in double and stored in the type the caller asks for.  That is what
+// NumPy does for the float64 rasters the pipeline holds at that point (float32 * int64
+// promotes) and for masks.  For two float32 values stored as float32 it equals float32
+// arithmetic: the product is exact in double, and a sum or difference is rounded twice
+// harmlessly (53 >= 2 * 24 + 2 bits).  A scalar is used as the double it arrives as, so
+// the caller rounds it to float32 first where NumPy would (backend.elementwise_dev
+// chooses the types and does that).  Storing NaN, +-inf or a value beyond the target type
+// into an integer raster is undefined, as in C++; callers do not ask for it.
+// Pointers need only their element's alignment (a row view of an odd-width raster).
+// HBM-bound: 4 cells per lane, one vector load per operand.
 #include "hdem_internal.h"
 
 namespace {

@@ -20,6 +20,17 @@ reference returns.  ``apply_device(raster)`` is the same operator on a
 orchestration's algebra (`hydro_dem_process.py:60-91`) can stay in HBM between the
 stencils; there masks are uint8 where NumPy holds bool / int64.  The
 operand may be a scalar, a host array (uploaded for the call) or a device raster.
+
+"The same operator" means the values and the result type of that ufunc, with a uint8
+raster read as the int64 mask it stands for (``backend.elementwise_dev`` has the rule):
+float32 with int64 gives float64; a Python scalar against a float32 raster is rounded to
+float32 as NumPy does, an ``np.float64`` scalar makes the result float64; a comparison
+gives uint8 for NumPy's bool; an integer result is int64, or uint8 for ``mask * 1``.
+A host array keeps its values and its NumPy type on the way up: bool and integers
+within 0 ... 255 travel as bytes, other integers as int64, floats up to 32 bits as
+float32 and wider ones as float64, and the result type is NumPy's for the array's own
+type (a bool array against a float32 raster gives float32).  tests/test_gpu_elementwise.py
+holds the device form to NumPy on these points.
 """
 
 import numpy as np
@@ -50,13 +61,21 @@ class _Elementwise(Filter):  # pylint: disable=too-few-public-methods
         if isinstance(other, backend.DeviceRaster) or np.ndim(other) == 0:
             return backend.elementwise_dev(self.device_op, raster, other)
         host = np.asarray(other)
-        if host.dtype == bool or (host.dtype.kind in "iu" and host.size and
-                                  0 <= host.min() and host.max() <= 255):
+        kind, logical = host.dtype.kind, backend.logical_type(host.dtype)
+        if kind not in "biuf":
+            raise ValueError(f"element-wise operand of type {host.dtype}")
+        if kind == "b" or (kind in "iu" and host.size and
+                           0 <= host.min() and host.max() <= 255):
             host = host.astype(np.uint8)                   # masks travel as bytes
-        elif host.dtype != np.float64:
-            host = host.astype(np.float32)
+        elif kind in "iu":
+            host = host.astype(np.int64)                   # every value kept (to +-2^53)
+        elif host.dtype.itemsize <= 4:
+            host = host.astype(np.float32)                 # float16 fits; NumPy promotes alike
+        else:
+            host = host.astype(np.float64)
         with backend.DeviceRaster.from_host(host, ctx=raster.ctx) as operand:
-            out = backend.elementwise_dev(self.device_op, raster, operand)
+            out = backend.elementwise_dev(self.device_op, raster, operand,
+                                          operand_type=logical)
             raster.ctx.synchronize()                       # the operand is freed on exit
         return out
 

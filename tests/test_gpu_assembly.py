@@ -57,23 +57,28 @@ def test_mask_chains_on_device_equal_the_reference(gold):
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64, np.uint8])
 def test_elementwise_operators_on_every_raster_type(dtype):
+    """Expected: what NumPy returns for ``a`` and the operand (a uint8 raster stands for an
+    int64 mask), types as ``test_elementwise_cases.same`` reads them."""
+    from test_elementwise_cases import same
     rng = np.random.default_rng(3)
     a = (rng.random((37, 53)) * 9).astype(dtype)            # odd size: the scalar tail
     b = (rng.random((37, 53)) * 5).astype(np.float32)
     da, db = backend.DeviceRaster.from_host(a), backend.DeviceRaster.from_host(b)
-    wide = np.float64 if dtype == np.float64 else np.float32
-    cases = [(hd.ProductFilter(factor=db), (b.astype(np.float64) * a).astype(wide)),
-             (hd.AdditionFilter(addend=2.5), (2.5 + a.astype(np.float64)).astype(wide)),
-             (hd.SubtractionFilter(minuend=db), (b.astype(np.float64) - a).astype(wide)),
-             (hd.GreaterThan(value=4), (a > 4).astype(np.uint8)),
-             (hd.LowerThan(value=4.0), (a < 4.0).astype(np.uint8)),
-             (hd.BooleanToInteger(), a)]
+    na = a.astype(np.int64) if dtype == np.uint8 else a     # what NumPy holds for ``a``
+    wide = np.float32 if dtype == np.float32 else np.float64    # (float32 * int64 promotes)
+    cases = [(hd.ProductFilter(factor=db), b * na),
+             (hd.AdditionFilter(addend=2.5), 2.5 + na),
+             (hd.SubtractionFilter(minuend=db), b - na),
+             (hd.GreaterThan(value=4), na > 4),
+             (hd.LowerThan(value=4.0), na < 4.0),
+             (hd.BooleanToInteger(), na * 1)]
     for f, want in cases:
         got = f.apply_device(da)
-        assert got.dtype == want.dtype and np.array_equal(got.to_host(), want), type(f).__name__
+        assert same(got.to_host(), want), type(f).__name__
+        assert got.dtype == (wide if want.dtype.kind == "f" else np.uint8), type(f).__name__
     # a host array as operand is uploaded for the call
     got = hd.ProductFilter(factor=b).apply_device(da)
-    assert np.array_equal(got.to_host(), (b.astype(np.float64) * a).astype(wide))
+    assert got.dtype == wide and same(got.to_host(), b * na)
     with pytest.raises(ValueError, match="operand shape"):
         hd.ProductFilter(factor=np.ones((3, 3), np.float32)).apply_device(da)
 
