@@ -21,6 +21,8 @@ the elevations' float type (float32 * int64 promotes).  The result is bit for bi
 reference's (`tests/golden/assembly.npz`, tests/test_gpu_elementwise.py).
 """
 
+import contextlib
+
 import numpy as np
 
 from . import backend
@@ -47,17 +49,12 @@ def final_dem(srtm, mask_lagoons, hsheds_nan_fixed, lagoons_values, rivers, ctx=
     (`image_hsheds.py:203-205`), host arrays; the masks are 0 / 1 grids (bool, uint8 or
     int64) and are read as int64.  Returns the host array the reference returns (float64,
     also for float32 elevations); with ``keep_terms`` also the three terms."""
-    up = lambda a: backend.DeviceRaster.from_host(a, ctx=ctx)      # noqa: E731
-    rasters = []
-
-    def own(r):
-        rasters.append(r)
-        return r
-
-    try:
-        d_srtm, d_hs = own(up(_elevations(srtm))), own(up(_elevations(hsheds_nan_fixed)))
-        d_values = own(up(_elevations(lagoons_values)))
-        d_lagoons, d_rivers = own(up(_mask(mask_lagoons))), own(up(_mask(rivers)))
+    with contextlib.ExitStack() as stack:
+        own = stack.enter_context               # every raster made here goes on leaving
+        up = lambda a: own(backend.DeviceRaster.from_host(a, ctx=ctx))      # noqa: E731
+        d_srtm, d_hs = up(_elevations(srtm)), up(_elevations(hsheds_nan_fixed))
+        d_values = up(_elevations(lagoons_values))
+        d_lagoons, d_rivers = up(_mask(mask_lagoons)), up(_mask(rivers))
         both = own(AdditionFilter(addend=d_lagoons).apply_device(d_rivers))
         neither = own(SubtractionFilter(minuend=1).apply_device(both))
         first = own(ProductFilter(factor=d_srtm).apply_device(neither))
@@ -69,6 +66,3 @@ def final_dem(srtm, mask_lagoons, hsheds_nan_fixed, lagoons_values, rivers, ctx=
         if keep_terms:
             return out, (first.to_host(), d_values.to_host(), third.to_host())
         return out
-    finally:
-        for r in rasters:
-            r.free()

@@ -516,8 +516,13 @@ class DeviceRaster:
         return cls(ctx or context(), int(ptr), shape, dtype, owner=False,
                    keepalive=keepalive)
 
-    def to_host(self):
-        out = host_empty(self.shape, self.dtype)
+    def to_host(self, out=None):
+        """The raster as a host array: a fresh one (:func:`host_empty`), or ``out``, a
+        C-contiguous array of the raster's type and size that the caller wants written."""
+        if out is None:
+            out = host_empty(self.shape, self.dtype)
+        elif not out.flags.c_contiguous or (out.dtype, out.nbytes) != (self.dtype, self.nbytes):
+            raise ValueError(f"out is not a contiguous {self.dtype} array of {self.nbytes} bytes")
         self.ctx.check(self.ctx.lib.hdem_memcpy_d2h(self.ctx.handle,
                                                     out.ctypes.data, self.ptr,
                                                     out.nbytes))
@@ -558,6 +563,26 @@ def on_device(operand, dtype=None, ctx=None):
         yield raster
 
 
+@contextlib.contextmanager
+def result_raster(out, shape, dtype, ctx):
+    """The raster an operator writes a result into: ``out``, or a fresh one when ``None``.
+
+    Who frees what, all over the package.  A raster a function allocates and does not return
+    (an uploaded operand, a scratch, a stage of a chain) is released by a ``with`` block.  One
+    it allocates for the caller is the caller's once returned, and is freed here if the block
+    raises first; one the caller passed in is never freed.  ``DeviceRaster.__del__`` is the
+    net under user code: nothing in here counts on it."""
+    if out is not None:
+        yield out
+        return
+    fresh = DeviceRaster.empty(shape, dtype, ctx)
+    try:
+        yield fresh
+    except BaseException:
+        fresh.free()
+        raise
+
+
 # ---------------------------------------------------------------------------
 # device-resident operators (thin: one C call each)
 # ---------------------------------------------------------------------------
@@ -569,9 +594,9 @@ def _need(r, dtype):
 
 def d8_dev(z, out=None):
     _need(z, np.float32)
-    out = out or DeviceRaster.empty(z.shape, np.uint8, z.ctx)
     c = z.ctx
-    c.check(c.lib.hdem_d8_f32_dev(c.handle, z.ptr, z.shape[0], z.shape[1], out.ptr))
+    with result_raster(out, z.shape, np.uint8, c) as out:
+        c.check(c.lib.hdem_d8_f32_dev(c.handle, z.ptr, z.shape[0], z.shape[1], out.ptr))
     return out
 
 
@@ -579,11 +604,11 @@ def flowacc_dev(codes, out=None):
     """D8 flow accumulation of a uint8 code raster (``hdem_flowacc_u8_dev``): a uint32
     raster and the stats dict.  Synchronises (the call reads its validity counters)."""
     _need(codes, np.uint8)
-    out = out or DeviceRaster.empty(codes.shape, np.uint32, codes.ctx)
     c = codes.ctx
     st = FlowAccStats()
-    c.check(c.lib.hdem_flowacc_u8_dev(c.handle, codes.ptr, codes.shape[0], codes.shape[1],
-                                      out.ptr, ctypes.byref(st)))
+    with result_raster(out, codes.shape, np.uint32, c) as out:
+        c.check(c.lib.hdem_flowacc_u8_dev(c.handle, codes.ptr, codes.shape[0], codes.shape[1],
+                                          out.ptr, ctypes.byref(st)))
     return out, st.as_dict()
 
 
@@ -600,23 +625,20 @@ def watershed_dev(codes, seeds=None, compact=False, out=None):
         if compact:
             raise ValueError("compact labels number the outlets: no pour points with them")
     c = codes.ctx
-    out = out or DeviceRaster.empty(codes.shape, np.uint32, c)
     st = WatershedStats()
-    # every cell may be an outlet: room for all, the first K come back
-    room = DeviceRaster.empty(codes.shape, np.uint32, c) if compact else None
-    try:
+    with contextlib.ExitStack() as stack:
+        out = stack.enter_context(result_raster(out, codes.shape, np.uint32, c))
+        # every cell may be an outlet: room for all, the first K come back
+        room = stack.enter_context(DeviceRaster.empty(codes.shape, np.uint32, c)) \
+            if compact else None
         c.check(c.lib.hdem_watershed_u8_dev(
             c.handle, codes.ptr, codes.shape[0], codes.shape[1],
             seeds.ptr if seeds is not None else None, WS_COMPACT if compact else 0, out.ptr,
             room.ptr if compact else None, ctypes.byref(st)))
         outlets = None
         if compact:
-            outlets = np.empty(st.basins, np.uint32)
-            c.check(c.lib.hdem_memcpy_d2h(c.handle, outlets.ctypes.data, room.ptr,
-                                          outlets.nbytes))
-    finally:
-        if room is not None:
-            room.free()
+            first = DeviceRaster.wrap(room.ptr, (st.basins,), np.uint32, c)
+            outlets = first.to_host(np.empty(st.basins, np.uint32))
     return out, outlets, st.as_dict()
 
 
@@ -689,20 +711,15 @@ def flowtrace_dev(codes, streams=None, threshold=None, dem=None, cellsize=1.0,
     kind, threshold, want = flowtrace_args(codes, streams, threshold, dem, cellsize, want)
     c = codes.ctx
     dtypes = dict(FT_OUTPUTS)
-    outs = {}
     st = FlowTraceStats()
-    try:
-        for name in want:
-            outs[name] = DeviceRaster.empty(codes.shape, dtypes[name], c)
+    with contextlib.ExitStack() as stack:
+        outs = {name: stack.enter_context(result_raster(None, codes.shape, dtypes[name], c))
+                for name in want}
         c.check(c.lib.hdem_flowtrace_u8_dev(
             c.handle, codes.ptr, codes.shape[0], codes.shape[1],
             streams.ptr if streams is not None else None, kind, threshold,
             dem.ptr if dem is not None else None, float(cellsize),
             *[outs[n].ptr if n in outs else None for n, _ in FT_OUTPUTS], 0, ctypes.byref(st)))
-    except Exception:
-        for r in outs.values():
-            r.free()
-        raise
     return outs, st.as_dict()
 
 
@@ -729,31 +746,25 @@ def resolve_flats_dev(codes, dem, want_distance=False, out=None):
     stats dict.  ``out`` may be ``codes`` itself.  Synchronises once per relaxation round."""
     resolve_flats_args(codes, dem)
     c = codes.ctx
-    mine = out is None
-    out = out or DeviceRaster.empty(codes.shape, np.uint8, c)
-    dist = None
     st = ResolveFlatsStats()
-    try:
-        if want_distance:
-            dist = DeviceRaster.empty(codes.shape, np.uint32, c)
+    with contextlib.ExitStack() as stack:
+        out = stack.enter_context(result_raster(out, codes.shape, np.uint8, c))
+        dist = stack.enter_context(result_raster(None, codes.shape, np.uint32, c)) \
+            if want_distance else None
         c.check(c.lib.hdem_resolve_flats_u8_dev(
             c.handle, codes.ptr, dem.ptr, codes.shape[0], codes.shape[1], out.ptr,
             dist.ptr if dist is not None else None, 0, ctypes.byref(st)))
-    except Exception:
-        for r in ([out] if mine else []) + ([dist] if dist is not None else []):
-            r.free()
-        raise
     return out, dist, st.as_dict()
 
 
 def sinkfill_dev(z, eps=0.0, max_rounds=0, out=None, flags=FILL_INIT):
     _need(z, np.float32)
-    out = out or DeviceRaster.empty(z.shape, np.float32, z.ctx)
     c = z.ctx
     st = FillStats()
-    c.check(c.lib.hdem_sinkfill_f32_dev(c.handle, z.ptr, z.shape[0], z.shape[1],
-                                        float(eps), int(max_rounds), int(flags),
-                                        out.ptr, ctypes.byref(st)))
+    with result_raster(out, z.shape, np.float32, c) as out:
+        c.check(c.lib.hdem_sinkfill_f32_dev(c.handle, z.ptr, z.shape[0], z.shape[1],
+                                            float(eps), int(max_rounds), int(flags),
+                                            out.ptr, ctypes.byref(st)))
     return out, st.as_dict()
 
 
@@ -761,10 +772,10 @@ def blockmax_dev(z, block, out=None):
     """Block-maximum coarsening (``hdem_blockmax_f32_dev``)."""
     _need(z, np.float32)
     shape = (-(-z.shape[0] // block), -(-z.shape[1] // block))
-    out = out or DeviceRaster.empty(shape, np.float32, z.ctx)
     c = z.ctx
-    c.check(c.lib.hdem_blockmax_f32_dev(c.handle, z.ptr, z.shape[0], z.shape[1], int(block),
-                                        out.ptr))
+    with result_raster(out, shape, np.float32, c) as out:
+        c.check(c.lib.hdem_blockmax_f32_dev(c.handle, z.ptr, z.shape[0], z.shape[1],
+                                            int(block), out.ptr))
     return out
 
 
@@ -851,16 +862,15 @@ def elementwise_dev(op, image, operand, out_dtype=None, out=None, operand_type=N
         # np.multiply(a, s, dtype=float64) would take the Python scalar unrounded
         narrow = work == np.float32 and np.dtype(out_dtype) != np.float64
         scalar = float(np.float32(operand)) if narrow else float(operand)
-    if out is None:
-        out = DeviceRaster.empty(image.shape, out_dtype, c)
-    elif out.shape != image.shape or out.dtype not in _EW_TYPES:
+    if out is not None and (out.shape != image.shape or out.dtype not in _EW_TYPES):
         raise ValueError(f"out is {out.dtype} {out.shape}, the image has shape {image.shape}")
     n = int(np.prod(image.shape))
-    c.check(c.lib.hdem_elementwise_dev(
-        c.handle, int(op), image.ptr, _EW_TYPES[image.dtype],
-        raster.ptr if raster is not None else None,
-        _EW_TYPES[raster.dtype] if raster is not None else 0,
-        scalar, n, out.ptr, _EW_TYPES[out.dtype]))
+    with result_raster(out, image.shape, out_dtype, c) as out:
+        c.check(c.lib.hdem_elementwise_dev(
+            c.handle, int(op), image.ptr, _EW_TYPES[image.dtype],
+            raster.ptr if raster is not None else None,
+            _EW_TYPES[raster.dtype] if raster is not None else 0,
+            scalar, n, out.ptr, _EW_TYPES[out.dtype]))
     return out
 
 
@@ -868,9 +878,8 @@ def copy_rate(ctx=None, nbytes=1 << 30, reps=5):
     """Measured device copy rate in GB/s (bytes moved through HBM = 2 x copied bytes per
     second): the achievable roof SURVEY 8d asks the kernels to be quoted against."""
     c = ctx or context()
-    src = DeviceRaster.empty((nbytes // 4096, 1024), np.float32, c)
-    dst = DeviceRaster.empty(src.shape, np.float32, c)
-    try:
+    with DeviceRaster.empty((nbytes // 4096, 1024), np.float32, c) as src, \
+            DeviceRaster.empty(src.shape, np.float32, c) as dst:
         c.check(c.lib.hdem_copy_rate_dev(c.handle, src.ptr, dst.ptr, src.nbytes))   # warm
         c.synchronize()
         was = c.profile_get(K_COPY)
@@ -880,9 +889,11 @@ def copy_rate(ctx=None, nbytes=1 << 30, reps=5):
         now = c.profile_get(K_COPY)
         ms = now["ms"] - was["ms"]
         return 2.0 * (now["units"] - was["units"]) / max(ms, 1e-9) / 1e6
-    finally:
-        src.free()
-        dst.free()
+
+
+def _destripe_quarter(shape):
+    """What the destripe's 55-cell window has to fit: a quadrant less its 10-cell margin."""
+    return tuple(max(n // 2 - 10, 0) for n in shape)
 
 
 def fourier_destripe_dev(dem, out=None, mask=None):
@@ -890,13 +901,13 @@ def fourier_destripe_dev(dem, out=None, mask=None):
     receives the reference's ``masks_fourier`` (shifted coordinates)."""
     _need(dem, np.float32)
     c = dem.ctx
-    out = out or DeviceRaster.empty(dem.shape, np.float32, c)
     if mask is not None:
         _need(mask, np.uint8)
-    quarter = (dem.shape[0] // 2 - 10, dem.shape[1] // 2 - 10)
-    c.check(c.lib.hdem_fourier_destripe_f32_dev(c.handle, dem.ptr, dem.shape[0], dem.shape[1],
-                                                out.ptr, mask.ptr if mask is not None else None),
-            window=55, shape=tuple(max(q, 0) for q in quarter))
+    with result_raster(out, dem.shape, np.float32, c) as out:
+        c.check(c.lib.hdem_fourier_destripe_f32_dev(
+            c.handle, dem.ptr, dem.shape[0], dem.shape[1], out.ptr,
+            mask.ptr if mask is not None else None),
+            window=55, shape=_destripe_quarter(dem.shape))
     return out
 
 
@@ -905,30 +916,30 @@ def blanks_fourier_dev(q, found=None, window_size=55):
     mean; ``q`` is rewritten with those cells zeroed."""
     _need(q, np.float32)
     c = q.ctx
-    found = found or DeviceRaster.empty(q.shape, np.uint8, c)
-    c.check(c.lib.hdem_blanks_fourier_f32_dev(c.handle, q.ptr, q.shape[0], q.shape[1],
-                                              int(window_size), found.ptr),
-            window=window_size, shape=q.shape)
+    with result_raster(found, q.shape, np.uint8, c) as found:
+        c.check(c.lib.hdem_blanks_fourier_f32_dev(c.handle, q.ptr, q.shape[0], q.shape[1],
+                                                  int(window_size), found.ptr),
+                window=window_size, shape=q.shape)
     return found
 
 
 def isolated_points_dev(mask, window_size=3, out=None):
     _need(mask, np.uint8)
     c = mask.ctx
-    out = out or DeviceRaster.empty(mask.shape, np.uint8, c)
-    c.check(c.lib.hdem_isolated_points_u8_dev(c.handle, mask.ptr, mask.shape[0], mask.shape[1],
-                                              int(window_size), out.ptr),
-            window=window_size, shape=mask.shape)
+    with result_raster(out, mask.shape, np.uint8, c) as out:
+        c.check(c.lib.hdem_isolated_points_u8_dev(c.handle, mask.ptr, mask.shape[0],
+                                                  mask.shape[1], int(window_size), out.ptr),
+                window=window_size, shape=mask.shape)
     return out
 
 
 def expand_dev(mask, window_size=13, out=None):
     _need(mask, np.uint8)
     c = mask.ctx
-    out = out or DeviceRaster.empty(mask.shape, np.uint8, c)
-    c.check(c.lib.hdem_expand_u8_dev(c.handle, mask.ptr, mask.shape[0], mask.shape[1],
-                                     int(window_size), out.ptr),
-            window=window_size, shape=mask.shape)
+    with result_raster(out, mask.shape, np.uint8, c) as out:
+        c.check(c.lib.hdem_expand_u8_dev(c.handle, mask.ptr, mask.shape[0], mask.shape[1],
+                                         int(window_size), out.ptr),
+                window=window_size, shape=mask.shape)
     return out
 
 
@@ -952,31 +963,42 @@ def widened_to_host(raster, dtype):
     dtype = np.dtype(dtype)
     if raster.dtype == dtype:
         return raster.to_host()
-    wide = elementwise_dev(EW_MUL, raster, 1.0, out_dtype=dtype)
-    try:
+    with elementwise_dev(EW_MUL, raster, 1.0, out_dtype=dtype) as wide:
         return wide.to_host()
-    finally:
-        wide.free()
 
 
 def correct_nan_dev(dem, out=None, window_size=3):
     _need(dem, np.float32)
     c = dem.ctx
-    out = out or DeviceRaster.empty(dem.shape, np.float32, c)
-    c.check(c.lib.hdem_correct_nan_f32_dev(c.handle, dem.ptr, dem.shape[0], dem.shape[1],
-                                           int(window_size), out.ptr),
-            window=window_size, shape=dem.shape)
+    with result_raster(out, dem.shape, np.float32, c) as out:
+        c.check(c.lib.hdem_correct_nan_f32_dev(c.handle, dem.ptr, dem.shape[0], dem.shape[1],
+                                               int(window_size), out.ptr),
+                window=window_size, shape=dem.shape)
     return out
 
 
 def majority_dev(img, window_size=11, out=None):
     _need(img, np.float32)
     c = img.ctx
-    out = out or DeviceRaster.empty(img.shape, np.float32, c)
-    c.check(c.lib.hdem_majority_f32_dev(c.handle, img.ptr, img.shape[0], img.shape[1],
-                                        int(window_size), out.ptr),
-            window=window_size, shape=img.shape)
+    with result_raster(out, img.shape, np.float32, c) as out:
+        c.check(c.lib.hdem_majority_f32_dev(c.handle, img.ptr, img.shape[0], img.shape[1],
+                                            int(window_size), out.ptr),
+                window=window_size, shape=img.shape)
     return out
+
+
+@contextlib.contextmanager
+def _scratch(shape, dtype, ctx, wanted=True):
+    """A scratch raster for the length of a call (``None`` when not ``wanted``).  ``hdem_free``
+    is stream-ordered now: dropping the synchronize in front of it is a speed change of its own."""
+    if not wanted:
+        yield None
+        return
+    with DeviceRaster.empty(shape, dtype, ctx) as raster:
+        try:
+            yield raster
+        finally:
+            ctx.synchronize()
 
 
 def _structure_arg(structure):
@@ -991,34 +1013,23 @@ def _structure_arg(structure):
 def binary_erosion_dev(mask, iterations=1, structure=None, out=None):
     _need(mask, np.uint8)
     c = mask.ctx
-    out = out or DeviceRaster.empty(mask.shape, np.uint8, c)
-    tmp = DeviceRaster.empty(mask.shape, np.uint8, c) if iterations > 1 else None
-    ptr, sh, sw, keep = _structure_arg(structure)
-    try:
+    ptr, sh, sw, _alive = _structure_arg(structure)
+    with result_raster(out, mask.shape, np.uint8, c) as out, \
+            _scratch(mask.shape, np.uint8, c, iterations > 1) as tmp:
         c.check(c.lib.hdem_binary_erosion_u8_dev(c.handle, mask.ptr, mask.shape[0],
                                                  mask.shape[1], ptr, sh, sw, int(iterations),
                                                  tmp.ptr if tmp else None, out.ptr))
-    finally:
-        if tmp is not None:
-            c.synchronize()
-            tmp.free()
-    del keep
     return out
 
 
 def binary_closing_dev(mask, structure=None, out=None):
     _need(mask, np.uint8)
     c = mask.ctx
-    out = out or DeviceRaster.empty(mask.shape, np.uint8, c)
-    tmp = DeviceRaster.empty(mask.shape, np.uint8, c)
-    ptr, sh, sw, keep = _structure_arg(structure)
-    try:
+    ptr, sh, sw, _alive = _structure_arg(structure)
+    with result_raster(out, mask.shape, np.uint8, c) as out, \
+            _scratch(mask.shape, np.uint8, c) as tmp:
         c.check(c.lib.hdem_binary_closing_u8_dev(c.handle, mask.ptr, mask.shape[0],
                                                  mask.shape[1], ptr, sh, sw, tmp.ptr, out.ptr))
-    finally:
-        c.synchronize()
-        tmp.free()
-    del keep
     return out
 
 
@@ -1030,18 +1041,19 @@ def grey_dilation_dev(img, size, out=None):
     else:
         _need(img, np.float32)
         fn = c.lib.hdem_grey_dilation_f32_dev
-    out = out or DeviceRaster.empty(img.shape, img.dtype, c)
     sy, sx = (size, size) if np.isscalar(size) else size
-    c.check(fn(c.handle, img.ptr, img.shape[0], img.shape[1], int(sy), int(sx), out.ptr))
+    with result_raster(out, img.shape, img.dtype, c) as out:
+        c.check(fn(c.handle, img.ptr, img.shape[0], img.shape[1], int(sy), int(sx), out.ptr))
     return out
 
 
 def tidying_lagoons_dev(img, out=None):
     _need(img, np.float32)
     c = img.ctx
-    out = out or DeviceRaster.empty(img.shape, np.float32, c)
-    c.check(c.lib.hdem_tidying_lagoons_f32_dev(c.handle, img.ptr, img.shape[0], img.shape[1],
-                                               out.ptr), window=7, shape=img.shape)
+    with result_raster(out, img.shape, np.float32, c) as out:
+        c.check(c.lib.hdem_tidying_lagoons_f32_dev(c.handle, img.ptr, img.shape[0],
+                                                   img.shape[1], out.ptr),
+                window=7, shape=img.shape)
     return out
 
 
@@ -1049,12 +1061,12 @@ def lagoons_detection_dev(hsheds):
     """(mask uint8, hsheds_nan_fixed, lagoons_values) device rasters."""
     _need(hsheds, np.float32)
     c = hsheds.ctx
-    fixed = DeviceRaster.empty(hsheds.shape, np.float32, c)
-    values = DeviceRaster.empty(hsheds.shape, np.float32, c)
-    mask = DeviceRaster.empty(hsheds.shape, np.uint8, c)
-    c.check(c.lib.hdem_lagoons_detection_f32_dev(c.handle, hsheds.ptr, hsheds.shape[0],
-                                                 hsheds.shape[1], fixed.ptr, values.ptr,
-                                                 mask.ptr), window=11, shape=hsheds.shape)
+    with result_raster(None, hsheds.shape, np.float32, c) as fixed, \
+            result_raster(None, hsheds.shape, np.float32, c) as values, \
+            result_raster(None, hsheds.shape, np.uint8, c) as mask:
+        c.check(c.lib.hdem_lagoons_detection_f32_dev(c.handle, hsheds.ptr, hsheds.shape[0],
+                                                     hsheds.shape[1], fixed.ptr, values.ptr,
+                                                     mask.ptr), window=11, shape=hsheds.shape)
     return mask, fixed, values
 
 
@@ -1063,33 +1075,33 @@ def sinkfill_d8_dev(z, eps=0.0, max_rounds=0, out=None, codes=None, flags=FILL_I
     Returns (filled raster, D8 raster, stats)."""
     _need(z, np.float32)
     c = z.ctx
-    out = out or DeviceRaster.empty(z.shape, np.float32, c)
-    codes = codes or DeviceRaster.empty(z.shape, np.uint8, c)
     st = FillStats()
-    c.check(c.lib.hdem_sinkfill_d8_f32_dev(c.handle, z.ptr, z.shape[0], z.shape[1], float(eps),
-                                           int(max_rounds), int(flags), out.ptr, codes.ptr,
-                                           ctypes.byref(st)))
+    with result_raster(out, z.shape, np.float32, c) as out, \
+            result_raster(codes, z.shape, np.uint8, c) as codes:
+        c.check(c.lib.hdem_sinkfill_d8_f32_dev(c.handle, z.ptr, z.shape[0], z.shape[1],
+                                               float(eps), int(max_rounds), int(flags),
+                                               out.ptr, codes.ptr, ctypes.byref(st)))
     return out, codes, st.as_dict()
 
 
 def boxmean3_dev(x, do_round=True, out=None):
-    out = out or DeviceRaster.empty(x.shape, x.dtype, x.ctx)
     c = x.ctx
     fn = (c.lib.hdem_boxmean3_f32_dev if x.dtype == np.float32
           else c.lib.hdem_boxmean3_f64_dev)
     if x.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
         raise ValueError(f"box mean needs a float raster, got {x.dtype}")
-    c.check(fn(c.handle, x.ptr, x.shape[0], x.shape[1], int(bool(do_round)), out.ptr))
+    with result_raster(out, x.shape, x.dtype, c) as out:
+        c.check(fn(c.handle, x.ptr, x.shape[0], x.shape[1], int(bool(do_round)), out.ptr))
     return out
 
 
 def quadratic_dev(dem, window_size=15, out=None):
     _need(dem, np.float32)
-    out = out or DeviceRaster.empty(dem.shape, np.float32, dem.ctx)
     c = dem.ctx
-    c.check(c.lib.hdem_quadratic_f32_dev(c.handle, dem.ptr, dem.shape[0],
-                                         dem.shape[1], int(window_size), out.ptr),
-            window=window_size, shape=dem.shape)
+    with result_raster(out, dem.shape, np.float32, c) as out:
+        c.check(c.lib.hdem_quadratic_f32_dev(c.handle, dem.ptr, dem.shape[0],
+                                             dem.shape[1], int(window_size), out.ptr),
+                window=window_size, shape=dem.shape)
     return out
 
 
@@ -1100,26 +1112,16 @@ def groves_dev(img, groves, window_size=15, threshold=1.5, iterations=3, out=Non
     _need(img, np.float32)
     _need(groves, np.uint8)
     c = img.ctx
-    out = out or DeviceRaster.empty(img.shape, np.float32, c)
     if scratch is not None:
         _need(scratch, np.float32)
-        c.check(c.lib.hdem_groves_f32_dev(c.handle, img.ptr, groves.ptr, img.shape[0],
-                                          img.shape[1], int(window_size),
-                                          float(threshold), int(iterations),
-                                          scratch.ptr, out.ptr),
-                window=window_size, shape=img.shape)
-        return out
-    scratch = DeviceRaster.empty(img.shape, np.float32, c) if iterations > 1 else None
-    try:
+    with result_raster(out, img.shape, np.float32, c) as out, \
+            _scratch(img.shape, np.float32, c, scratch is None and iterations > 1) as mine:
+        scratch = scratch or mine
         c.check(c.lib.hdem_groves_f32_dev(c.handle, img.ptr, groves.ptr, img.shape[0],
                                           img.shape[1], int(window_size),
                                           float(threshold), int(iterations),
                                           scratch.ptr if scratch else None, out.ptr),
                 window=window_size, shape=img.shape)
-    finally:
-        if scratch is not None:
-            c.synchronize()
-            scratch.free()
     return out
 
 
@@ -1301,34 +1303,33 @@ def fourier_destripe(dem, return_mask=False):
     dem = _host2d(dem, np.float32)
     out = host_empty(dem.shape, dem.dtype)
     mask = host_empty(dem.shape, np.uint8) if return_mask else None
-    quarter = (dem.shape[0] // 2 - 10, dem.shape[1] // 2 - 10)
     c.check(c.lib.hdem_fourier_destripe_f32(c.handle, dem.ctypes.data, dem.shape[0],
                                             dem.shape[1], out.ctypes.data,
                                             mask.ctypes.data if return_mask else None),
-            window=55, shape=tuple(max(q, 0) for q in quarter))
+            window=55, shape=_destripe_quarter(dem.shape))
     return (out, mask) if return_mask else out
 
 
 def blanks_fourier(q, window_size=55):
     """(found float64 0/1, q * (1 - found)) like BlanksFourier.apply."""
-    qd = DeviceRaster.from_host(_host2d(q, np.float32))
-    found = blanks_fourier_dev(qd, window_size=window_size)
-    return widened_to_host(found, np.float64), qd.to_host()
+    with DeviceRaster.from_host(_host2d(q, np.float32)) as qd, \
+            blanks_fourier_dev(qd, window_size=window_size) as found:
+        return widened_to_host(found, np.float64), qd.to_host()
 
 
 def isolated_points(mask, window_size=3):
-    m = DeviceRaster.from_host(_host2d(mask, np.uint8))
-    return isolated_points_dev(m, window_size).to_host()
+    with DeviceRaster.from_host(_host2d(mask, np.uint8)) as m, \
+            isolated_points_dev(m, window_size) as out:
+        return out.to_host()
 
 
 def expand(mask, window_size=13, dtype=np.uint8):
     """ExpandFilter on a host raster (cells > 0 are set); the 0 / 1 result in ``dtype``."""
     g = np.asarray(mask)
-    if g.dtype in (np.uint8, np.bool_):
-        m = DeviceRaster.from_host(_host2d(g, g.dtype).view(np.uint8))
-    else:
-        m = DeviceRaster.from_host(_host2d(np.greater(g, 0), np.bool_).view(np.uint8))
-    return widened_to_host(expand_dev(m, window_size), dtype)
+    set_ = _host2d(g, g.dtype) if g.dtype in (np.uint8, np.bool_) else \
+        _host2d(np.greater(g, 0), np.bool_)
+    with DeviceRaster.from_host(set_.view(np.uint8)) as m, expand_dev(m, window_size) as out:
+        return widened_to_host(out, dtype)
 
 
 def fft2(x, inverse=False):
@@ -1336,7 +1337,8 @@ def fft2(x, inverse=False):
     complex128 for anything else -- scipy.fftpack's rule (extension_filters.py:379,414)."""
     single = np.asarray(x).dtype in (np.dtype(np.float32), np.dtype(np.complex64))
     a = _host2d(x, np.complex64 if single else np.complex128)
-    d = fft2_dev(DeviceRaster.from_host(a), inverse).to_host()
+    with DeviceRaster.from_host(a) as data:
+        d = fft2_dev(data, inverse).to_host()
     if not inverse:
         return d
     return d / (np.float32(a.size) if single else np.float64(a.size))

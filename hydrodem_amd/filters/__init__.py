@@ -22,6 +22,7 @@ float64) and the filters that write into their input (``CorrectNANValues``,
 elevations keep the type they were uploaded with.
 """
 
+import contextlib
 from abc import ABC, abstractmethod
 
 from numpy import ndarray
@@ -127,11 +128,15 @@ class ComposedFilter(Filter):  # pylint: disable=too-few-public-methods
         """Chain on a device-resident raster; the caller keeps ownership of
         ``raster`` and receives a new one."""
         stage = raster
-        for member in self.filters:
-            following = member.apply_device(stage)
-            if stage is not raster and stage is not following:
-                stage.free()        # intermediate of this chain
-            stage = following
+        with contextlib.ExitStack() as intermediate:    # holds the stage this chain made
+            for member in self.filters:
+                following = member.apply_device(stage)
+                if following is not stage:
+                    intermediate.close()                # frees the stage before
+                    if following is not raster:
+                        intermediate.enter_context(following)
+                    stage = following
+            intermediate.pop_all()                      # the last stage is the caller's
         return stage
 
 
@@ -160,8 +165,11 @@ class ComposedFilterResults(Filter):  # pylint: disable=too-few-public-methods
         ``results``."""
         lazy = LazyResults()
         stage = raster
-        for member in self.filters:
-            stage = member.apply_device(stage)
-            lazy.device[type(member).__name__] = stage
+        with contextlib.ExitStack() as collected:       # released if a member raises
+            collected.callback(lazy.release, keep=raster)
+            for member in self.filters:
+                stage = member.apply_device(stage)
+                lazy.device[type(member).__name__] = stage
+            collected.pop_all()                         # the stages are the results' now
         self.results = lazy
         return stage

@@ -40,6 +40,7 @@ every reference stencil re-reads its input through ``astype('float32')``
 anyway (`sliding_window.py:132`).
 """
 
+import contextlib
 import copy
 from collections import Counter  # noqa: F401  (name of the reference module's namespace)
 
@@ -688,16 +689,17 @@ class HydroConditioning(ComposedFilter):  # pylint: disable=too-few-public-metho
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
         fill = self.filters[0]
-        with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z:
+        with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z, \
+                contextlib.ExitStack() as stack:
             # one call: the certifying pass of the fill writes the flow directions
             filled, codes, fill.stats = backend.sinkfill_d8_dev(
                 z, eps=fill.epsilon, max_rounds=fill.max_rounds)
-            with filled, codes:
-                if self.flats == "resolve":
-                    _, _, self.resolve_stats = backend.resolve_flats_dev(codes, filled,
-                                                                         out=codes)
-                self.filled = filled.to_host()
-                return codes.to_host()
+            stack.enter_context(filled)
+            stack.enter_context(codes)
+            if self.flats == "resolve":
+                _, _, self.resolve_stats = backend.resolve_flats_dev(codes, filled, out=codes)
+            self.filled = filled.to_host()
+            return codes.to_host()
 
     def apply_batch(self, rasters):
         """Fill + D8 of several rasters in ONE pass of the solver: ``[(filled, codes), ...]``.
@@ -799,29 +801,31 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
         _check_raster("DemToHAND", image_to_filter, np.float32, "a float32 DEM")
-        with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z:
-            with self.apply_device(z) as hand:
-                out = hand.to_host()
-        if self.keep_partial_results:
-            for name in ("filled", "codes", "accumulation", "distance"):
-                with getattr(self, name) as raster:
-                    setattr(self, name, raster.to_host())
+        with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z, \
+                contextlib.ExitStack() as stack:
+            hand = stack.enter_context(self.apply_device(z))
+            names = ("filled", "codes", "accumulation", "distance") \
+                if self.keep_partial_results else ()
+            kept = [stack.enter_context(getattr(self, name)) for name in names]
+            out = hand.to_host()
+            for name, raster in zip(names, kept):
+                setattr(self, name, raster.to_host())
         return out
 
     def apply_device(self, raster):
         _check_raster("DemToHAND", raster, np.float32, "a float32 DEM")
         fill, _, accumulate = self.filters
         self.filled = self.codes = self.accumulation = self.distance = None
-        kept = []
-        filled, codes, fill.stats = backend.sinkfill_d8_dev(
-            raster, eps=fill.epsilon, max_rounds=fill.max_rounds)
-        kept += [filled, codes]
-        try:
+        with contextlib.ExitStack() as stack:
+            filled, codes, fill.stats = backend.sinkfill_d8_dev(
+                raster, eps=fill.epsilon, max_rounds=fill.max_rounds)
+            stack.enter_context(filled)
+            stack.enter_context(codes)
             resolve_stats = None
             if self.flats == "resolve":
                 _, _, resolve_stats = backend.resolve_flats_dev(codes, filled, out=codes)
             acc, accumulate.stats = backend.flowacc_dev(codes)
-            kept.append(acc)
+            stack.enter_context(acc)
             trace = HeightAboveDrainage(dem=filled, streams=acc, threshold=self.threshold,
                                         cellsize=self.cellsize,
                                         keep_partial_results=self.keep_partial_results)
@@ -832,13 +836,10 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
                 self.stats["ResolveFlats"] = resolve_stats
             if self.keep_partial_results:
                 trace.drainage.free()
-                self.filled, self.codes, self.accumulation = kept
+                self.filled, self.codes, self.accumulation = filled, codes, acc
                 self.distance = trace.distance
-                kept = []
+                stack.pop_all()                     # the caller's to free from here on
             return hand
-        finally:
-            for r in kept:
-                r.free()
 
 
 # ---------------------------------------------------------------------------
@@ -991,6 +992,22 @@ class DetectApplyFourier(ComposedFilter):  # pylint: disable=too-few-public-meth
 # ---------------------------------------------------------------------------
 # HydroSHEDS / lagoon branch
 # ---------------------------------------------------------------------------
+def _write_back_repaired(image, uploaded, fixed, window_size):
+    """``CorrectNANValues`` works in place: ``fixed``, the repair of ``uploaded`` (``image`` as
+    contiguous float32), goes back into ``image``.  The kernel passes every other cell through
+    bit for bit, so an ``image`` that went up as it is receives the repaired raster whole; any
+    other only its repaired cells, the voids inside the ring of ``window_size // 2`` cells
+    (its other values need not be float32 numbers)."""
+    if uploaded is image:
+        fixed.to_host(out=image)
+        return
+    r = int(window_size) // 2
+    sel = uploaded < 0
+    sel[:r] = sel[uploaded.shape[0] - r:] = False
+    sel[:, :r] = sel[:, uploaded.shape[1] - r:] = False
+    np.copyto(image, fixed.to_host(), where=sel, casting="unsafe")
+
+
 class MajorityFilter(Filter):  # pylint: disable=too-few-public-methods
     """The value that fills more than 70 % of ``window_size**2 - 1`` cells of the
     circular window (square minus corners, the centre counts), else 0; the ring
@@ -1000,9 +1017,9 @@ class MajorityFilter(Filter):  # pylint: disable=too-few-public-methods
         self.window_size = window_size
 
     def apply(self, image_to_filter):
-        img = backend.DeviceRaster.from_host(
-            np.ascontiguousarray(image_to_filter, dtype=np.float32))
-        return backend.widened_to_host(backend.majority_dev(img, self.window_size), np.float64)
+        with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as img, \
+                backend.majority_dev(img, self.window_size) as out:
+            return backend.widened_to_host(out, np.float64)
 
     def apply_device(self, raster):
         return backend.majority_dev(raster, self.window_size)
@@ -1017,21 +1034,11 @@ class CorrectNANValues(Filter):  # pylint: disable=too-few-public-methods
         self.window_size = window_size
 
     def apply(self, image_to_filter):
-        dem = image_to_filter
-        g = np.ascontiguousarray(dem, dtype=np.float32)
-        fixed = backend.correct_nan_dev(backend.DeviceRaster.from_host(g),
-                                        window_size=self.window_size)
-        if g is dem:
-            # (every cell that is not repaired comes back bit for bit)
-            fixed.ctx.check(fixed.ctx.lib.hdem_memcpy_d2h(fixed.ctx.handle, g.ctypes.data,
-                                                          fixed.ptr, g.nbytes))
-            return dem
-        r = int(self.window_size) // 2
-        sel = g < 0
-        sel[:r] = sel[g.shape[0] - r:] = False
-        sel[:, :r] = sel[:, g.shape[1] - r:] = False
-        np.copyto(dem, fixed.to_host(), where=sel, casting="unsafe")
-        return dem
+        g = np.ascontiguousarray(image_to_filter, dtype=np.float32)
+        with backend.DeviceRaster.from_host(g) as dem, \
+                backend.correct_nan_dev(dem, window_size=self.window_size) as fixed:
+            _write_back_repaired(image_to_filter, g, fixed, self.window_size)
+        return image_to_filter
 
     def apply_device(self, raster):
         return backend.correct_nan_dev(raster, window_size=self.window_size)
@@ -1072,9 +1079,9 @@ class TidyingLagoons(ComposedFilter):  # pylint: disable=too-few-public-methods
         Filter.apply(self, image_to_filter)
         self.filters[2].factor = content = image_to_filter
         if self._stock():
-            img = backend.DeviceRaster.from_host(
-                np.ascontiguousarray(image_to_filter, dtype=np.float32))
-            return backend.widened_to_host(backend.tidying_lagoons_dev(img), np.float64)
+            with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as img, \
+                    backend.tidying_lagoons_dev(img) as out:
+                return backend.widened_to_host(out, np.float64)
         for filter_ in self.filters:
             content = filter_.apply(content)
         return content
@@ -1100,21 +1107,12 @@ class LagoonsDetection(ComposedFilterResults):  # pylint: disable=too-few-public
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
         g = np.ascontiguousarray(image_to_filter, dtype=np.float32)
-        mask, fixed, values = backend.lagoons_detection_dev(backend.DeviceRaster.from_host(g))
-        # CorrectNANValues works in place.  The kernel passes every other cell through bit for
-        # bit, so a float32 raster simply receives the repaired one; any other type only its
-        # repaired cells (its other values need not be float32 numbers).
-        if g is image_to_filter:
-            fixed.ctx.check(fixed.ctx.lib.hdem_memcpy_d2h(fixed.ctx.handle, g.ctypes.data,
-                                                          fixed.ptr, g.nbytes))
-        else:
-            sel = g < 0
-            sel[0] = sel[-1] = False
-            sel[:, 0] = sel[:, -1] = False
-            np.copyto(image_to_filter, fixed.to_host(), where=sel, casting="unsafe")
-        self.hsheds_nan_fixed = image_to_filter
-        self.lagoons_values = backend.widened_to_host(values, np.float64)
-        self.mask_lagoons = backend.widened_to_host(mask, np.int64)
+        with backend.DeviceRaster.from_host(g) as hsheds, contextlib.ExitStack() as stack:
+            mask, fixed, values = map(stack.enter_context, backend.lagoons_detection_dev(hsheds))
+            _write_back_repaired(image_to_filter, g, fixed, 3)
+            self.hsheds_nan_fixed = image_to_filter
+            self.lagoons_values = backend.widened_to_host(values, np.float64)
+            self.mask_lagoons = backend.widened_to_host(mask, np.int64)
         self.results = {"CorrectNANValues": self.hsheds_nan_fixed,
                         "TidyingLagoons": self.lagoons_values,
                         "MaskPositives": self.mask_lagoons}

@@ -19,7 +19,6 @@ structures / sizes) and ``BitwiseXOR`` :12-60.
 
 import copy
 
-
 import numpy as np
 
 from . import Filter
@@ -120,10 +119,6 @@ class BitwiseXOR(Filter):  # pylint: disable=too-few-public-methods
         return np.bitwise_xor(self.operand, image_to_filter)
 
 
-def _mask_raster(image):
-    return backend.DeviceRaster.from_host(backend.mask_bytes(image))
-
-
 class BinaryErosion(Filter):  # pylint: disable=too-few-public-methods
     """``scipy.ndimage.binary_erosion(image, iterations=...)`` -> bool grid
     (extension_filters.py:187-235)."""
@@ -133,8 +128,9 @@ class BinaryErosion(Filter):  # pylint: disable=too-few-public-methods
 
     def apply(self, image_to_filter):
         super().apply(image_to_filter)
-        out = backend.binary_erosion_dev(_mask_raster(image_to_filter), self.iterations)
-        return out.to_host().view(np.bool_)                   # (the kernels write 0 / 1)
+        with backend.DeviceRaster.from_host(backend.mask_bytes(image_to_filter)) as mask, \
+                backend.binary_erosion_dev(mask, self.iterations) as out:
+            return out.to_host().view(np.bool_)               # (the kernels write 0 / 1)
 
 
 class BinaryClosing(Filter):  # pylint: disable=too-few-public-methods
@@ -146,8 +142,9 @@ class BinaryClosing(Filter):  # pylint: disable=too-few-public-methods
 
     def apply(self, image_to_filter):
         super().apply(image_to_filter)
-        out = backend.binary_closing_dev(_mask_raster(image_to_filter), self.structure)
-        return out.to_host().view(np.bool_)
+        with backend.DeviceRaster.from_host(backend.mask_bytes(image_to_filter)) as mask, \
+                backend.binary_closing_dev(mask, self.structure) as out:
+            return out.to_host().view(np.bool_)
 
 
 class GreyDilation(Filter):  # pylint: disable=too-few-public-methods
@@ -163,7 +160,6 @@ class GreyDilation(Filter):  # pylint: disable=too-few-public-methods
         super().apply(image_to_filter)
         src = np.asarray(image_to_filter)
         work = np.float32 if src.dtype == np.float32 else np.float64
-        img = backend.DeviceRaster.from_host(np.ascontiguousarray(src, dtype=work))
-        out = backend.grey_dilation_dev(img, self.size).to_host()
-        img.free()
-        return out.astype(src.dtype, copy=False)
+        with backend.DeviceRaster.from_host(np.ascontiguousarray(src, dtype=work)) as img, \
+                backend.grey_dilation_dev(img, self.size) as out:
+            return out.to_host().astype(src.dtype, copy=False)
