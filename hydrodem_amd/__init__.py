@@ -23,6 +23,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      PostProcessingFinal, SinkFill,
                                      D8FlowDirection, FlowAccumulation, Watersheds,
                                      FlowDistance, HeightAboveDrainage, ResolveFlats,
+                                     Depressions, DepressionInventory,
                                      HydroConditioning, DemToHAND,
                                      ExpandFilter, IsolatedPoints, BlanksFourier,
                                      DetectBlanksFourier, MaskFourier, FourierInitial,

@@ -117,6 +117,26 @@ class ResolveFlatsStats(_SizedStats):
                 ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class DepressionsStats(_SizedStats):
+    """``hdem_depressions_stats``."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_int32),
+                ("depressions", ctypes.c_int64), ("raised_cells", ctypes.c_int64),
+                ("tile_components", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_tile", ctypes.c_float), ("ms_seam", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("reserved2", ctypes.c_int32)]
+
+    def as_dict(self):
+        fields = super().as_dict()
+        del fields["reserved2"]
+        return fields
+
+
+DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
+# columns of the depression table, in the order of the C ABI's pointers
+DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
+                ("max_depth", np.float32), ("volume_q20", np.uint64))
+
 # HDEM_FT_STREAMS_*
 FT_STREAMS_NONE, FT_STREAMS_MASK_U8, FT_STREAMS_ACC_U32 = 0, 1, 2
 # outputs of the flow trace, in the order of the C ABI's pointers
@@ -203,6 +223,13 @@ SIGNATURES = {
                               _c.POINTER(ResolveFlatsStats)],
     "hdem_resolve_flats_u8_dev": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i,
                                   _c.POINTER(ResolveFlatsStats)],
+    "hdem_depressions_f32": [_vp, _vp, _vp, _i, _i, _i, _vp, _c.POINTER(DepressionsStats)],
+    "hdem_depressions_f32_dev": [_vp, _vp, _vp, _i, _i, _i, _vp,
+                                 _c.POINTER(DepressionsStats)],
+    "hdem_depression_table_f32": [_vp, _vp, _vp, _vp, _i, _i, _c.c_int64,
+                                  _vp, _vp, _vp, _vp, _vp],
+    "hdem_depression_table_f32_dev": [_vp, _vp, _vp, _vp, _i, _i, _c.c_int64,
+                                      _vp, _vp, _vp, _vp, _vp],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 
@@ -757,6 +784,82 @@ def resolve_flats_dev(codes, dem, want_distance=False, out=None):
     return out, dist, st.as_dict()
 
 
+def depressions_args(dem, filled, labels=None):
+    """The checks of the depression operators that need no device: ``dem``, ``filled`` and
+    ``labels`` are anything with ``dtype`` and ``shape`` (NumPy arrays or device rasters)."""
+    if np.dtype(filled.dtype) != np.float32:
+        raise ValueError(f"the filled raster is float32, got {filled.dtype}")
+    shape = tuple(filled.shape)
+    if len(shape) != 2:
+        raise ValueError(f"depressions take a 2-D raster, got {len(shape)} dimensions")
+    if dem is None:
+        raise ValueError("depressions need the dem the filled raster is compared with")
+    if np.dtype(dem.dtype) != np.float32:
+        raise ValueError(f"the dem is float32, got {dem.dtype}")
+    if tuple(dem.shape) != shape:
+        raise ValueError(f"the dem is {tuple(dem.shape)}, the filled raster {shape}")
+    if labels is not None:
+        if np.dtype(labels.dtype) != np.uint32:
+            raise ValueError(f"the labels are uint32, got {labels.dtype}")
+        if tuple(labels.shape) != shape:
+            raise ValueError(f"the labels are {tuple(labels.shape)}, the filled raster {shape}")
+
+
+def _depression_count(count):
+    if isinstance(count, bool) or int(count) != count or int(count) < 0:
+        raise ValueError(f"count is the number of depressions, got {count!r}")
+    return int(count)
+
+
+def depression_table_of(columns, cellsize=1.0):
+    """The table as the operators hand it out: the five columns of the C ABI and ``volume``,
+    float64, ``volume_q20 / 2**20 * cellsize**2``."""
+    table = dict(columns)
+    table["volume"] = table["volume_q20"].astype(np.float64) / 2.0 ** 20 * float(cellsize) ** 2
+    return table
+
+
+def depressions_dev(dem, filled, compact=True, out=None):
+    """Depression labels of a ``dem`` / ``filled`` pair of float32 rasters
+    (``hdem_depressions_f32_dev``): a uint32 raster and the stats dict, whose ``depressions``
+    is K.  ``compact``: labels 1 ... K in scan order of the first cell (the numbering of
+    ``scipy.ndimage.label``), else 1 + the flat index of the first cell.  Synchronises (the
+    call reads K and its validity counters)."""
+    depressions_args(dem, filled)
+    c = filled.ctx
+    st = DepressionsStats()
+    with result_raster(out, filled.shape, np.uint32, c) as out:
+        c.check(c.lib.hdem_depressions_f32_dev(
+            c.handle, dem.ptr, filled.ptr, filled.shape[0], filled.shape[1],
+            DEPR_COMPACT if compact else 0, out.ptr, ctypes.byref(st)))
+    return out, st.as_dict()
+
+
+def depression_table_dev(dem, filled, labels, count, cellsize=1.0):
+    """One row per compact label of ``labels`` (``hdem_depression_table_f32_dev``; ``count``
+    is K of the labelling): a dict of host arrays of length K, ``first``, ``area``, ``level``,
+    ``max_depth``, ``volume_q20`` and ``volume``.  The columns are gathered in one device block
+    that is downloaded and freed here; ``count == 0`` allocates and launches nothing."""
+    depressions_args(dem, filled, labels)
+    count = _depression_count(count)
+    c = filled.ctx
+    # one block: the uint64 column first, then the four 4-byte columns
+    order = sorted(DEPR_COLUMNS, key=lambda col: -np.dtype(col[1]).itemsize)
+    host = np.empty(sum(np.dtype(t).itemsize for _, t in order) * count, np.uint8)
+    columns, at = {}, 0
+    for name, dtype in order:
+        n = np.dtype(dtype).itemsize * count
+        columns[name] = (at, host[at:at + n].view(dtype))
+        at += n
+    if count:
+        with DeviceRaster.empty(host.shape, np.uint8, c) as block:
+            c.check(c.lib.hdem_depression_table_f32_dev(
+                c.handle, dem.ptr, filled.ptr, labels.ptr, filled.shape[0], filled.shape[1],
+                count, *[block.ptr + columns[name][0] for name, _ in DEPR_COLUMNS]))
+            block.to_host(host)
+    return depression_table_of({name: columns[name][1] for name, _ in DEPR_COLUMNS}, cellsize)
+
+
 def sinkfill_dev(z, eps=0.0, max_rounds=0, out=None, flags=FILL_INIT):
     _need(z, np.float32)
     c = z.ctx
@@ -1230,6 +1333,42 @@ def resolve_flats(codes, dem, want_distance=False):
         c.handle, codes.ctypes.data, dem.ctypes.data, codes.shape[0], codes.shape[1],
         out.ctypes.data, dist.ctypes.data if want_distance else None, 0, ctypes.byref(st)))
     return out, dist, st.as_dict()
+
+
+def depressions(dem, filled, compact=True):
+    """Depression labels of host arrays (``hdem_depressions_f32``; see
+    :func:`depressions_dev`): the uint32 labels and the stats dict."""
+    for name, a in (("dem", dem), ("filled", filled)):
+        if not isinstance(a, np.ndarray):
+            raise ValueError(f"{name} is a NumPy array, got {type(a)}")
+    depressions_args(dem, filled)
+    dem, filled = np.ascontiguousarray(dem), np.ascontiguousarray(filled)
+    c = context()
+    out = host_empty(filled.shape, np.uint32)
+    st = DepressionsStats()
+    c.check(c.lib.hdem_depressions_f32(
+        c.handle, dem.ctypes.data, filled.ctypes.data, filled.shape[0], filled.shape[1],
+        DEPR_COMPACT if compact else 0, out.ctypes.data, ctypes.byref(st)))
+    return out, st.as_dict()
+
+
+def depression_table(dem, filled, labels, count, cellsize=1.0):
+    """The depression table of host arrays (``hdem_depression_table_f32``; see
+    :func:`depression_table_dev`)."""
+    for name, a in (("dem", dem), ("filled", filled), ("labels", labels)):
+        if not isinstance(a, np.ndarray):
+            raise ValueError(f"{name} is a NumPy array, got {type(a)}")
+    depressions_args(dem, filled, labels)
+    count = _depression_count(count)
+    dem, filled, labels = (np.ascontiguousarray(a) for a in (dem, filled, labels))
+    columns = {name: np.empty(count, dtype) for name, dtype in DEPR_COLUMNS}
+    if count:
+        c = context()
+        c.check(c.lib.hdem_depression_table_f32(
+            c.handle, dem.ctypes.data, filled.ctypes.data, labels.ctypes.data,
+            filled.shape[0], filled.shape[1], count,
+            *[columns[name].ctypes.data for name, _ in DEPR_COLUMNS]))
+    return depression_table_of(columns, cellsize)
 
 
 def sinkfill(z, eps=0.0, max_rounds=0, return_stats=False):

@@ -662,6 +662,147 @@ class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods
         return out
 
 
+def _check_cellsize(cellsize):
+    try:
+        cellsize = float(cellsize)
+    except (TypeError, ValueError):
+        raise ValueError(f"cellsize is a number, got {cellsize!r}") from None
+    if not np.isfinite(cellsize) or cellsize <= 0:
+        raise ValueError(f"cellsize must be finite and positive, got {cellsize}")
+    return cellsize
+
+
+class Depressions(Filter):  # pylint: disable=too-few-public-methods
+    """Depression labelling and inventory (new operator).  Applied to a **filled** float32
+    raster, with -- at construction -- the float32 ``dem`` it is compared with (array or
+    ``DeviceRaster``).  A cell is *raised* where ``filled > dem`` (false where either is NaN);
+    a depression is an 8-connected component of raised cells and ``first`` its smallest flat
+    index ``y * W + x``.  Any such pair of rasters is legal, not only a DEM and its sink fill.
+    Returns uint32 labels, 0 where the cell is not raised.
+
+    ``labels="compact"`` (default): the depressions numbered 1 ... K in ascending order of
+    ``first`` -- exactly ``scipy.ndimage.label(filled > dem, structure=np.ones((3, 3)))``.
+    ``labels="first"``: ``1 + first`` of the cell's depression.
+
+    ``table=True`` (compact labels only) also fills ``table``, one row per label ``k`` at
+    index ``k - 1``: ``first`` (uint32), ``area`` (uint32, cells), ``level`` (float32, the
+    minimum of ``filled``: the water level after an ``epsilon=0`` fill), ``max_depth``
+    (float32, the maximum of ``filled - dem``), ``volume_q20`` (uint64, the sum of the depths
+    in units of 2^-20, each rounded to nearest even and saturating at 2^31 - 1) and
+    ``volume`` (float64, ``volume_q20 / 2**20 * cellsize**2``).  Labels and table are exact,
+    identical from run to run and from ``apply`` and ``apply_device``.
+
+    ``ValueError`` for a ``dem`` that is missing or of another type, dtype or dimension,
+    unknown ``labels``, a table without compact labels, a bad ``cellsize`` (all at
+    construction), a filled raster that is not 2-D float32 of the dem's shape (before the
+    device is touched) and more than 2^32 - 1 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        depressions (K), raised_cells, tile_components, tile_h / tile_w of the last call;
+        phase times when profiling is on.
+    count : int or None
+        K of the last call.
+    table : dict of numpy.ndarray, or None
+        the table of the last call: host arrays of length K, whichever form was called.
+    """
+
+    auto_device = True      # device form == host form for a float32 raster
+
+    def __init__(self, *, dem, labels="compact", table=False, cellsize=1.0):
+        if dem is None:
+            raise ValueError("Depressions needs the dem the filled raster is compared with")
+        if not (isinstance(dem, np.ndarray) or backend.is_device_raster(dem)):
+            raise ValueError(f"dem is a NumPy array or a DeviceRaster, got {type(dem)}")
+        if len(dem.shape) != 2:
+            raise ValueError(f"dem is a 2-D raster, got {len(dem.shape)} dimensions")
+        if np.dtype(dem.dtype) != np.float32:
+            raise ValueError(f"dem has dtype float32, got {dem.dtype}")
+        if labels not in ("first", "compact"):
+            raise ValueError(f"labels is 'first' or 'compact', got {labels!r}")
+        if table and labels != "compact":
+            raise ValueError("the table has one row per compact label: table=True needs "
+                             "labels='compact'")
+        self.dem = dem
+        self.labels = labels
+        self.want_table = bool(table)
+        self.cellsize = _check_cellsize(cellsize)
+        self.stats = {}
+        self.count = None
+        self.table = None
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        backend.depressions_args(self.dem, image_to_filter)
+        dem = self.dem.to_host() if backend.is_device_raster(self.dem) else self.dem
+        self.table = None
+        out, self.stats = backend.depressions(dem, image_to_filter, self.labels == "compact")
+        self.count = self.stats["depressions"]
+        if self.want_table:
+            self.table = backend.depression_table(dem, image_to_filter, out, self.count,
+                                                  self.cellsize)
+        return out
+
+    def apply_device(self, raster):
+        backend.depressions_args(self.dem, raster)
+        self.table = None
+        with backend.on_device(self.dem, np.float32, raster.ctx) as dem, \
+                backend.result_raster(None, raster.shape, np.uint32, raster.ctx) as out:
+            _, self.stats = backend.depressions_dev(dem, raster, self.labels == "compact",
+                                                    out=out)
+            self.count = self.stats["depressions"]
+            if self.want_table:
+                self.table = backend.depression_table_dev(dem, raster, out, self.count,
+                                                          self.cellsize)
+        return out
+
+
+class DepressionInventory(Filter):  # pylint: disable=too-few-public-methods
+    """A float32 DEM to its depressions in one device-resident pass: ``SinkFill(epsilon)``,
+    then compact ``Depressions`` labels of the DEM and its fill, then their table.  The DEM is
+    uploaded once and nothing is downloaded in between.  Returns the uint32 labels.
+
+    ``filled`` is the filled DEM of the last call: a host array after ``apply``, a device
+    raster (the caller's to free) after ``apply_device``.  ``table`` (host arrays, see
+    ``Depressions``), ``count`` and ``stats`` (of the labelling; ``fill_stats`` of the fill)
+    are those of the last call."""
+
+    def __init__(self, *, epsilon=0.0, cellsize=1.0):
+        try:
+            self.epsilon = float(epsilon)
+        except (TypeError, ValueError):
+            raise ValueError(f"epsilon is a number, got {epsilon!r}") from None
+        if not np.isfinite(self.epsilon) or self.epsilon < 0:
+            raise ValueError(f"epsilon must be finite and not negative, got {epsilon}")
+        self.cellsize = _check_cellsize(cellsize)
+        self.filled = self.table = self.count = None
+        self.stats, self.fill_stats = {}, {}
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("DepressionInventory", image_to_filter, np.float32, "a float32 DEM")
+        with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z, \
+                self.apply_device(z) as labels, self.filled as filled:
+            self.filled = None
+            out = labels.to_host()
+            self.filled = filled.to_host()
+        return out
+
+    def apply_device(self, raster):
+        _check_raster("DepressionInventory", raster, np.float32, "a float32 DEM")
+        self.filled = self.table = self.count = None
+        with contextlib.ExitStack() as stack:
+            filled, self.fill_stats = backend.sinkfill_dev(raster, self.epsilon)
+            stack.enter_context(filled)
+            labels = Depressions(dem=raster, table=True, cellsize=self.cellsize)
+            out = labels.apply_device(filled)
+            self.stats, self.count, self.table = labels.stats, labels.count, labels.table
+            self.filled = filled
+            stack.pop_all()                         # the caller's to free from here on
+        return out
+
+
 def _check_flats(flats):
     if flats not in ("keep", "resolve"):
         raise ValueError(f"flats is 'keep' or 'resolve', got {flats!r}")

@@ -587,6 +587,72 @@ int hdem_resolve_flats_u8_dev(hdem_ctx *ctx, const uint8_t *d8, const float *dem
                               uint8_t *out, uint32_t *dist, int flags,
                               hdem_resolve_flats_stats *stats);  /* device pointers */
 
+/* ---- A9  Depressions.apply / DepressionInventory.apply  (new operators: depression
+ *          labelling and inventory) ------------------------------------------------------
+ * dem, filled: float32 H x W; any such pair is legal, not only a raster and its sink fill.
+ *   raised(c)    filled[c] > dem[c], a float compare: false when either value is NaN
+ *   depression   an 8-connected component D of raised cells; first(D) is its smallest flat
+ *                index y * W + x
+ * hdem_depressions_f32 writes uint32 labels:
+ *   flags == 0                   label[c] = 1 + first(D) for c in D, 0 where c is not raised
+ *   flags == HDEM_DEPR_COMPACT   the depressions numbered 1 ... K in ascending order of first
+ *       (K = stats.depressions): the numbering of scipy.ndimage.label with the 3 x 3
+ *       structure, which numbers components in scan order of their first cell.
+ * hdem_depression_table_f32 takes the compact labels of that pair and K and writes one row per
+ * label k = 1 ... K into the columns (index k - 1); each column may be NULL (not wanted), at
+ * least one must not be:
+ *   first       uint32   first(D)
+ *   area        uint32   the number of cells
+ *   level       float32  the minimum of filled over D (after an epsilon = 0 fill every cell of
+ *                        a depression holds it)
+ *   max_depth   float32  the maximum of filled[c] - dem[c], one float32 subtraction per cell
+ *   volume_q20  uint64   the sum of min(rint((double)(filled[c] - dem[c]) * 2^20), 2^31 - 1):
+ *                        depth in fixed point with a quantum of 2^-20, round to nearest even,
+ *                        saturating just under 2048; an integer sum cannot overflow here
+ *                        (2^32 cells x 2^31 < 2^63)
+ * K == 0 is legal and launches nothing.  Labels and every column are an order-independent
+ * reduction (min, max, integer add): exact, identical from run to run and independent of the
+ * schedule, and so are the three counters of the stats.
+ * HDEM_ERR_BAD_ARG for unknown flags, for H * W > 2^32 - 1 -- before any allocation or launch
+ * -- and, from the table call, in bounded time, for a label > K and for a labelled cell that
+ * is not raised ("the labels do not belong to these rasters: N cells").  Every loop of the
+ * union-find carries an iteration cap; HDEM_ERR_NOT_CONVERGED if one is ever reached.  On
+ * error the contents of the outputs are unspecified.
+ * Workspace from the context's arena: none per cell for the labelling (the label raster is
+ * its own union-find forest), 12 B per 64 cells (0.19 B per cell) more for the compact
+ * numbering, 512 B for the table.  The _dev forms synchronise the context's stream to read K
+ * and their validity counters.  stats may be NULL; otherwise the caller sets
+ * stats->struct_size = sizeof(hdem_depressions_stats) first (56 bytes in this version; a
+ * shorter struct is filled as far as it goes).  The three phase times are filled only while
+ * profiling is on (hdem_profile_enable); the calls have no kernel id. */
+#define HDEM_DEPR_COMPACT 1
+typedef struct hdem_depressions_stats {
+    uint32_t struct_size;   /* in: sizeof(hdem_depressions_stats), set by the caller        */
+    int32_t reserved;       /* 0                                                            */
+    int64_t depressions;    /* K                                                            */
+    int64_t raised_cells;
+    int64_t tile_components; /* components of phase A, summed over the 64 x 64 tiles        */
+    int32_t tile_h, tile_w;
+    float ms_tile;          /* phase A: components inside a tile (HIP events; profiling)    */
+    float ms_seam;          /* phase B: unions across the tile seams                        */
+    float ms_final;         /* phase C: roots flattened, labels written and numbered        */
+    int32_t reserved2;      /* 0                                                            */
+} hdem_depressions_stats;   /* sizeof == 56 */
+int hdem_depressions_f32(hdem_ctx *ctx, const float *dem, const float *filled, int H, int W,
+                         int flags, uint32_t *labels,
+                         hdem_depressions_stats *stats);         /* host pointers, synchronous */
+int hdem_depressions_f32_dev(hdem_ctx *ctx, const float *dem, const float *filled, int H, int W,
+                             int flags, uint32_t *labels,
+                             hdem_depressions_stats *stats);     /* device pointers */
+int hdem_depression_table_f32(hdem_ctx *ctx, const float *dem, const float *filled,
+                              const uint32_t *labels, int H, int W, int64_t K, uint32_t *first,
+                              uint32_t *area, float *level, float *max_depth,
+                              uint64_t *volume_q20);             /* host pointers, synchronous */
+int hdem_depression_table_f32_dev(hdem_ctx *ctx, const float *dem, const float *filled,
+                                  const uint32_t *labels, int H, int W, int64_t K,
+                                  uint32_t *first, uint32_t *area, float *level,
+                                  float *max_depth, uint64_t *volume_q20);  /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
