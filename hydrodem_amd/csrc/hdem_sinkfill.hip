@@ -1978,16 +1978,22 @@ extern "C" int hdem_sinkfill_f32_dev(hdem_ctx *ctx, const float *z, int H, int W
                 coarse_eps = (float)b * (eps + ulp) + ulp;
                 coarse_add = (float)b * (eps + ulp) + 2.0f * ulp;
             }
-            ctx->in_coarse_presolve = true;
-            const int rc = hdem_sinkfill_f32_dev(ctx, cz, ch, cwid, coarse_eps, 0,
-                                                 HDEM_FILL_INIT | HDEM_FILL_NO_VERIFY |
-                                                     HDEM_FILL_NO_COARSE,
-                                                 cfill, nullptr);
-            ctx->in_coarse_presolve = false;
-            if (rc) return rc;
-            coarse = cfill;
-            coarse_cw = cwid;
-            coarse_shift = cshift;
+            // (elevations near FLT_MAX: the span overflows and there is no finite allowance --
+            // no bound to offer, the fill starts from +inf as it does without the switch)
+            if (std::isfinite(coarse_add)) {
+                ctx->in_coarse_presolve = true;
+                const int rc = hdem_sinkfill_f32_dev(ctx, cz, ch, cwid, coarse_eps, 0,
+                                                     HDEM_FILL_INIT | HDEM_FILL_NO_VERIFY |
+                                                         HDEM_FILL_NO_COARSE,
+                                                     cfill, nullptr);
+                ctx->in_coarse_presolve = false;
+                if (rc) return rc;
+                coarse = cfill;
+                coarse_cw = cwid;
+                coarse_shift = cshift;
+            } else {
+                coarse_add = 0.0f;
+            }
         }
     }
     ctx->start_coarse = nullptr;                // a caller's coarse raster is used once

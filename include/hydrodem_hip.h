@@ -191,7 +191,16 @@ typedef struct hdem_fill_stats {
                                       problem that does wait; stats->pending is -1.          */
 
 /* eps = 0 gives flats (exact, order-independent, bit-reproducible);
- * eps > 0 is the Planchon-Darboux gradient.  max_rounds <= 0 -> default. */
+ * eps > 0 is the Planchon-Darboux gradient.  max_rounds <= 0 -> default.
+ *
+ * Input contract of the three fill entry points: every elevation of z is a finite float32, or
+ * NaN for nodata.  Any sign and any magnitude up to FLT_MAX is supported and gives the bits of
+ * the definition (negative and zero-crossing terrain, +0 / -0, relief far below or eps far
+ * below one ulp, elevations above 3.0e38: tests/test_gpu_elevation_regimes.py).  +inf and
+ * -inf are NOT supported: +inf is what a tile visit reads a nodata wall as, so an interior
+ * +inf cell comes back as NaN from a tile that was visited and as +inf from one that never
+ * was -- the result depends on the visit history.  Replace infinities by NaN (nodata) or by a
+ * finite value before the call. */
 int hdem_sinkfill_f32(hdem_ctx *ctx, const float *z, int H, int W, float eps,
                       int max_rounds, float *w, hdem_fill_stats *stats);
 int hdem_sinkfill_f32_dev(hdem_ctx *ctx, const float *z, int H, int W,
