@@ -64,7 +64,7 @@ struct hdem_ctx {
     std::vector<hipEvent_t> event_pool;
     hdem_kernel_stat stats[HDEM_K_COUNT] = {};
     // sink-fill workspace (grown on demand, reused across calls)
-    void *fill_ws[3] = {nullptr, nullptr, nullptr};   // [hub_depth]
+    void *fill_ws[3] = {nullptr, nullptr, nullptr};   // [nesting depth of the fill]
     size_t fill_ws_bytes[3] = {0, 0, 0};
     int fill_slice_us = 0;             // 0: run the asynchronous phase to convergence
     int fill_last_h = 0, fill_last_w = 0;   // problem the worklist in fill_ws belongs to
@@ -79,14 +79,9 @@ struct hdem_ctx {
     const int32_t *start_row_map = nullptr;
     int start_cw = 0, start_shift = 0;
     void *coarse_buf = nullptr;
-    bool in_coarse_presolve = false;   // the fill in progress is that pre-solve
-    uint8_t *fill_d8 = nullptr;        // D8 raster the certifying pass of the next fill writes
-    bool fill_d8_done = false;         // ... and whether it did
-    bool fill_d8_ring_done = false;    // ... the raster ring included (the certifying stream)
     size_t coarse_bytes = 0;
     void *hub_buf[2] = {nullptr, nullptr};   // hub start of the sink fill: rim lines, hub raster
     size_t hub_bytes[2] = {0, 0};            // ([1]: of the hub raster's own fill)
-    int hub_depth = 0;                       // 0: a caller's fill, 1: of a hub raster, 2: of its raster
     // ... prepared for a row-block partition (hdem_fill_hub_prepare_dev), and the levels the
     // partition worked out for the next INIT fill of that block
     const float *hub_prep_z = nullptr;

@@ -1588,10 +1588,12 @@ __global__ __launch_bounds__(NT) void fill_seam_busy_kernel(const int *__restric
 
 size_t stat_ints_of(const fill_ws &ws) { return (size_t)ws.G * STAT_WORDS * 2; }
 
-int ensure_ws(hdem_ctx *ctx, int H, int W, int max_rounds, int G, bool *resume, fill_ws *ws,
-              bool *keep_stats_io = nullptr)
+// (a workspace per nesting depth: the fill of a hub raster runs in the middle of the fill it
+// starts, whose workspace is set up already)
+int ensure_ws(hdem_ctx *ctx, int depth, int H, int W, int max_rounds, int G, bool *resume,
+              fill_ws *ws, bool *keep_stats_io)
 {
-    bool keep_stats = keep_stats_io && *keep_stats_io;
+    bool keep_stats = *keep_stats_io;
     // tiles cover the interior (rows 1..H-2, cols 1..W-2); none if there is no interior
     ws->tiles_x = W >= 3 && H >= 3 ? (W - 2 + FT - 1) / FT : 0;
     ws->tiles_y = W >= 3 && H >= 3 ? (H - 2 + FT - 1) / FT : 0;
@@ -1600,15 +1602,13 @@ int ensure_ws(hdem_ctx *ctx, int H, int W, int max_rounds, int G, bool *resume, 
     ws->G = std::max(1, std::min(G, ws->ntiles));
     ws->S = std::max(1, (ws->ntiles + ws->G - 1) / ws->G);
     const size_t n = (size_t)std::max(ws->ntiles, 1), gs = (size_t)ws->G * ws->S;
-    const size_t stat_ints = (size_t)ws->G * STAT_WORDS * 2;
+    const size_t stat_ints = stat_ints_of(*ws);
     const size_t head = HEAD_INTS;                                 // error + pad (128 B)
     const size_t ints = head + stat_ints + PEND_SHARDS * PEND_STRIDE + n + 2 * gs +
                         (size_t)max_rounds + 32 + 3 * n;
     const size_t bytes = ints * sizeof(int);
-    // (a workspace per nesting depth: the fill of a hub raster runs in the middle of the fill it
-    // starts, whose workspace is set up already)
-    void *&ws_buf = ctx->fill_ws[ctx->hub_depth];
-    size_t &ws_bytes = ctx->fill_ws_bytes[ctx->hub_depth];
+    void *&ws_buf = ctx->fill_ws[depth];
+    size_t &ws_bytes = ctx->fill_ws_bytes[depth];
     if (ws_bytes < bytes) {
         if (ws_buf) {
             HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -1648,7 +1648,7 @@ int ensure_ws(hdem_ctx *ctx, int H, int W, int max_rounds, int G, bool *resume, 
     // launch and are written out behind it); a resumed worklist keeps pend / state /
     // tile_key / prio of the last slice
     const size_t zeros = head + stat_ints + any_ints + n + (*resume ? 0 : pend_ints + gs);
-    if (keep_stats_io) *keep_stats_io = keep_stats;
+    *keep_stats_io = keep_stats;
     if (keep_stats) {
         // (the counters of deferred calls stay: the first call that waits reports them too)
         HDEM_HIP_CHECK(hipMemsetAsync(base, 0, head * sizeof(int), ctx->stream));
@@ -1712,28 +1712,67 @@ int hub_alloc(hdem_ctx *ctx, int depth, int H, int W, hub_bufs *hb)
     return HDEM_OK;
 }
 
-void hub_launch_dist(hdem_ctx *ctx, const float *z, float *w, int H, int W, const hub_bufs &hb)
+// The fill's switches for experiments and tests.  Read from the environment at the top of
+// every entry point that needs them (the tests change them between two calls of one process)
+// and passed down from there.
+constexpr long long NO_TEST_BUDGET = -0x7fffffffffffffffll - 1;   // test_budget_us: not set
+struct fill_knobs {
+    bool sync;                 // HDEM_FILL_SYNC: the round driver alone, as HDEM_FILL_SYNC_ONLY
+    bool trace;                // HDEM_FILL_TRACE: every fill's counters on stderr
+    bool certify_rounds;       // HDEM_FILL_CERTIFY_ROUNDS: certify by rounds, never by the stream
+    bool hub;                  // HDEM_FILL_HUB=0: no hub start of the library's own
+    int hub_min_tiles;         // HDEM_HUB_MIN_TILES: ... from this many tiles on
+    int hub_min_tiles_nested;  // HDEM_HUB_MIN_TILES_NESTED: ... in the fill of a hub raster
+    int hub_iters;             // HDEM_HUB_ITERS: hub_dist_kernel's instantiation (experiments)
+    int hub_wgs;               // HDEM_HUB_WGS: a resident grid of this many per CU walks the tiles
+                               // (experiments; 0: one workgroup per tile)
+    bool eps_coarse;           // HDEM_FILL_EPS_COARSE: own coarse start at eps > 0 too
+    long long coarse_min_cells;   // HDEM_COARSE_MIN_CELLS: own coarse start from this size on
+    int coarse_shift;          // HDEM_COARSE_SHIFT: log2 of its block edge
+    int wgs_per_cu;            // HDEM_FILL_WGS_PER_CU: grid of the launches (experiments, tests)
+    long long test_budget_us;  // HDEM_FILL_TEST_BUDGET_US: tests cut the asynchronous phase short
+                               // so that the passes behind it have work (pre-solves ignore it)
+};
+
+fill_knobs fill_read_knobs()
+{
+    const auto num = [](const char *name, long long unset) {
+        const char *e = getenv(name);
+        return e ? atoll(e) : unset;
+    };
+    fill_knobs k;
+    k.sync = getenv("HDEM_FILL_SYNC") != nullptr;
+    k.trace = getenv("HDEM_FILL_TRACE") != nullptr;
+    k.certify_rounds = getenv("HDEM_FILL_CERTIFY_ROUNDS") != nullptr;
+    k.hub = num("HDEM_FILL_HUB", 1) != 0;
+    k.hub_min_tiles = (int)num("HDEM_HUB_MIN_TILES", HUB_MIN_TILES);
+    k.hub_min_tiles_nested = (int)num("HDEM_HUB_MIN_TILES_NESTED", HUB_MIN_TILES_NESTED);
+    k.hub_iters = (int)num("HDEM_HUB_ITERS", 3);
+    k.hub_wgs = (int)num("HDEM_HUB_WGS", 0);
+    k.eps_coarse = getenv("HDEM_FILL_EPS_COARSE") != nullptr;
+    k.coarse_min_cells = num("HDEM_COARSE_MIN_CELLS", COARSE_MIN_CELLS);
+    k.coarse_shift = (int)num("HDEM_COARSE_SHIFT", COARSE_SHIFT);
+    k.wgs_per_cu = (int)num("HDEM_FILL_WGS_PER_CU", 8);
+    k.test_budget_us = num("HDEM_FILL_TEST_BUDGET_US", NO_TEST_BUDGET);
+    return k;
+}
+
+void hub_launch_dist(hdem_ctx *ctx, const fill_knobs &kn, const float *z, float *w, int H, int W,
+                     const hub_bufs &hb)
 {
     const int ntiles = hb.tiles_x * hb.tiles_y;
-    // (HDEM_HUB_ITERS / HDEM_HUB_WGS: experiments)
-    const int iters = getenv("HDEM_HUB_ITERS") ? atoi(getenv("HDEM_HUB_ITERS")) : 3;
     // one workgroup per tile: a resident grid of 8 per CU walking the tiles was measured
-    // at 0.77 against 0.64 ms (HDEM_HUB_WGS: that grid, per CU)
-    const int grid = getenv("HDEM_HUB_WGS") ? std::min(ntiles, ctx->num_cus * atoi(getenv("HDEM_HUB_WGS")))
-                                            : (ntiles + 7) / 8 * 8;     // (whole rounds of the 8 XCDs)
-    hipStream_t st = ctx->stream;
-    if (iters >= 4)
-        hipLaunchKernelGGL(hub_dist_kernel<4>, dim3(grid), dim3(NT), 0, st, z, w, H, W, hb.tiles_x,
-                           ntiles, hb.edge, hb.node);
-    else if (iters == 3)
-        hipLaunchKernelGGL(hub_dist_kernel<3>, dim3(grid), dim3(NT), 0, st, z, w, H, W, hb.tiles_x,
-                           ntiles, hb.edge, hb.node);
-    else if (iters <= 1)
-        hipLaunchKernelGGL(hub_dist_kernel<1>, dim3(grid), dim3(NT), 0, st, z, w, H, W, hb.tiles_x,
-                           ntiles, hb.edge, hb.node);
-    else
-        hipLaunchKernelGGL(hub_dist_kernel<2>, dim3(grid), dim3(NT), 0, st, z, w, H, W, hb.tiles_x,
-                           ntiles, hb.edge, hb.node);
+    // at 0.77 against 0.64 ms
+    const int grid = kn.hub_wgs ? std::min(ntiles, ctx->num_cus * kn.hub_wgs)
+                                : (ntiles + 7) / 8 * 8;     // (whole rounds of the 8 XCDs)
+    // (named in this order, one statement each: the code object holds the instantiations in the
+    // order the host code first names them)
+    auto kernel = &hub_dist_kernel<4>;
+    if (kn.hub_iters == 3) kernel = &hub_dist_kernel<3>;
+    else if (kn.hub_iters <= 1) kernel = &hub_dist_kernel<1>;
+    else if (kn.hub_iters < 4) kernel = &hub_dist_kernel<2>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), 0, ctx->stream, z, w, H, W, hb.tiles_x, ntiles,
+                       hb.edge, hb.node);
 }
 
 void hub_launch_edges(hdem_ctx *ctx, const float *z, float *w, int H, int W, int flags,
@@ -1759,11 +1798,12 @@ extern "C" int hdem_fill_hub_prepare_dev(hdem_ctx *ctx, const float *z, int H, i
     HDEM_REQUIRE(H >= 3 && W >= 3, HDEM_ERR_BAD_ARG, "hub start needs an interior, got %d x %d", H, W);
     HDEM_REQUIRE(z != w, HDEM_ERR_BAD_ARG, "sink fill cannot run in place");
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
+    const fill_knobs kn = fill_read_knobs();
     hub_bufs hb;
     if (int rc = hub_alloc(ctx, 0, H, W, &hb)) return rc;
     {
         hdem_scoped_timer tm(ctx, HDEM_K_FILL_HUB, (int64_t)H * W);
-        hub_launch_dist(ctx, z, w, H, W, hb);
+        hub_launch_dist(ctx, kn, z, w, H, W, hb);
     }
     HDEM_HIP_CHECK(hipGetLastError());
     ctx->hub_prep_z = z;
@@ -1853,396 +1893,476 @@ extern "C" int hdem_set_fill_seam_words(hdem_ctx *ctx, int *words)
     return HDEM_OK;
 }
 
-extern "C" int hdem_sinkfill_f32_dev(hdem_ctx *ctx, const float *z, int H, int W, float eps,
-                                     int max_rounds, int flags, float *w,
-                                     hdem_fill_stats *stats)
-{
-    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    if (int rc = hdem_check_raster(z, w, H, W)) return rc;
-    HDEM_REQUIRE(z != w, HDEM_ERR_BAD_ARG, "sink fill cannot run in place");
-    HDEM_REQUIRE(eps >= 0.0f && eps == eps, HDEM_ERR_BAD_ARG, "eps must be >= 0, got %g",
-                 (double)eps);
-    HDEM_HIP_CHECK(hipSetDevice(ctx->device));
-    if (max_rounds <= 0) max_rounds = 1 << 16;
-    const int K = 8;   // rounds enqueued between convergence checks
-    max_rounds = (max_rounds + K - 1) / K * K;
-    // (64 rows of a window must be addressable with 32-bit byte offsets)
-    const bool use_async = !(flags & HDEM_FILL_SYNC_ONLY) && getenv("HDEM_FILL_SYNC") == nullptr &&
-                           (size_t)64 * W * sizeof(float) < (size_t)0xffffffffu;
-    const bool trace = getenv("HDEM_FILL_TRACE") != nullptr;
-    // (taken here: the coarse pre-solve below re-enters this function)
-    uint8_t *const d8_request = ctx->fill_d8;
-    ctx->fill_d8 = nullptr;
-    ctx->fill_d8_done = false;
-    const int async_id = ctx->in_coarse_presolve ? HDEM_K_FILL_COARSE : HDEM_K_FILL_TILE;
+// ---- the host driver of one fill --------------------------------------------------------
+// fill_run is the fill behind hdem_sinkfill_f32_dev and hdem_sinkfill_d8_f32_dev, and it is
+// the fill of its own start rasters: the coarse pre-solve and the hub raster are filled by
+// fill_run calls one level down, which are told what they are through fill_call.
+namespace {
 
-    // a worklist can only be resumed for the problem it was built for; when it cannot,
-    // every tile is due again (correct, just slower)
-    const bool want_resume = (flags & HDEM_FILL_RESUME) && (flags & HDEM_FILL_WARM);
-    const bool same = ctx->fill_last_h == H && ctx->fill_last_w == W && ctx->fill_last_z == z &&
-                      ctx->fill_last_out == w;
-    bool resume = want_resume && use_async && same && ctx->fill_resumable;
-    if (want_resume) flags |= HDEM_FILL_NO_VERIFY;
-    // ---- coarse start (INIT, eps = 0): the caller's coarse fill, or our own -------------
+constexpr int FILL_K = 8;          // rounds enqueued between convergence checks
+
+enum fill_role {                   // (the value is fill_async_kernel's ROLE)
+    FILL_CALLER = 0,               // the fill the caller asked for: K_FILL_TILE
+    FILL_PRESOLVE = 1,             // the fill of a start raster: K_FILL_COARSE, nobody waits for it
+};
+
+struct fill_call {
+    const float *z;
+    int H, W;
+    float eps;
+    int max_rounds, flags;
+    float *w;
+    hdem_fill_stats *stats;
+    uint8_t *d8;                   // D8 raster for the certifying pass to write, or null
+    int depth;                     // 0: a caller's fill and its coarse pre-solve, 1: of a hub raster,
+                                   // 2: of that raster's hub raster; picks fill_ws[] and hub_buf[]
+    fill_role role;
+};
+
+struct fill_outcome {
+    bool d8_done = false;          // the certifying pass wrote the D8 codes
+    bool d8_ring_done = false;     // ... the raster ring included (the certifying stream)
+};
+
+enum fill_start_kind {
+    START_INF,                     // +inf behind the ring
+    START_COARSE_GIVEN,            // the caller's filled coarse raster (hdem_set_fill_coarse_start)
+    START_COARSE_OWN,              // the block-maximum raster, filled here first
+    START_HUB_GIVEN,               // the levels of a row-block partition (hdem_set_fill_hub_levels)
+    START_HUB_OWN,                 // the hub graph of this raster, filled here first
+    START_WARM,                    // what is in w
+};
+
+struct fill_start {
+    fill_start_kind kind = START_INF;
     const float *coarse = nullptr;
     const int *row_map = nullptr;
-    int coarse_cw = 0, coarse_shift = 0;
-    // hub start (above): the single-GPU INIT default from HUB_MIN_TILES tiles on; or the levels
-    // a row-block partition worked out for this block (hdem_set_fill_hub_levels)
+    int cw = 0, shift = 0;
+    float coarse_add = 0.0f;
     const float *hub_lev = nullptr;
     hub_bufs hubs = {};
-    const int hub_depth = ctx->hub_depth;
+};
+
+// What the call has decided before it touches the stream.
+struct fill_plan {
+    int flags, max_rounds;         // as amended (RESUME implies NO_VERIFY, rounds in whole batches)
+    bool use_async, want_resume, same, resume, defer, warm, did_async;
+    int mode, slice_us;
+    const int *idle_words;
+};
+
+// Where the launches have left the fill.
+struct fill_result {
+    int converged = 0, round = 0;
+    int64_t pending = 0;
+    bool verify = true;
+    bool have_counts = false;      // head words + counters already on the host
+    bool d8_by_stream = false;     // the certifying stream wrote the codes (every cell)
+    bool ended = false;            // nothing to report: the call returns as it is
+    uint8_t *d8 = nullptr;
+};
+
+int fill_run(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, fill_outcome *out);
+
+int fill_async_id(const fill_call &c)
+{
+    return c.role == FILL_PRESOLVE ? HDEM_K_FILL_COARSE : HDEM_K_FILL_TILE;
+}
+
+unsigned fill_tile_blocks(const fill_ws &ws)
+{
+    return (unsigned)std::max(1, (ws.ntiles + INIT_NT - 1) / INIT_NT);
+}
+
+// The problem the worklist in the workspace belongs to; nothing to resume until the call
+// has ended well.
+void fill_remember(hdem_ctx *ctx, const fill_call &c)
+{
+    ctx->fill_last_h = c.H;
+    ctx->fill_last_w = c.W;
+    ctx->fill_last_z = c.z;
+    ctx->fill_last_out = c.w;
+    ctx->fill_resumable = ctx->fill_quiescent = false;
+}
+
+// Head words and per-workgroup counters to the host, in one wait; with_pend: the shards of the
+// pending count too, which land behind them.
+int fill_read_counts(hdem_ctx *ctx, const fill_ws &ws, bool with_pend)
+{
+    const size_t ints = HEAD_INTS + stat_ints_of(ws);
+    HDEM_HIP_CHECK(hipMemcpyAsync(ctx->host_counts, ws.error, ints * sizeof(int),
+                                  hipMemcpyDeviceToHost, ctx->stream));
+    if (with_pend)
+        HDEM_HIP_CHECK(hipMemcpyAsync(ctx->host_counts + ints, ws.pend,
+                                      PEND_SHARDS * PEND_STRIDE * sizeof(int),
+                                      hipMemcpyDeviceToHost, ctx->stream));
+    HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return HDEM_OK;
+}
+
+// ---- phase 1: what the relaxation starts from -------------------------------------------
+// Consumes the caller's hub levels (always) and allocates the hub buffers of an own hub start.
+int fill_choose_start(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, const fill_plan &p,
+                      fill_start *s)
+{
+    const int H = c.H, W = c.W;
+    const bool ghosts = (p.flags & (HDEM_FILL_GHOST_TOP | HDEM_FILL_GHOST_BOTTOM)) != 0;
+    // hub start: the single-GPU INIT default from HUB_MIN_TILES tiles on; or the levels a
+    // row-block partition worked out for this block (hdem_set_fill_hub_levels)
     const float *const hub_given = ctx->hub_levels_given;
     ctx->hub_levels_given = nullptr;
     if (hub_given) {
-        HDEM_REQUIRE(!(flags & HDEM_FILL_WARM) && eps == 0.0f && use_async &&
-                         ctx->hub_prep_z == z && ctx->hub_prep_w == w && ctx->hub_prep_h == H &&
+        HDEM_REQUIRE(!(p.flags & HDEM_FILL_WARM) && c.eps == 0.0f && p.use_async &&
+                         ctx->hub_prep_z == c.z && ctx->hub_prep_w == c.w && ctx->hub_prep_h == H &&
                          ctx->hub_prep_cols == W,
                      HDEM_ERR_BAD_ARG, "hub levels were set for another fill than this one");
         ctx->hub_prep_z = nullptr;
-        hub_lev = hub_given;
-    } else if (!(flags & HDEM_FILL_WARM) && eps == 0.0f && !ctx->start_coarse && use_async &&
-               !(flags & (HDEM_FILL_GHOST_TOP | HDEM_FILL_GHOST_BOTTOM)) &&
+        s->kind = START_HUB_GIVEN;
+        s->hub_lev = hub_given;
+    } else if (p.flags & HDEM_FILL_WARM) {
+        s->kind = START_WARM;
+    } else if (c.eps == 0.0f && !ctx->start_coarse && p.use_async && !ghosts &&
                // (NO_COARSE is the caller's "start from +inf"; the fill of a hub raster -- depth
                // 1 -- carries it only to keep the block-maximum start out, and may take a hub
                // start of its own, whose raster -- depth 2 -- is filled plainly)
-               (hub_depth == 1 || (hub_depth == 0 && !(flags & HDEM_FILL_NO_COARSE))) &&
-               !(getenv("HDEM_FILL_HUB") && atoi(getenv("HDEM_FILL_HUB")) == 0) && H >= 3 && W >= 3) {
-        const int txs = (W - 2 + FT - 1) / FT, tys = (H - 2 + FT - 1) / FT;
-        const int min_tiles = hub_depth ? (getenv("HDEM_HUB_MIN_TILES_NESTED")
-                                               ? atoi(getenv("HDEM_HUB_MIN_TILES_NESTED"))
-                                               : HUB_MIN_TILES_NESTED)
-                                        : (getenv("HDEM_HUB_MIN_TILES") ? atoi(getenv("HDEM_HUB_MIN_TILES"))
-                                                                        : HUB_MIN_TILES);
-        if ((int64_t)txs * tys >= min_tiles) {
-            if (int rc = hub_alloc(ctx, hub_depth, H, W, &hubs)) return rc;
-            hub_lev = hubs.lev;
-        }
-    }
-    float coarse_add = 0.0f;
-    // (eps > 0: the block-maximum start below is valid and keeps the bits -- tested -- but the
-    // launch behind it takes 14 instead of 9 ms at 16384^2: a bound that is flat inside every
-    // block, under a surface that climbs cell by cell, has every tile relax many times while
-    // the values from the outlets are still on their way; from +inf the tiles run in the order
-    // the flood reaches them.  Off unless HDEM_FILL_EPS_COARSE is set.)
-    const bool eps_coarse = eps != 0.0f && !ctx->start_coarse && getenv("HDEM_FILL_EPS_COARSE");
-    if (!(flags & HDEM_FILL_WARM) && !hub_lev && (eps == 0.0f || eps_coarse)) {
+               (c.depth == 1 || (c.depth == 0 && !(p.flags & HDEM_FILL_NO_COARSE))) && kn.hub &&
+               H >= 3 && W >= 3 &&
+               (int64_t)((W - 2 + FT - 1) / FT) * ((H - 2 + FT - 1) / FT) >=
+                   (c.depth ? kn.hub_min_tiles_nested : kn.hub_min_tiles)) {
+        if (int rc = hub_alloc(ctx, c.depth, H, W, &s->hubs)) return rc;
+        s->kind = START_HUB_OWN;
+        s->hub_lev = s->hubs.lev;
+    } else if (c.eps == 0.0f || (kn.eps_coarse && !ctx->start_coarse)) {
+        // coarse start (eps > 0: only on request, see fill_coarse_presolve)
         if (ctx->start_coarse) {
-            coarse = ctx->start_coarse;
-            row_map = ctx->start_row_map;
-            coarse_cw = ctx->start_cw;
-            coarse_shift = ctx->start_shift;
-        } else if (use_async && !(flags & (HDEM_FILL_NO_COARSE | HDEM_FILL_GHOST_TOP |
-                                           HDEM_FILL_GHOST_BOTTOM)) &&
-                   (int64_t)H * W >= (getenv("HDEM_COARSE_MIN_CELLS")
-                                         ? atoll(getenv("HDEM_COARSE_MIN_CELLS"))
-                                         : (int64_t)COARSE_MIN_CELLS)) {
-            // fill the block-maximum raster first: 1/256 of the cells, and every level in
-            // it bounds the fine fill of its block from above
-            const int cshift = getenv("HDEM_COARSE_SHIFT") ? atoi(getenv("HDEM_COARSE_SHIFT")) : COARSE_SHIFT;
-            const int b = 1 << cshift, ch = (H + b - 1) / b, cwid = (W + b - 1) / b;
-            const size_t need = ((size_t)2 * ch * cwid + 4) * sizeof(float);
-            if (ctx->coarse_bytes < need) {
-                if (ctx->coarse_buf) {
-                    HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                    HDEM_HIP_CHECK(hipFree(ctx->coarse_buf));
-                    ctx->coarse_buf = nullptr;
-                    ctx->coarse_bytes = 0;
-                }
-                if (int rc = hdem_raw_alloc(ctx, need, &ctx->coarse_buf)) return rc;
-                ctx->coarse_bytes = need;
-            }
-            float *cz = (float *)ctx->coarse_buf, *cfill = cz + (size_t)ch * cwid;
-            if (int rc = hdem_blockmax_f32_dev(ctx, z, H, W, b, cz)) return rc;
-            float coarse_eps = 0.0f;
-            if (eps != 0.0f) {
-                // Gradient fill (eps > 0): a fine path that follows a chain of blocks makes at
-                // most b steps per block of the chain, every step adds eps -- in float32: at
-                // most eps + half an ulp of the value, and every value of the fill is below
-                // twice the largest |elevation| + what the path adds -- so the coarse raster
-                // filled with  eps_c = b (eps + ulp) + ulp  (the last ulp: its own additions
-                // round too) bounds a cell of block B by  level(B) + b (eps + ulp) + 2 ulp:
-                // up to b steps from the cell to the chain, one rounding of that sum.
-                int *amax = (int *)(cfill + (size_t)ch * cwid);
-                HDEM_HIP_CHECK(hipMemsetAsync(amax, 0, sizeof(int), ctx->stream));
-                hipLaunchKernelGGL(absmax_kernel, dim3(64), dim3(INIT_NT), 0, ctx->stream, cz,
-                                   (size_t)ch * cwid, amax);
-                float top = 0.0f;
-                HDEM_HIP_CHECK(hipMemcpyAsync(&top, amax, sizeof(float), hipMemcpyDeviceToHost,
-                                              ctx->stream));
-                HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                // (values may climb above the highest block by the gradient itself: twice the
-                // top, and never less than 1, is a generous binade)
-                const float span = 2.0f * std::max(top, 1.0f) + (float)(ch + cwid) * b * eps;
-                const float ulp = std::nextafter(span, HDEM_INF) - span;
-                coarse_eps = (float)b * (eps + ulp) + ulp;
-                coarse_add = (float)b * (eps + ulp) + 2.0f * ulp;
-            }
-            // (elevations near FLT_MAX: the span overflows and there is no finite allowance --
-            // no bound to offer, the fill starts from +inf as it does without the switch)
-            if (std::isfinite(coarse_add)) {
-                ctx->in_coarse_presolve = true;
-                const int rc = hdem_sinkfill_f32_dev(ctx, cz, ch, cwid, coarse_eps, 0,
-                                                     HDEM_FILL_INIT | HDEM_FILL_NO_VERIFY |
-                                                         HDEM_FILL_NO_COARSE,
-                                                     cfill, nullptr);
-                ctx->in_coarse_presolve = false;
-                if (rc) return rc;
-                coarse = cfill;
-                coarse_cw = cwid;
-                coarse_shift = cshift;
-            } else {
-                coarse_add = 0.0f;
-            }
+            s->kind = START_COARSE_GIVEN;
+            s->coarse = ctx->start_coarse;
+            s->row_map = ctx->start_row_map;
+            s->cw = ctx->start_cw;
+            s->shift = ctx->start_shift;
+        } else if (p.use_async && !(p.flags & HDEM_FILL_NO_COARSE) && !ghosts &&
+                   (int64_t)H * W >= kn.coarse_min_cells) {
+            s->kind = START_COARSE_OWN;
         }
     }
-    ctx->start_coarse = nullptr;                // a caller's coarse raster is used once
-    ctx->start_row_map = nullptr;
-    fill_ws ws;
-    // (HDEM_FILL_WGS_PER_CU: experiments and tests; the machine holds 8 of these one-wave
-    // workgroups per CU -- more than 8 is a launch that cannot be resident at once)
-    const int wgs_per_cu = getenv("HDEM_FILL_WGS_PER_CU") ? atoi(getenv("HDEM_FILL_WGS_PER_CU")) : 8;
-    bool keep_stats = ctx->fill_stats_carry && same && !ctx->in_coarse_presolve;
-    if (int rc = ensure_ws(ctx, H, W, max_rounds, ctx->num_cus * std::max(1, std::min(wgs_per_cu, 16)),
-                           &resume, &ws, &keep_stats))
+    return HDEM_OK;
+}
+
+// ---- phase 2: the library's own coarse start --------------------------------------------
+// Fills the block-maximum raster first: 1/256 of the cells, and every level in it bounds the
+// fine fill of its block from above.  Runs before the workspace of the call itself is set up
+// and shares slot c.depth of it.  Grows ctx->coarse_buf.
+// (eps > 0: the block-maximum start is valid and keeps the bits -- tested -- but the launch
+// behind it takes 14 instead of 9 ms at 16384^2: a bound that is flat inside every block,
+// under a surface that climbs cell by cell, has every tile relax many times while the values
+// from the outlets are still on their way; from +inf the tiles run in the order the flood
+// reaches them.  Off unless HDEM_FILL_EPS_COARSE is set.)
+int fill_coarse_presolve(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, fill_start *s)
+{
+    const float eps = c.eps;
+    const int b = 1 << kn.coarse_shift, ch = (c.H + b - 1) / b, cwid = (c.W + b - 1) / b;
+    const size_t need = ((size_t)2 * ch * cwid + 4) * sizeof(float);
+    if (ctx->coarse_bytes < need) {
+        if (ctx->coarse_buf) {
+            HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            HDEM_HIP_CHECK(hipFree(ctx->coarse_buf));
+            ctx->coarse_buf = nullptr;
+            ctx->coarse_bytes = 0;
+        }
+        if (int rc = hdem_raw_alloc(ctx, need, &ctx->coarse_buf)) return rc;
+        ctx->coarse_bytes = need;
+    }
+    float *cz = (float *)ctx->coarse_buf, *cfill = cz + (size_t)ch * cwid;
+    if (int rc = hdem_blockmax_f32_dev(ctx, c.z, c.H, c.W, b, cz)) return rc;
+    float coarse_eps = 0.0f, coarse_add = 0.0f;
+    if (eps != 0.0f) {
+        // Gradient fill (eps > 0): a fine path that follows a chain of blocks makes at
+        // most b steps per block of the chain, every step adds eps -- in float32: at
+        // most eps + half an ulp of the value, and every value of the fill is below
+        // twice the largest |elevation| + what the path adds -- so the coarse raster
+        // filled with  eps_c = b (eps + ulp) + ulp  (the last ulp: its own additions
+        // round too) bounds a cell of block B by  level(B) + b (eps + ulp) + 2 ulp:
+        // up to b steps from the cell to the chain, one rounding of that sum.
+        int *amax = (int *)(cfill + (size_t)ch * cwid);
+        HDEM_HIP_CHECK(hipMemsetAsync(amax, 0, sizeof(int), ctx->stream));
+        hipLaunchKernelGGL(absmax_kernel, dim3(64), dim3(INIT_NT), 0, ctx->stream, cz,
+                           (size_t)ch * cwid, amax);
+        float top = 0.0f;
+        HDEM_HIP_CHECK(hipMemcpyAsync(&top, amax, sizeof(float), hipMemcpyDeviceToHost,
+                                      ctx->stream));
+        HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        // (values may climb above the highest block by the gradient itself: twice the
+        // top, and never less than 1, is a generous binade)
+        const float span = 2.0f * std::max(top, 1.0f) + (float)(ch + cwid) * b * eps;
+        const float ulp = std::nextafter(span, HDEM_INF) - span;
+        coarse_eps = (float)b * (eps + ulp) + ulp;
+        coarse_add = (float)b * (eps + ulp) + 2.0f * ulp;
+    }
+    // (elevations near FLT_MAX: the span overflows and there is no finite allowance --
+    // no bound to offer, the fill starts from +inf as it does without the switch)
+    if (!std::isfinite(coarse_add)) {
+        s->kind = START_INF;
+        return HDEM_OK;
+    }
+    const fill_call pre = {cz, ch, cwid, coarse_eps, 0,
+                           HDEM_FILL_INIT | HDEM_FILL_NO_VERIFY | HDEM_FILL_NO_COARSE,
+                           cfill, nullptr, nullptr, c.depth, FILL_PRESOLVE};
+    fill_outcome unused;
+    if (int rc = fill_run(ctx, kn, pre, &unused)) return rc;
+    s->coarse = cfill;
+    s->cw = cwid;
+    s->shift = kn.coarse_shift;
+    s->coarse_add = coarse_add;
+    return HDEM_OK;
+}
+
+// ---- phase 3: workspace, the counters deferred calls left in it, what is due -------------
+// Takes fill_stats_carry (a pre-solve leaves it alone), writes fill_last_* / fill_resumable /
+// fill_quiescent; reads fill_seam_words and fill_slice_us.
+int fill_workspace(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, const fill_start &s,
+                   fill_plan *p, fill_ws *ws)
+{
+    // (more than 8 of these one-wave workgroups per CU is a launch that cannot be resident
+    // at once)
+    bool keep_stats = ctx->fill_stats_carry && p->same && c.role != FILL_PRESOLVE;
+    if (int rc = ensure_ws(ctx, c.depth, c.H, c.W, p->max_rounds,
+                           ctx->num_cus * std::max(1, std::min(kn.wgs_per_cu, 16)), &p->resume, ws,
+                           &keep_stats))
         return rc;
-    if (!ctx->in_coarse_presolve) ctx->fill_stats_carry = false;
-    if (keep_stats && !(flags & HDEM_FILL_DEFER))
-        hipLaunchKernelGGL(fill_carry_sum_kernel, dim3(1), dim3(INIT_NT), 0, ctx->stream, ws.stats,
-                           ws.G, ws.error);
+    if (c.role != FILL_PRESOLVE) ctx->fill_stats_carry = false;
+    if (keep_stats && !(p->flags & HDEM_FILL_DEFER))
+        hipLaunchKernelGGL(fill_carry_sum_kernel, dim3(1), dim3(INIT_NT), 0, ctx->stream, ws->stats,
+                           ws->G, ws->error);
     // a deferred call (see the header): only as a resumed correcting solve
-    const bool defer = (flags & HDEM_FILL_DEFER) != 0;
-    HDEM_REQUIRE(!defer || (want_resume && use_async && ctx->fill_seam_words && !d8_request),
+    p->defer = (p->flags & HDEM_FILL_DEFER) != 0;
+    HDEM_REQUIRE(!p->defer || (p->want_resume && p->use_async && ctx->fill_seam_words && !c.d8),
                  HDEM_ERR_BAD_ARG,
                  "HDEM_FILL_DEFER needs WARM | RESUME, seam words and the asynchronous driver");
     // not resumable: fine if the last call on this problem left nothing queued (then the ACT
     // flags describe all there is to do), otherwise every tile is due again
-    if (want_resume && !resume && !(same && ctx->fill_quiescent))
-        flags &= ~(HDEM_FILL_ACT_TOP | HDEM_FILL_ACT_BOTTOM);
-    ctx->fill_last_h = H;
-    ctx->fill_last_w = W;
-    ctx->fill_last_z = z;
-    ctx->fill_last_out = w;
-    ctx->fill_resumable = ctx->fill_quiescent = false;   // until this call has ended well
-    hipStream_t st = ctx->stream;
-    const unsigned tile_blocks = (unsigned)std::max(1, (ws.ntiles + INIT_NT - 1) / INIT_NT);
-    const bool warm = (flags & HDEM_FILL_WARM) != 0;
+    if (p->want_resume && !p->resume && !(p->same && ctx->fill_quiescent))
+        p->flags &= ~(HDEM_FILL_ACT_TOP | HDEM_FILL_ACT_BOTTOM);
+    fill_remember(ctx, c);
+    p->warm = (p->flags & HDEM_FILL_WARM) != 0;
     // (from a coarse start every tile has something to lower: all of them are due)
-    int mode = warm ? (flags & (HDEM_FILL_ACT_TOP | HDEM_FILL_ACT_BOTTOM))
-                    : ((coarse || hub_lev) ? 0 : -1);
-    // resuming with no replaced ghost row: nothing to add to the worklist (mode 0 would
-    // mean "all tiles")
-    const bool seed_async = !(resume && mode == 0);
+    p->mode = p->warm ? (p->flags & (HDEM_FILL_ACT_TOP | HDEM_FILL_ACT_BOTTOM))
+                      : ((s.coarse || s.hub_lev) ? 0 : -1);
     // (a deferred call whose words are all clear has nothing to do -- unless every tile is due)
-    const int *idle_words = (defer && mode != 0) ? ctx->fill_seam_words : nullptr;
-    const int slice_us = (flags & HDEM_FILL_NO_VERIFY) ? ctx->fill_slice_us : 0;
-    int64_t pending = 0;
+    p->idle_words = (p->defer && p->mode != 0) ? ctx->fill_seam_words : nullptr;
+    p->slice_us = (p->flags & HDEM_FILL_NO_VERIFY) ? ctx->fill_slice_us : 0;
+    p->did_async = p->use_async && ws->ntiles > 0;
+    return HDEM_OK;
+}
 
-    if (hub_lev && !hub_given) {
+// ---- phase 4: the start values ----------------------------------------------------------
+// An own hub start fills its hub raster with fill_run one level down -- after this call's
+// workspace is set up, so in the next slot and the next hub_buf -- and at depth 0 writes
+// fill_last_* again, which the inner call set for its own raster.
+int fill_write_start(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, const fill_plan &p,
+                     const fill_start &s, const fill_ws &ws)
+{
+    const float *z = c.z;
+    float *w = c.w;
+    const int H = c.H, W = c.W;
+    if (s.kind == START_HUB_OWN) {
         {
             hdem_scoped_timer tm(ctx, HDEM_K_FILL_HUB, (int64_t)H * W);
-            hub_launch_dist(ctx, z, w, H, W, hubs);
-            hub_launch_edges(ctx, z, w, H, W, 0, hubs);
+            hub_launch_dist(ctx, kn, z, w, H, W, s.hubs);
+            hub_launch_edges(ctx, z, w, H, W, 0, s.hubs);
         }
         HDEM_HIP_CHECK(hipGetLastError());
-        // the hub raster is filled by this same function (in a workspace of its own)
-        const bool was_presolve = ctx->in_coarse_presolve;
-        ctx->in_coarse_presolve = true;
-        ctx->hub_depth = hub_depth + 1;
-        const int rc = hdem_sinkfill_f32_dev(ctx, hubs.cr, hubs.ch, hubs.cw, 0.0f, 0,
-                                             HDEM_FILL_INIT | HDEM_FILL_NO_VERIFY |
-                                                 HDEM_FILL_NO_COARSE,
-                                             hubs.lev, nullptr);
-        ctx->hub_depth = hub_depth;
-        ctx->in_coarse_presolve = was_presolve;
-        if (rc) return rc;
-        if (hub_depth == 0) {                      // (the inner call wrote these for its own raster)
-            ctx->fill_last_h = H;
-            ctx->fill_last_w = W;
-            ctx->fill_last_z = z;
-            ctx->fill_last_out = w;
-            ctx->fill_resumable = ctx->fill_quiescent = false;
-        }
+        const fill_call hub = {s.hubs.cr, s.hubs.ch, s.hubs.cw, 0.0f, 0,
+                               HDEM_FILL_INIT | HDEM_FILL_NO_VERIFY | HDEM_FILL_NO_COARSE,
+                               s.hubs.lev, nullptr, nullptr, c.depth + 1, FILL_PRESOLVE};
+        fill_outcome unused;
+        if (int rc = fill_run(ctx, kn, hub, &unused)) return rc;
+        if (c.depth == 0) fill_remember(ctx, c);
         // (no pass over the raster for max(d, level): every tile makes it on its first visit)
-    } else if (hub_lev) {
+    } else if (s.kind == START_HUB_GIVEN) {
         // the caller's levels: d is in w already (hdem_fill_hub_prepare_dev), the ghost rows are
         // the caller's start values
-    } else if (!warm) {
+    } else if (!p.warm) {
         hdem_scoped_timer tm(ctx, HDEM_K_FILL_INIT, (int64_t)H * W);
         const size_t n = (size_t)((H + INIT_ROWS - 1) / INIT_ROWS) * ((W + 3) / 4);
         hipLaunchKernelGGL(fill_init_kernel, dim3((unsigned)((n + INIT_NT - 1) / INIT_NT)),
-                           dim3(INIT_NT), 0, st, z, w, H, W, ws.tiles_x, ws.tile_key,
-                           flags & HDEM_FILL_GHOST_TOP, flags & HDEM_FILL_GHOST_BOTTOM,
-                           flags & HDEM_FILL_GHOST_GIVEN, coarse, coarse_cw, coarse_shift,
-                           row_map, coarse_add);
+                           dim3(INIT_NT), 0, ctx->stream, z, w, H, W, ws.tiles_x, ws.tile_key,
+                           p.flags & HDEM_FILL_GHOST_TOP, p.flags & HDEM_FILL_GHOST_BOTTOM,
+                           p.flags & HDEM_FILL_GHOST_GIVEN, s.coarse, s.cw, s.shift, s.row_map,
+                           s.coarse_add);
     }
-    int converged = ws.ntiles == 0 ? 1 : 0, round = 0, async_error = 0;
-    bool have_counts = false;          // head words + counters already on the host
-    bool d8_by_stream = false;         // the certifying stream wrote the codes (every cell)
-    const bool did_async = use_async && ws.ntiles > 0;
-    if (did_async) {
-        // ---- asynchronous phase: does (nearly) all of the work -------------------
-        if (seed_async)
-            hipLaunchKernelGGL(fill_seed_kernel, dim3(tile_blocks), dim3(INIT_NT), 0, st,
-                               ws.tile_key, ws.tiles_x, ws.tiles_y, H, mode, ws.G, ws.S, 1,
-                               ws.state, ws.prio, ws.pend, 0, ws.any, coarse, coarse_cw,
-                               coarse_shift, row_map, W, hub_lev, defer ? ctx->fill_seam_words : nullptr);
+    return HDEM_OK;
+}
+
+// ---- phase 5: the asynchronous launch, which does (nearly) all of the work ---------------
+int fill_launch_async(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, const fill_plan &p,
+                      const fill_start &s, const fill_ws &ws)
+{
+    hipStream_t st = ctx->stream;
+    if (p.did_async) {
+        // resuming with no replaced ghost row: nothing to add to the worklist (mode 0 would
+        // mean "all tiles")
+        if (!(p.resume && p.mode == 0))
+            hipLaunchKernelGGL(fill_seed_kernel, dim3(fill_tile_blocks(ws)), dim3(INIT_NT), 0, st,
+                               ws.tile_key, ws.tiles_x, ws.tiles_y, c.H, p.mode, ws.G, ws.S, 1,
+                               ws.state, ws.prio, ws.pend, 0, ws.any, s.coarse, s.cw, s.shift,
+                               s.row_map, c.W, s.hub_lev, p.defer ? ctx->fill_seam_words : nullptr);
         // wall-clock budget (100 MHz ticks): generous against the ~0.15 us per tile a
         // 16384^2 fill takes, small enough that a stuck launch costs a fraction of a second;
         // or the caller's time slice (soft: the launch just stops taking tiles)
-        long long budget = slice_us > 0 ? (long long)slice_us * 100ll
-                                        : 20000000ll + (long long)ws.ntiles * 200ll;
-        int soft = slice_us > 0;
-        // (tests: cut the asynchronous phase short so that the passes behind it have work)
+        long long budget = p.slice_us > 0 ? (long long)p.slice_us * 100ll
+                                          : 20000000ll + (long long)ws.ntiles * 200ll;
+        int soft = p.slice_us > 0;
         // (not the pre-solve of a start raster: that one is to run as it always does)
-        if (const char *tb = ctx->in_coarse_presolve ? nullptr : getenv("HDEM_FILL_TEST_BUDGET_US")) {
-            budget = atoll(tb) * 100ll;
+        if (c.role != FILL_PRESOLVE && kn.test_budget_us != NO_TEST_BUDGET) {
+            budget = kn.test_budget_us * 100ll;
             soft = 1;
         }
-        hdem_scoped_timer tm(ctx, async_id, 0);
-        if (eps != 0.0f)
-            hipLaunchKernelGGL((fill_async_kernel<true, 0>), dim3(ws.G), dim3(NT), 0, st, z, w, H,
-                               W, eps, ws.tiles_x, ws.tiles_y, ws.ntiles, ws.S, ws.state,
-                               ws.prio, ws.pend, ws.error, ws.stats, budget, soft, ws.flat, ws.zmax,
-                               hub_lev, ws.applied, idle_words);
-        else if (ctx->in_coarse_presolve)
-            hipLaunchKernelGGL((fill_async_kernel<false, 1>), dim3(ws.G), dim3(NT), 0, st, z, w,
-                               H, W, eps, ws.tiles_x, ws.tiles_y, ws.ntiles, ws.S, ws.state,
-                               ws.prio, ws.pend, ws.error, ws.stats, budget, soft, ws.flat, ws.zmax,
-                               hub_lev, ws.applied, idle_words);
-        else
-            hipLaunchKernelGGL((fill_async_kernel<false, 0>), dim3(ws.G), dim3(NT), 0, st, z, w,
-                               H, W, eps, ws.tiles_x, ws.tiles_y, ws.ntiles, ws.S, ws.state,
-                               ws.prio, ws.pend, ws.error, ws.stats, budget, soft, ws.flat, ws.zmax,
-                               hub_lev, ws.applied, idle_words);
+        hdem_scoped_timer tm(ctx, fill_async_id(c), 0);
+        auto kernel = &fill_async_kernel<true, 0>;        // (order: as in hub_launch_dist)
+        if (c.eps == 0.0f && c.role == FILL_PRESOLVE) kernel = &fill_async_kernel<false, 1>;
+        else if (c.eps == 0.0f) kernel = &fill_async_kernel<false, 0>;
+        hipLaunchKernelGGL(kernel, dim3(ws.G), dim3(NT), 0, st, c.z, c.w, c.H, c.W, c.eps,
+                           ws.tiles_x, ws.tiles_y, ws.ntiles, ws.S, ws.state, ws.prio, ws.pend,
+                           ws.error, ws.stats, budget, soft, ws.flat, ws.zmax, s.hub_lev, ws.applied,
+                           p.idle_words);
     }
-    if (did_async && eps == 0.0f) {
+    if (p.did_async && c.eps == 0.0f) {
         // tiles that ended the launch flat have only their edge lines in memory
         hdem_scoped_timer tm(ctx, HDEM_K_FILL_FLAT, 0);
-        hipLaunchKernelGGL(flat_store_kernel, dim3(ws.ntiles), dim3(NT), 0, st, w, H, W, ws.tiles_x,
-                           ws.ntiles, ws.flat, hub_lev, ws.applied, idle_words);
+        hipLaunchKernelGGL(flat_store_kernel, dim3(ws.ntiles), dim3(NT), 0, st, c.w, c.H, c.W,
+                           ws.tiles_x, ws.ntiles, ws.flat, s.hub_lev, ws.applied, p.idle_words);
     }
     HDEM_HIP_CHECK(hipGetLastError());
-    // ---- round-synchronous phase: certifies (or finishes) the fixed point --------
-    // behind the asynchronous phase every tile is checked once (mode 0 = all tiles);
-    // on its own it starts from the same seeds
-    bool verify = !(did_async && (flags & HDEM_FILL_NO_VERIFY));
-    // flow directions on request (hdem_sinkfill_d8_f32_dev): written by the certifying
-    // pass when that pass sees every tile, i.e. behind the asynchronous phase
-    uint8_t *d8 = d8_request;
-    // The coarse pre-solve needs no host round trip at all: whatever state its launch ends
-    // in -- even one cut short -- is an upper bound of the coarse fill, which is all the
-    // fine solve asks of it; its counters are only read when somebody is looking.
-    if (ctx->in_coarse_presolve && did_async && !verify && !trace && !stats) {
+    return HDEM_OK;
+}
+
+// The round driver: finishes (or, on its own, is) the solve.  Behind the asynchronous phase
+// every tile is checked once (mode 0 = all tiles); on its own it starts from the same seeds.
+int fill_settle_rounds(hdem_ctx *ctx, const fill_call &c, const fill_plan &p, const fill_ws &ws,
+                       fill_result *r)
+{
+    hipStream_t st = ctx->stream;
+    if (ws.ntiles > 0 && r->verify && !r->converged)
+        hipLaunchKernelGGL(fill_seed_kernel, dim3(fill_tile_blocks(ws)), dim3(INIT_NT), 0, st,
+                           ws.tile_key, ws.tiles_x, ws.tiles_y, c.H, p.did_async ? 0 : p.mode, ws.G,
+                           ws.S, 0, ws.state, ws.prio, ws.pend, (int)ST_ROUND0, ws.any, nullptr, 0,
+                           0, nullptr, c.W, nullptr, nullptr);
+    // rounds per host check: behind the asynchronous phase the first round is expected to
+    // find nothing, so only one more is queued with it (an empty launch costs ~9 us)
+    const int KB = p.did_async ? 2 : FILL_K;
+    const auto kernel = c.eps != 0.0f ? &fill_round_kernel<true> : &fill_round_kernel<false>;
+    while (ws.ntiles > 0 && r->verify && r->round < p.max_rounds && !r->converged) {
+        for (int k = 0; k < KB; ++k) {
+            const int rnd = r->round + k;
+            hdem_scoped_timer tm(ctx, HDEM_K_FILL_ROUND, 0);
+            hipLaunchKernelGGL(kernel, dim3(ws.G), dim3(NT), 0, st, c.z, c.w, c.H, c.W, c.eps,
+                               ws.tiles_x, ws.tiles_y, ws.ntiles, ws.S, ws.state, ST_ROUND0 + rnd,
+                               ws.any + rnd + 1, ws.stats, r->d8);
+        }
+        HDEM_HIP_CHECK(hipGetLastError());
+        HDEM_HIP_CHECK(hipMemcpyAsync(ctx->host_counts, ws.any + r->round, (KB + 1) * sizeof(int),
+                                      hipMemcpyDeviceToHost, st));
+        HDEM_HIP_CHECK(hipStreamSynchronize(st));
+        for (int k = 0; k < KB; ++k) {
+            if (ctx->host_counts[k] == 0) { r->converged = 1; break; }
+            ++r->round;
+        }
+        if (!r->converged && ctx->host_counts[KB] == 0) r->converged = 1;
+    }
+    return HDEM_OK;
+}
+
+// ---- phase 6: certify (or finish) the fixed point ---------------------------------------
+// The two ways out without a report write fill_resumable / fill_quiescent (a deferred call
+// fill_stats_carry too) and set r->ended.
+int fill_settle(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, const fill_plan &p,
+                const fill_ws &ws, fill_result *r)
+{
+    hipStream_t st = ctx->stream;
+    r->converged = ws.ntiles == 0 ? 1 : 0;
+    r->verify = !(p.did_async && (p.flags & HDEM_FILL_NO_VERIFY));
+    // The pre-solve of a start raster needs no host round trip at all: whatever state its
+    // launch ends in -- even one cut short -- is an upper bound of the coarse fill, which is all
+    // the fine solve asks of it; its counters are only read when somebody is looking.
+    if (c.role == FILL_PRESOLVE && p.did_async && !r->verify && !kn.trace && !c.stats) {
         ctx->fill_resumable = ctx->fill_quiescent = false;
+        r->ended = true;
         return HDEM_OK;
     }
-    if (defer && did_async && !verify) {
+    if (p.defer && p.did_async && !r->verify) {
         hipLaunchKernelGGL(fill_seam_busy_kernel, dim3(1), dim3(NT), 0, st, ws.pend, ws.error,
                            ctx->fill_seam_words);
         HDEM_HIP_CHECK(hipGetLastError());
-        if (stats) { *stats = hdem_fill_stats{}; stats->pending = -1; stats->tiles = ws.ntiles; stats->tile_h = stats->tile_w = FT; }
+        if (c.stats) {
+            *c.stats = hdem_fill_stats{};
+            c.stats->pending = -1;
+            c.stats->tiles = ws.ntiles;
+            c.stats->tile_h = c.stats->tile_w = FT;
+        }
         ctx->fill_stats_carry = true;
         ctx->fill_resumable = true;          // (the worklist is whatever the launch leaves)
         ctx->fill_quiescent = false;
+        r->ended = true;
         return HDEM_OK;
     }
-    if (!verify) {
+    if (!r->verify) {
         // trust the asynchronous phase unless it gave up; after a time slice, report how
         // many tiles are still queued (the worklist stays in the workspace for RESUME)
-        // (one wait for all of it: head words, counters and -- after a slice -- the shards of
-        // the pending count, which sit behind the counters' neighbours in the workspace)
-        HDEM_HIP_CHECK(hipMemcpyAsync(ctx->host_counts, ws.error,
-                                      (HEAD_INTS + stat_ints_of(ws)) * sizeof(int),
-                                      hipMemcpyDeviceToHost, st));
-        int *host_pend = ctx->host_counts + HEAD_INTS + stat_ints_of(ws);
-        if (slice_us > 0)
-            HDEM_HIP_CHECK(hipMemcpyAsync(host_pend, ws.pend, PEND_SHARDS * PEND_STRIDE * sizeof(int),
-                                          hipMemcpyDeviceToHost, st));
-        HDEM_HIP_CHECK(hipStreamSynchronize(st));
-        async_error = ctx->host_counts[0];
-        if (slice_us > 0)
-            for (int i = 0; i < PEND_SHARDS; ++i) pending += host_pend[i * PEND_STRIDE];
-        if (async_error) { verify = true; pending = 0; }
-        else { converged = pending == 0; have_counts = true; }
+        if (int rc = fill_read_counts(ctx, ws, p.slice_us > 0)) return rc;
+        const int *host_pend = ctx->host_counts + HEAD_INTS + stat_ints_of(ws);
+        if (p.slice_us > 0)
+            for (int i = 0; i < PEND_SHARDS; ++i) r->pending += host_pend[i * PEND_STRIDE];
+        if (ctx->host_counts[0]) { r->verify = true; r->pending = 0; }      // (it gave up)
+        else { r->converged = r->pending == 0; r->have_counts = true; }
     }
-    // (the pass must see every tile: behind the asynchronous phase, or a WARM round-driver
-    // call with all tiles due -- the verifying call of the row-block loop)
-    if (!(verify && (did_async || (warm && mode == 0)))) d8 = nullptr;
-    // Behind the asynchronous phase -- and in the verifying call of the row-block loop --
-    // the surface is normally final: certify it with one streaming pass (hdem_stencil.hip;
-    // it also writes the flow directions) and only fall back to certifying rounds of tile
-    // visits when that pass finds a cell to lower.
-    // (HDEM_FILL_CERTIFY_ROUNDS: always the rounds.)
-    const bool sees_all = did_async || (warm && mode == 0);      // (as for d8 above)
-    if (ws.ntiles > 0 && verify && sees_all && !getenv("HDEM_FILL_CERTIFY_ROUNDS")) {
+    // flow directions on request (hdem_sinkfill_d8_f32_dev): written by the certifying pass
+    // when that pass sees every tile: behind the asynchronous phase, or a WARM round-driver
+    // call with all tiles due -- the verifying call of the row-block loop
+    const bool sees_all = p.did_async || (p.warm && p.mode == 0);
+    r->d8 = (r->verify && sees_all) ? c.d8 : nullptr;
+    // There the surface is normally final: certify it with one streaming pass
+    // (hdem_stencil.hip; it also writes the flow directions) and only fall back to certifying
+    // rounds of tile visits when that pass finds a cell to lower.
+    if (ws.ntiles > 0 && r->verify && sees_all && !kn.certify_rounds) {
         int *flag = ws.error + 4;                          // (zeroed with the other head words)
         {
-            hdem_scoped_timer tm(ctx, HDEM_K_FILL_ROUND, (int64_t)H * W);
-            if (int rc = hdem_certify_d8_launch(ctx, z, w, H, W, eps, d8, flag)) return rc;
+            hdem_scoped_timer tm(ctx, HDEM_K_FILL_ROUND, (int64_t)c.H * c.W);
+            if (int rc = hdem_certify_d8_launch(ctx, c.z, c.w, c.H, c.W, c.eps, r->d8, flag)) return rc;
         }
         // one read-back for everything the host wants to know: the head words (budget flag,
         // partial residency, the certifying pass's flag) and the per-workgroup counters sit
         // next to each other.  Normally the flag is clear and this is the call's only wait.
-        HDEM_HIP_CHECK(hipMemcpyAsync(ctx->host_counts, ws.error, (HEAD_INTS + stat_ints_of(ws)) * sizeof(int),
-                                      hipMemcpyDeviceToHost, st));
-        HDEM_HIP_CHECK(hipStreamSynchronize(st));
-        if (ctx->host_counts[4] == 0) { converged = 1; have_counts = true; d8_by_stream = d8 != nullptr; }
-    }
-    if (ws.ntiles > 0 && verify && !converged)
-        hipLaunchKernelGGL(fill_seed_kernel, dim3(tile_blocks), dim3(INIT_NT), 0, st,
-                           ws.tile_key, ws.tiles_x, ws.tiles_y, H, did_async ? 0 : mode, ws.G,
-                           ws.S, 0, ws.state, ws.prio, ws.pend, (int)ST_ROUND0, ws.any, nullptr, 0,
-                           0, nullptr, W, nullptr, nullptr);
-    // rounds per host check: behind the asynchronous phase the first round is expected to
-    // find nothing, so only one more is queued with it (an empty launch costs ~9 us)
-    const int KB = did_async ? 2 : K;
-    while (ws.ntiles > 0 && verify && round < max_rounds && !converged) {
-        for (int k = 0; k < KB; ++k) {
-            const int r = round + k;
-            hdem_scoped_timer tm(ctx, HDEM_K_FILL_ROUND, 0);
-            if (eps != 0.0f)
-                hipLaunchKernelGGL(fill_round_kernel<true>, dim3(ws.G), dim3(NT), 0, st, z, w, H,
-                                   W, eps, ws.tiles_x, ws.tiles_y, ws.ntiles, ws.S, ws.state,
-                                   ST_ROUND0 + r, ws.any + r + 1, ws.stats, d8);
-            else
-                hipLaunchKernelGGL(fill_round_kernel<false>, dim3(ws.G), dim3(NT), 0, st, z, w,
-                                   H, W, eps, ws.tiles_x, ws.tiles_y, ws.ntiles, ws.S, ws.state,
-                                   ST_ROUND0 + r, ws.any + r + 1, ws.stats, d8);
+        if (int rc = fill_read_counts(ctx, ws, false)) return rc;
+        if (ctx->host_counts[4] == 0) {
+            r->converged = 1;
+            r->have_counts = true;
+            r->d8_by_stream = r->d8 != nullptr;
         }
-        HDEM_HIP_CHECK(hipGetLastError());
-        HDEM_HIP_CHECK(hipMemcpyAsync(ctx->host_counts, ws.any + round, (KB + 1) * sizeof(int),
-                                      hipMemcpyDeviceToHost, st));
-        HDEM_HIP_CHECK(hipStreamSynchronize(st));
-        for (int k = 0; k < KB; ++k) {
-            if (ctx->host_counts[k] == 0) { converged = 1; break; }
-            ++round;
-        }
-        if (!converged && ctx->host_counts[KB] == 0) converged = 1;
     }
-    // ---- statistics ----------------------------------------------------------------
-    const size_t stat_words = (size_t)ws.G * STAT_WORDS;
-    if (!have_counts) {
-        HDEM_HIP_CHECK(hipMemcpyAsync(ctx->host_counts, ws.error,
-                                      (HEAD_INTS + stat_ints_of(ws)) * sizeof(int),
-                                      hipMemcpyDeviceToHost, st));
-        HDEM_HIP_CHECK(hipStreamSynchronize(st));
-    }
+    return fill_settle_rounds(ctx, c, p, ws, r);
+}
+
+// ---- phase 7: counters, stats, profile units and the state the context keeps -------------
+// Writes fill_resumable / fill_quiescent; nothing else of the context but the profile.
+int fill_report(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, const fill_plan &p,
+                const fill_ws &ws, const fill_result &r, fill_outcome *out)
+{
+    if (!r.have_counts)
+        if (int rc = fill_read_counts(ctx, ws, false)) return rc;
     const unsigned long long *hs = (const unsigned long long *)(ctx->host_counts + HEAD_INTS);
-    async_error = ctx->host_counts[0];
-    const int partial_residency = ctx->host_counts[3];
+    const int async_error = ctx->host_counts[0], partial_residency = ctx->host_counts[3];
     unsigned long long tot[STAT_WORDS] = {};
-    for (size_t i = 0; i < stat_words; ++i) tot[i % STAT_WORDS] += hs[i];
+    for (size_t i = 0; i < (size_t)ws.G * STAT_WORDS; ++i) tot[i % STAT_WORDS] += hs[i];
     // (visits of flat tiles touch ~500 cells, not a window: counted apart, stats->visits_flat)
-    ctx->stats[async_id].units += (int64_t)(tot[0] - tot[6] - tot[STAT_FLAT]) * FT * FT;
+    ctx->stats[fill_async_id(c)].units += (int64_t)(tot[0] - tot[6] - tot[STAT_FLAT]) * FT * FT;
     ctx->stats[HDEM_K_FILL_ROUND].units += (int64_t)tot[6] * FT * FT;
-    if (trace)
+    if (kn.trace)
         fprintf(stderr, "sink fill: visits %llu iterations %llu unchanged %llu requeued %llu, "
                         "flat %llu, sync rounds %d, async_error %d; async busy %.3f ms idle %.3f ms per "
-                        "workgroup (G=%d)\n", tot[0], tot[1], tot[2], tot[3], tot[STAT_FLAT], round, async_error,
+                        "workgroup (G=%d)\n", tot[0], tot[1], tot[2], tot[3], tot[STAT_FLAT], r.round, async_error,
                 tot[4] / 1e5 / ws.G, tot[5] / 1e5 / ws.G, ws.G);
 #ifdef HDEM_VISIT_PROF
-    if (trace && tot[0])
+    if (kn.trace && tot[0])
         fprintf(stderr, "  per-visit us (sync visits): load %.2f check %.2f zt %.2f iterate %.2f "
                         "store %.2f wake-tests %.2f finish (per visit) %.2f (changed visits %llu)\n",
                 tot[9] / 100.0 / tot[0], tot[10] / 100.0 / tot[0],
@@ -2250,9 +2370,9 @@ extern "C" int hdem_sinkfill_f32_dev(hdem_ctx *ctx, const float *z, int H, int W
                 tot[13] / 100.0 / (tot[0] - tot[2] + 1), tot[14] / 100.0 / (tot[0] - tot[2] + 1),
                 tot[15] / 100.0 / tot[0], tot[0] - tot[2]);
 #endif
-    if (stats) {
-        stats->rounds = round;
-        stats->converged = converged;
+    if (hdem_fill_stats *stats = c.stats) {
+        stats->rounds = r.round;
+        stats->converged = r.converged;
         stats->tile_visits = (int64_t)tot[0];
         stats->tiles = ws.ntiles;
         stats->tile_h = FT;
@@ -2265,23 +2385,71 @@ extern "C" int hdem_sinkfill_f32_dev(hdem_ctx *ctx, const float *z, int H, int W
         stats->visits_unchanged = (int64_t)tot[2];
         stats->visits_requeued = (int64_t)tot[3];
         stats->round_visits = (int64_t)tot[6];
-    }
-    if (stats) {
-        stats->pending = pending;
+        stats->pending = r.pending;
         const unsigned long long *carry = (const unsigned long long *)(ctx->host_counts + CARRY_INT);
         stats->deferred_visits = (int64_t)carry[0];
         stats->deferred_unchanged = (int64_t)carry[1];
     }
-    if (!converged && pending == 0) {
-        hdem_set_error("sink fill did not converge in %d rounds", max_rounds);
+    if (!r.converged && r.pending == 0) {
+        hdem_set_error("sink fill did not converge in %d rounds", p.max_rounds);
         return HDEM_ERR_NOT_CONVERGED;
     }
-    ctx->fill_d8_done = d8 != nullptr && converged;
-    ctx->fill_d8_ring_done = ctx->fill_d8_done && d8_by_stream;
+    out->d8_done = r.d8 != nullptr && r.converged;
+    out->d8_ring_done = out->d8_done && r.d8_by_stream;
     // the round driver leaves round stamps in the state words: no worklist to resume
-    ctx->fill_resumable = did_async && !verify;
-    ctx->fill_quiescent = converged != 0;
+    ctx->fill_resumable = p.did_async && !r.verify;
+    ctx->fill_quiescent = r.converged != 0;
     return HDEM_OK;
+}
+
+int fill_run(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, fill_outcome *out)
+{
+    if (int rc = hdem_check_raster(c.z, c.w, c.H, c.W)) return rc;
+    HDEM_REQUIRE(c.z != c.w, HDEM_ERR_BAD_ARG, "sink fill cannot run in place");
+    HDEM_REQUIRE(c.eps >= 0.0f && c.eps == c.eps, HDEM_ERR_BAD_ARG, "eps must be >= 0, got %g",
+                 (double)c.eps);
+    HDEM_HIP_CHECK(hipSetDevice(ctx->device));
+    fill_plan p = {};
+    p.flags = c.flags;
+    p.max_rounds = ((c.max_rounds <= 0 ? 1 << 16 : c.max_rounds) + FILL_K - 1) / FILL_K * FILL_K;
+    // (64 rows of a window must be addressable with 32-bit byte offsets)
+    p.use_async = !(c.flags & HDEM_FILL_SYNC_ONLY) && !kn.sync &&
+                  (size_t)64 * c.W * sizeof(float) < (size_t)0xffffffffu;
+    // a worklist can only be resumed for the problem it was built for; when it cannot,
+    // every tile is due again (correct, just slower)
+    // (`same` is taken here: the fills of the start rasters write fill_last_* for theirs)
+    p.want_resume = (c.flags & HDEM_FILL_RESUME) && (c.flags & HDEM_FILL_WARM);
+    p.same = ctx->fill_last_h == c.H && ctx->fill_last_w == c.W && ctx->fill_last_z == c.z &&
+             ctx->fill_last_out == c.w;
+    p.resume = p.want_resume && p.use_async && p.same && ctx->fill_resumable;
+    if (p.want_resume) p.flags |= HDEM_FILL_NO_VERIFY;
+
+    fill_start start;
+    if (int rc = fill_choose_start(ctx, kn, c, p, &start)) return rc;
+    if (start.kind == START_COARSE_OWN)
+        if (int rc = fill_coarse_presolve(ctx, kn, c, &start)) return rc;
+    ctx->start_coarse = nullptr;                // a caller's coarse raster is used once
+    ctx->start_row_map = nullptr;
+    fill_ws ws;
+    if (int rc = fill_workspace(ctx, kn, c, start, &p, &ws)) return rc;
+    if (int rc = fill_write_start(ctx, kn, c, p, start, ws)) return rc;
+    if (int rc = fill_launch_async(ctx, kn, c, p, start, ws)) return rc;
+    fill_result r;
+    if (int rc = fill_settle(ctx, kn, c, p, ws, &r)) return rc;
+    if (r.ended) return HDEM_OK;
+    return fill_report(ctx, kn, c, p, ws, r, out);
+}
+
+}  // namespace
+
+extern "C" int hdem_sinkfill_f32_dev(hdem_ctx *ctx, const float *z, int H, int W, float eps,
+                                     int max_rounds, int flags, float *w,
+                                     hdem_fill_stats *stats)
+{
+    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
+    fill_outcome unused;
+    return fill_run(ctx, fill_read_knobs(),
+                    {z, H, W, eps, max_rounds, flags, w, stats, nullptr, 0, FILL_CALLER}, &unused);
 }
 
 // rows 0 and H-1, columns 0 and W-1 of a D8 raster: no direction on the raster ring
@@ -2298,13 +2466,13 @@ extern "C" int hdem_sinkfill_d8_f32_dev(hdem_ctx *ctx, const float *z, int H, in
 {
     HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
     if (int rc = hdem_check_raster(z, d8, H, W)) return rc;
-    ctx->fill_d8 = d8;
-    const int rc = hdem_sinkfill_f32_dev(ctx, z, H, W, eps, max_rounds, flags, w, stats);
-    ctx->fill_d8 = nullptr;
-    if (rc) return rc;
-    if (!ctx->fill_d8_done)              // no certifying pass over every tile: the plain kernel
+    fill_outcome got;
+    if (int rc = fill_run(ctx, fill_read_knobs(),
+                          {z, H, W, eps, max_rounds, flags, w, stats, d8, 0, FILL_CALLER}, &got))
+        return rc;
+    if (!got.d8_done)                   // no certifying pass over every tile: the plain kernel
         return hdem_d8_f32_dev(ctx, w, H, W, d8);
-    if (!ctx->fill_d8_ring_done)        // (tile visits write tile interiors only)
+    if (!got.d8_ring_done)              // (tile visits write tile interiors only)
         hipLaunchKernelGGL(d8_ring_kernel, dim3((std::max(H, W) + INIT_NT - 1) / INIT_NT),
                            dim3(INIT_NT), 0, ctx->stream, d8, H, W);
     HDEM_HIP_CHECK(hipGetLastError());
