@@ -529,8 +529,7 @@ class DeviceRaster:
     def from_host(cls, array, dtype=None, ctx=None):
         a = np.ascontiguousarray(array, dtype=dtype or (
             array.dtype if array.dtype in _DTYPES else np.float32))
-        if a.ndim != 2:
-            raise ValueError(f"expected a 2-D raster, got shape {a.shape}")
+        _need2d(a)
         r = cls.empty(a.shape, a.dtype, ctx)
         r.ctx.check(r.ctx.lib.hdem_memcpy_h2d(r.ctx.handle, r.ptr,
                                               a.ctypes.data, a.nbytes))
@@ -619,24 +618,149 @@ def _need(r, dtype):
         raise ValueError(f"expected a {np.dtype(dtype)} raster, got {r.dtype}")
 
 
-def d8_dev(z, out=None):
-    _need(z, np.float32)
-    c = z.ctx
-    with result_raster(out, z.shape, np.uint8, c) as out:
-        c.check(c.lib.hdem_d8_f32_dev(c.handle, z.ptr, z.shape[0], z.shape[1], out.ptr))
+def _need2d(r):
+    if len(r.shape) != 2:
+        raise ValueError(f"expected a 2-D raster, got shape {r.shape}")
+
+
+def _one_call_dev(name, x, dtype, out, out_dtype, *args, window=None):
+    """The device operators that are one C call ``name(ctx, x, H, W, *args, out)`` on a raster
+    of ``dtype``; a ``window`` is what the call may refuse."""
+    _need(x, dtype)
+    c = x.ctx
+    with result_raster(out, x.shape, out_dtype, c) as out:
+        c.check(getattr(c.lib, name)(c.handle, x.ptr, *x.shape, *args, out.ptr),
+                window=window, shape=x.shape)
     return out
+
+
+def d8_dev(z, out=None):
+    return _one_call_dev("hdem_d8_f32_dev", z, np.float32, out, np.uint8)
+
+
+# ---------------------------------------------------------------------------
+# the terrain operators: one body each, entered from a host side and a device side
+# ---------------------------------------------------------------------------
+
+class _Side:
+    """Who calls the body of a terrain operator: ``_HOST`` with NumPy arrays, for the C entry
+    point of the operator's name, or ``_DEVICE`` with device rasters, for its ``_dev`` twin."""
+
+    def __init__(self, device):
+        self.device, self.suffix = device, "_dev" if device else ""
+
+    def take(self, name, a, required=False, mask=False):
+        """The operand ``name``: a device raster as it is; a host operand as a contiguous
+        ``ndarray`` (a bool ``mask`` as bytes; ``None``, left out, unless ``required``)."""
+        if self.device or (a is None and not required):
+            return a
+        if not isinstance(a, np.ndarray):
+            raise ValueError(f"{name} is a NumPy array, got {type(a)}")
+        return np.ascontiguousarray(a.view(np.uint8) if mask and a.dtype == np.bool_ else a)
+
+    def address(self, a):
+        return None if a is None else a.ptr if self.device else a.ctypes.data
+
+    def context(self, raster):
+        return raster.ctx if self.device else context()
+
+    def result(self, stack, out, shape, dtype, ctx):
+        """Where a result goes: a :func:`host_empty` array, or a :func:`result_raster`
+        entered in the body's ``stack``, so that its ownership rule is the one rule."""
+        if not self.device:
+            return host_empty(shape, dtype)
+        return stack.enter_context(result_raster(out, shape, dtype, ctx))
+
+    def call(self, c, name, *args):
+        c.check(getattr(c.lib, name + self.suffix)(c.handle, *args))
+
+
+_HOST, _DEVICE = _Side(False), _Side(True)
+
+
+def _check(raster, dtype, says, what=None, flat=None, like=None):
+    """The one operand check of the terrain operators, in the words of the caller: ``raster``
+    (anything with ``dtype`` and ``shape``) ``says`` it is of ``dtype`` (``what``: another
+    name for that; ``None``: any), is 2-D for the operator that ``flat`` names, and has the
+    shape ``like = (noun, shape)``.  Returns its shape as a tuple."""
+    shape = tuple(raster.shape)
+    if dtype is not None and np.dtype(raster.dtype) != np.dtype(dtype):
+        raise ValueError(f"{says} {what or np.dtype(dtype)}, got {raster.dtype}")
+    if flat is not None and len(shape) != 2:
+        raise ValueError(f"{flat} a 2-D raster, got {len(shape)} dimensions")
+    if like is not None and shape != like[1]:
+        raise ValueError(f"{says} {shape}, {like[0]} {like[1]}")
+    return shape
+
+
+def _d8_codes(codes, operator):
+    _check(codes, np.uint8, f"{operator} takes", "uint8 D8 codes")
+    _need2d(codes)
+
+
+def _cellsize(cellsize):
+    """``cellsize`` as a float: a number, finite and positive."""
+    try:
+        cellsize = float(cellsize)
+    except (TypeError, ValueError):
+        raise ValueError(f"cellsize is a number, got {cellsize!r}") from None
+    if not np.isfinite(cellsize) or cellsize <= 0:
+        raise ValueError(f"cellsize must be finite and positive, got {cellsize}")
+    return cellsize
+
+
+def _flowacc(side, codes, out):
+    _d8_codes(codes, "flow accumulation")
+    codes = side.take("codes", codes)
+    c = side.context(codes)
+    st = FlowAccStats()
+    with contextlib.ExitStack() as stack:
+        out = side.result(stack, out, codes.shape, np.uint32, c)
+        side.call(c, "hdem_flowacc_u8", side.address(codes), *codes.shape, side.address(out),
+                  ctypes.byref(st))
+    return out, st.as_dict()
 
 
 def flowacc_dev(codes, out=None):
     """D8 flow accumulation of a uint8 code raster (``hdem_flowacc_u8_dev``): a uint32
     raster and the stats dict.  Synchronises (the call reads its validity counters)."""
-    _need(codes, np.uint8)
-    c = codes.ctx
-    st = FlowAccStats()
-    with result_raster(out, codes.shape, np.uint32, c) as out:
-        c.check(c.lib.hdem_flowacc_u8_dev(c.handle, codes.ptr, codes.shape[0], codes.shape[1],
-                                          out.ptr, ctypes.byref(st)))
-    return out, st.as_dict()
+    return _flowacc(_DEVICE, codes, out)
+
+
+def flowacc(codes, return_stats=False):
+    """D8 flow accumulation of a uint8 code raster (``hdem_flowacc_u8``): uint32."""
+    out, stats = _flowacc(_HOST, np.asarray(codes), None)
+    return (out, stats) if return_stats else out
+
+
+def _watershed(side, codes, seeds, compact, out):
+    _d8_codes(codes, "watershed labelling")
+    codes = side.take("codes", codes)
+    if seeds is not None:
+        _check(seeds, np.uint32, "seeds are", like=("the codes", tuple(codes.shape)))
+        if compact:
+            raise ValueError("compact labels number the outlets: no pour points with them")
+        seeds = side.take("seeds", seeds)
+    c = side.context(codes)
+    st = WatershedStats()
+    with contextlib.ExitStack() as stack:
+        out = side.result(stack, out, codes.shape, np.uint32, c)
+        # every cell may be an outlet: room for all, the first K come back -- in host memory
+        # (untouched pages cost nothing), or in a device scratch that K entries are read from
+        room = None
+        if compact:
+            room = np.empty(codes.size, np.uint32) if not side.device else \
+                stack.enter_context(DeviceRaster.empty(codes.shape, np.uint32, c))
+        side.call(c, "hdem_watershed_u8", side.address(codes), *codes.shape,
+                  side.address(seeds), WS_COMPACT if compact else 0, side.address(out),
+                  side.address(room), ctypes.byref(st))
+        outlets = None
+        if compact and not side.device:
+            outlets = room[:st.basins].copy()
+        elif compact:
+            first = DeviceRaster.wrap(room.ptr, (st.basins,), np.uint32, c)
+            outlets = first.to_host(np.empty(st.basins, np.uint32))
+    return out, outlets, st.as_dict()
 
 
 def watershed_dev(codes, seeds=None, compact=False, out=None):
@@ -644,40 +768,23 @@ def watershed_dev(codes, seeds=None, compact=False, out=None):
     raster, the ``outlets`` of the compact numbering (a host uint32 array of K flat indices,
     ``None`` otherwise) and the stats dict.  ``seeds``: a uint32 raster of pour points or
     ``None``.  Synchronises (the call reads its validity counters)."""
-    _need(codes, np.uint8)
-    if seeds is not None:
-        _need(seeds, np.uint32)
-        if tuple(seeds.shape) != tuple(codes.shape):
-            raise ValueError(f"seeds are {tuple(seeds.shape)}, the codes {tuple(codes.shape)}")
-        if compact:
-            raise ValueError("compact labels number the outlets: no pour points with them")
-    c = codes.ctx
-    st = WatershedStats()
-    with contextlib.ExitStack() as stack:
-        out = stack.enter_context(result_raster(out, codes.shape, np.uint32, c))
-        # every cell may be an outlet: room for all, the first K come back
-        room = stack.enter_context(DeviceRaster.empty(codes.shape, np.uint32, c)) \
-            if compact else None
-        c.check(c.lib.hdem_watershed_u8_dev(
-            c.handle, codes.ptr, codes.shape[0], codes.shape[1],
-            seeds.ptr if seeds is not None else None, WS_COMPACT if compact else 0, out.ptr,
-            room.ptr if compact else None, ctypes.byref(st)))
-        outlets = None
-        if compact:
-            first = DeviceRaster.wrap(room.ptr, (st.basins,), np.uint32, c)
-            outlets = first.to_host(np.empty(st.basins, np.uint32))
-    return out, outlets, st.as_dict()
+    return _watershed(_DEVICE, codes, seeds, compact, out)
+
+
+def watershed(codes, seeds=None, compact=False):
+    """D8 watershed labels of a uint8 code raster (``hdem_watershed_u8``): the uint32
+    labels, the ``outlets`` of the compact numbering (``None`` otherwise) and the stats
+    dict.  ``seeds``: a uint32 raster of pour points of the codes' shape, or ``None``."""
+    return _watershed(_HOST, np.asarray(codes), None if seeds is None else np.asarray(seeds),
+                      compact, None)
 
 
 def flowtrace_args(codes, streams, threshold, dem, cellsize, want):
     """The checks of the flow trace that need no device: ``codes``, ``streams`` and ``dem`` are
     anything with ``dtype`` and ``shape`` (NumPy arrays or device rasters).  Returns the
     stream kind, the threshold for the C call and ``want`` as a tuple in the ABI's order."""
-    if np.dtype(codes.dtype) != np.uint8:
-        raise ValueError(f"the flow trace takes uint8 D8 codes, got {codes.dtype}")
-    shape = tuple(codes.shape)
-    if len(shape) != 2:
-        raise ValueError(f"the flow trace takes a 2-D raster, got {len(shape)} dimensions")
+    shape = _check(codes, np.uint8, "the flow trace takes", "uint8 D8 codes",
+                   flat="the flow trace takes")
     if isinstance(want, str):
         want = (want,)
     names = [n for n, _ in FT_OUTPUTS]
@@ -693,8 +800,7 @@ def flowtrace_args(codes, streams, threshold, dem, cellsize, want):
             raise ValueError("a threshold needs the uint32 raster it applies to")
         threshold = 0
     else:
-        if tuple(streams.shape) != shape:
-            raise ValueError(f"streams are {tuple(streams.shape)}, the codes {shape}")
+        _check(streams, None, "streams are", like=("the codes", shape))
         if np.dtype(streams.dtype) == np.uint8:
             kind = FT_STREAMS_MASK_U8
             if threshold is not None:
@@ -712,19 +818,26 @@ def flowtrace_args(codes, streams, threshold, dem, cellsize, want):
             raise ValueError("streams are a uint8 mask or a uint32 raster with a threshold, "
                              f"got {streams.dtype}")
     if dem is not None:
-        if np.dtype(dem.dtype) != np.float32:
-            raise ValueError(f"the dem is float32, got {dem.dtype}")
-        if tuple(dem.shape) != shape:
-            raise ValueError(f"the dem is {tuple(dem.shape)}, the codes {shape}")
+        _check(dem, np.float32, "the dem is", like=("the codes", shape))
     elif "hand" in want:
         raise ValueError("hand needs the dem it is measured on")
-    try:
-        cellsize = float(cellsize)
-    except (TypeError, ValueError):
-        raise ValueError(f"cellsize is a number, got {cellsize!r}") from None
-    if not np.isfinite(cellsize) or cellsize <= 0:
-        raise ValueError(f"cellsize must be finite and positive, got {cellsize}")
+    _cellsize(cellsize)
     return kind, threshold, want
+
+
+def _flowtrace(side, codes, streams, threshold, dem, cellsize, want):
+    codes, streams, dem = (side.take("codes", codes), side.take("streams", streams, mask=True),
+                           side.take("dem", dem))
+    kind, threshold, want = flowtrace_args(codes, streams, threshold, dem, cellsize, want)
+    c = side.context(codes)
+    st = FlowTraceStats()
+    with contextlib.ExitStack() as stack:
+        outs = {name: side.result(stack, None, codes.shape, dtype, c)
+                for name, dtype in FT_OUTPUTS if name in want}
+        side.call(c, "hdem_flowtrace_u8", side.address(codes), *codes.shape,
+                  side.address(streams), kind, threshold, side.address(dem), float(cellsize),
+                  *[side.address(outs.get(name)) for name, _ in FT_OUTPUTS], 0, ctypes.byref(st))
+    return outs, st.as_dict()
 
 
 def flowtrace_dev(codes, streams=None, threshold=None, dem=None, cellsize=1.0,
@@ -735,35 +848,36 @@ def flowtrace_dev(codes, streams=None, threshold=None, dem=None, cellsize=1.0,
     ``>= threshold``).  ``want``: any of ``stop``, ``ncard``, ``ndiag`` (uint32), ``distance``,
     ``hand`` (float32; ``hand`` needs the float32 ``dem``).  Returns ``{name: DeviceRaster}``
     and the stats dict.  Synchronises (the call reads its validity counters)."""
-    kind, threshold, want = flowtrace_args(codes, streams, threshold, dem, cellsize, want)
-    c = codes.ctx
-    dtypes = dict(FT_OUTPUTS)
-    st = FlowTraceStats()
-    with contextlib.ExitStack() as stack:
-        outs = {name: stack.enter_context(result_raster(None, codes.shape, dtypes[name], c))
-                for name in want}
-        c.check(c.lib.hdem_flowtrace_u8_dev(
-            c.handle, codes.ptr, codes.shape[0], codes.shape[1],
-            streams.ptr if streams is not None else None, kind, threshold,
-            dem.ptr if dem is not None else None, float(cellsize),
-            *[outs[n].ptr if n in outs else None for n, _ in FT_OUTPUTS], 0, ctypes.byref(st)))
-    return outs, st.as_dict()
+    return _flowtrace(_DEVICE, codes, streams, threshold, dem, cellsize, want)
+
+
+def flowtrace(codes, streams=None, threshold=None, dem=None, cellsize=1.0, want=("distance",)):
+    """D8 flow trace of host arrays (``hdem_flowtrace_u8``; see :func:`flowtrace_dev`):
+    ``{name: ndarray}`` and the stats dict.  A bool ``streams`` array is a mask."""
+    return _flowtrace(_HOST, codes, streams, threshold, dem, cellsize, want)
 
 
 def resolve_flats_args(codes, dem):
     """The checks of the flat resolution that need no device: ``codes`` and ``dem`` are
     anything with ``dtype`` and ``shape`` (NumPy arrays or device rasters)."""
-    if np.dtype(codes.dtype) != np.uint8:
-        raise ValueError(f"flat resolution takes uint8 D8 codes, got {codes.dtype}")
-    shape = tuple(codes.shape)
-    if len(shape) != 2:
-        raise ValueError(f"flat resolution takes a 2-D raster, got {len(shape)} dimensions")
+    shape = _check(codes, np.uint8, "flat resolution takes", "uint8 D8 codes",
+                   flat="flat resolution takes")
     if dem is None:
         raise ValueError("flat resolution needs the dem the codes were made on")
-    if np.dtype(dem.dtype) != np.float32:
-        raise ValueError(f"the dem is float32, got {dem.dtype}")
-    if tuple(dem.shape) != shape:
-        raise ValueError(f"the dem is {tuple(dem.shape)}, the codes {shape}")
+    _check(dem, np.float32, "the dem is", like=("the codes", shape))
+
+
+def _resolve_flats(side, codes, dem, want_distance, out):
+    codes, dem = side.take("codes", codes), side.take("dem", dem)
+    resolve_flats_args(codes, dem)
+    c = side.context(codes)
+    st = ResolveFlatsStats()
+    with contextlib.ExitStack() as stack:
+        out = side.result(stack, out, codes.shape, np.uint8, c)
+        dist = side.result(stack, None, codes.shape, np.uint32, c) if want_distance else None
+        side.call(c, "hdem_resolve_flats_u8", side.address(codes), side.address(dem),
+                  *codes.shape, side.address(out), side.address(dist), 0, ctypes.byref(st))
+    return out, dist, st.as_dict()
 
 
 def resolve_flats_dev(codes, dem, want_distance=False, out=None):
@@ -771,38 +885,24 @@ def resolve_flats_dev(codes, dem, want_distance=False, out=None):
     codes with every flat cell pointed along a shortest equal-elevation path to where its
     flat drains, the uint32 distance raster (``None`` unless ``want_distance``) and the
     stats dict.  ``out`` may be ``codes`` itself.  Synchronises once per relaxation round."""
-    resolve_flats_args(codes, dem)
-    c = codes.ctx
-    st = ResolveFlatsStats()
-    with contextlib.ExitStack() as stack:
-        out = stack.enter_context(result_raster(out, codes.shape, np.uint8, c))
-        dist = stack.enter_context(result_raster(None, codes.shape, np.uint32, c)) \
-            if want_distance else None
-        c.check(c.lib.hdem_resolve_flats_u8_dev(
-            c.handle, codes.ptr, dem.ptr, codes.shape[0], codes.shape[1], out.ptr,
-            dist.ptr if dist is not None else None, 0, ctypes.byref(st)))
-    return out, dist, st.as_dict()
+    return _resolve_flats(_DEVICE, codes, dem, want_distance, out)
+
+
+def resolve_flats(codes, dem, want_distance=False):
+    """D8 directions across flats of host arrays (``hdem_resolve_flats_u8``; see
+    :func:`resolve_flats_dev`): the codes, the distances or ``None``, the stats dict."""
+    return _resolve_flats(_HOST, codes, dem, want_distance, None)
 
 
 def depressions_args(dem, filled, labels=None):
     """The checks of the depression operators that need no device: ``dem``, ``filled`` and
     ``labels`` are anything with ``dtype`` and ``shape`` (NumPy arrays or device rasters)."""
-    if np.dtype(filled.dtype) != np.float32:
-        raise ValueError(f"the filled raster is float32, got {filled.dtype}")
-    shape = tuple(filled.shape)
-    if len(shape) != 2:
-        raise ValueError(f"depressions take a 2-D raster, got {len(shape)} dimensions")
+    shape = _check(filled, np.float32, "the filled raster is", flat="depressions take")
     if dem is None:
         raise ValueError("depressions need the dem the filled raster is compared with")
-    if np.dtype(dem.dtype) != np.float32:
-        raise ValueError(f"the dem is float32, got {dem.dtype}")
-    if tuple(dem.shape) != shape:
-        raise ValueError(f"the dem is {tuple(dem.shape)}, the filled raster {shape}")
+    _check(dem, np.float32, "the dem is", like=("the filled raster", shape))
     if labels is not None:
-        if np.dtype(labels.dtype) != np.uint32:
-            raise ValueError(f"the labels are uint32, got {labels.dtype}")
-        if tuple(labels.shape) != shape:
-            raise ValueError(f"the labels are {tuple(labels.shape)}, the filled raster {shape}")
+        _check(labels, np.uint32, "the labels are", like=("the filled raster", shape))
 
 
 def _depression_count(count):
@@ -819,20 +919,66 @@ def depression_table_of(columns, cellsize=1.0):
     return table
 
 
+def _depressions(side, dem, filled, compact, out):
+    dem, filled = (side.take("dem", dem, required=True),
+                   side.take("filled", filled, required=True))
+    depressions_args(dem, filled)
+    c = side.context(filled)
+    st = DepressionsStats()
+    with contextlib.ExitStack() as stack:
+        out = side.result(stack, out, filled.shape, np.uint32, c)
+        side.call(c, "hdem_depressions_f32", side.address(dem), side.address(filled),
+                  *filled.shape, DEPR_COMPACT if compact else 0, side.address(out),
+                  ctypes.byref(st))
+    return out, st.as_dict()
+
+
 def depressions_dev(dem, filled, compact=True, out=None):
     """Depression labels of a ``dem`` / ``filled`` pair of float32 rasters
     (``hdem_depressions_f32_dev``): a uint32 raster and the stats dict, whose ``depressions``
     is K.  ``compact``: labels 1 ... K in scan order of the first cell (the numbering of
     ``scipy.ndimage.label``), else 1 + the flat index of the first cell.  Synchronises (the
     call reads K and its validity counters)."""
-    depressions_args(dem, filled)
-    c = filled.ctx
-    st = DepressionsStats()
-    with result_raster(out, filled.shape, np.uint32, c) as out:
-        c.check(c.lib.hdem_depressions_f32_dev(
-            c.handle, dem.ptr, filled.ptr, filled.shape[0], filled.shape[1],
-            DEPR_COMPACT if compact else 0, out.ptr, ctypes.byref(st)))
-    return out, st.as_dict()
+    return _depressions(_DEVICE, dem, filled, compact, out)
+
+
+def depressions(dem, filled, compact=True):
+    """Depression labels of host arrays (``hdem_depressions_f32``; see
+    :func:`depressions_dev`): the uint32 labels and the stats dict."""
+    return _depressions(_HOST, dem, filled, compact, None)
+
+
+def _depression_table(side, dem, filled, labels, count, cellsize):
+    dem, filled, labels = (side.take("dem", dem, required=True),
+                           side.take("filled", filled, required=True),
+                           side.take("labels", labels, required=True))
+    depressions_args(dem, filled, labels)
+    count = _depression_count(count)
+    if not side.device:     # five columns, written where they are (``offsets``: addresses)
+        columns = {name: np.empty(count, dtype) for name, dtype in DEPR_COLUMNS}
+        offsets = {name: column.ctypes.data for name, column in columns.items()}
+    else:
+        # one device block, downloaded and freed here: the uint64 column first, then the
+        # four 4-byte columns
+        order = sorted(DEPR_COLUMNS, key=lambda col: -np.dtype(col[1]).itemsize)
+        host = np.empty(sum(np.dtype(t).itemsize for _, t in order) * count, np.uint8)
+        columns, offsets, at = {}, {}, 0
+        for name, dtype in order:
+            n = np.dtype(dtype).itemsize * count
+            columns[name], offsets[name] = host[at:at + n].view(dtype), at
+            at += n
+    if count:
+        c = side.context(filled)
+        with contextlib.ExitStack() as stack:
+            if side.device:
+                block = stack.enter_context(DeviceRaster.empty(host.shape, np.uint8, c))
+                offsets = {name: block.ptr + at for name, at in offsets.items()}
+            side.call(c, "hdem_depression_table_f32", side.address(dem), side.address(filled),
+                      side.address(labels), *filled.shape, count,
+                      *[offsets[name] for name, _ in DEPR_COLUMNS])
+            if side.device:
+                block.to_host(host)
+    return depression_table_of({name: columns[name] for name, _ in DEPR_COLUMNS}, cellsize)
 
 
 def depression_table_dev(dem, filled, labels, count, cellsize=1.0):
@@ -840,24 +986,13 @@ def depression_table_dev(dem, filled, labels, count, cellsize=1.0):
     is K of the labelling): a dict of host arrays of length K, ``first``, ``area``, ``level``,
     ``max_depth``, ``volume_q20`` and ``volume``.  The columns are gathered in one device block
     that is downloaded and freed here; ``count == 0`` allocates and launches nothing."""
-    depressions_args(dem, filled, labels)
-    count = _depression_count(count)
-    c = filled.ctx
-    # one block: the uint64 column first, then the four 4-byte columns
-    order = sorted(DEPR_COLUMNS, key=lambda col: -np.dtype(col[1]).itemsize)
-    host = np.empty(sum(np.dtype(t).itemsize for _, t in order) * count, np.uint8)
-    columns, at = {}, 0
-    for name, dtype in order:
-        n = np.dtype(dtype).itemsize * count
-        columns[name] = (at, host[at:at + n].view(dtype))
-        at += n
-    if count:
-        with DeviceRaster.empty(host.shape, np.uint8, c) as block:
-            c.check(c.lib.hdem_depression_table_f32_dev(
-                c.handle, dem.ptr, filled.ptr, labels.ptr, filled.shape[0], filled.shape[1],
-                count, *[block.ptr + columns[name][0] for name, _ in DEPR_COLUMNS]))
-            block.to_host(host)
-    return depression_table_of({name: columns[name][1] for name, _ in DEPR_COLUMNS}, cellsize)
+    return _depression_table(_DEVICE, dem, filled, labels, count, cellsize)
+
+
+def depression_table(dem, filled, labels, count, cellsize=1.0):
+    """The depression table of host arrays (``hdem_depression_table_f32``; see
+    :func:`depression_table_dev`)."""
+    return _depression_table(_HOST, dem, filled, labels, count, cellsize)
 
 
 def sinkfill_dev(z, eps=0.0, max_rounds=0, out=None, flags=FILL_INIT):
@@ -1017,33 +1152,18 @@ def fourier_destripe_dev(dem, out=None, mask=None):
 def blanks_fourier_dev(q, found=None, window_size=55):
     """One BlanksFourier pass: returns the byte mask of cells above 4x their hollow
     mean; ``q`` is rewritten with those cells zeroed."""
-    _need(q, np.float32)
-    c = q.ctx
-    with result_raster(found, q.shape, np.uint8, c) as found:
-        c.check(c.lib.hdem_blanks_fourier_f32_dev(c.handle, q.ptr, q.shape[0], q.shape[1],
-                                                  int(window_size), found.ptr),
-                window=window_size, shape=q.shape)
-    return found
+    return _one_call_dev("hdem_blanks_fourier_f32_dev", q, np.float32, found, np.uint8,
+                         int(window_size), window=window_size)
 
 
 def isolated_points_dev(mask, window_size=3, out=None):
-    _need(mask, np.uint8)
-    c = mask.ctx
-    with result_raster(out, mask.shape, np.uint8, c) as out:
-        c.check(c.lib.hdem_isolated_points_u8_dev(c.handle, mask.ptr, mask.shape[0],
-                                                  mask.shape[1], int(window_size), out.ptr),
-                window=window_size, shape=mask.shape)
-    return out
+    return _one_call_dev("hdem_isolated_points_u8_dev", mask, np.uint8, out, np.uint8,
+                         int(window_size), window=window_size)
 
 
 def expand_dev(mask, window_size=13, out=None):
-    _need(mask, np.uint8)
-    c = mask.ctx
-    with result_raster(out, mask.shape, np.uint8, c) as out:
-        c.check(c.lib.hdem_expand_u8_dev(c.handle, mask.ptr, mask.shape[0], mask.shape[1],
-                                         int(window_size), out.ptr),
-                window=window_size, shape=mask.shape)
-    return out
+    return _one_call_dev("hdem_expand_u8_dev", mask, np.uint8, out, np.uint8,
+                         int(window_size), window=window_size)
 
 
 def fft2_dev(data, inverse=False):
@@ -1071,23 +1191,13 @@ def widened_to_host(raster, dtype):
 
 
 def correct_nan_dev(dem, out=None, window_size=3):
-    _need(dem, np.float32)
-    c = dem.ctx
-    with result_raster(out, dem.shape, np.float32, c) as out:
-        c.check(c.lib.hdem_correct_nan_f32_dev(c.handle, dem.ptr, dem.shape[0], dem.shape[1],
-                                               int(window_size), out.ptr),
-                window=window_size, shape=dem.shape)
-    return out
+    return _one_call_dev("hdem_correct_nan_f32_dev", dem, np.float32, out, np.float32,
+                         int(window_size), window=window_size)
 
 
 def majority_dev(img, window_size=11, out=None):
-    _need(img, np.float32)
-    c = img.ctx
-    with result_raster(out, img.shape, np.float32, c) as out:
-        c.check(c.lib.hdem_majority_f32_dev(c.handle, img.ptr, img.shape[0], img.shape[1],
-                                            int(window_size), out.ptr),
-                window=window_size, shape=img.shape)
-    return out
+    return _one_call_dev("hdem_majority_f32_dev", img, np.float32, out, np.float32,
+                         int(window_size), window=window_size)
 
 
 @contextlib.contextmanager
@@ -1151,13 +1261,8 @@ def grey_dilation_dev(img, size, out=None):
 
 
 def tidying_lagoons_dev(img, out=None):
-    _need(img, np.float32)
-    c = img.ctx
-    with result_raster(out, img.shape, np.float32, c) as out:
-        c.check(c.lib.hdem_tidying_lagoons_f32_dev(c.handle, img.ptr, img.shape[0],
-                                                   img.shape[1], out.ptr),
-                window=7, shape=img.shape)
-    return out
+    return _one_call_dev("hdem_tidying_lagoons_f32_dev", img, np.float32, out, np.float32,
+                         window=7)
 
 
 def lagoons_detection_dev(hsheds):
@@ -1199,13 +1304,8 @@ def boxmean3_dev(x, do_round=True, out=None):
 
 
 def quadratic_dev(dem, window_size=15, out=None):
-    _need(dem, np.float32)
-    c = dem.ctx
-    with result_raster(out, dem.shape, np.float32, c) as out:
-        c.check(c.lib.hdem_quadratic_f32_dev(c.handle, dem.ptr, dem.shape[0],
-                                             dem.shape[1], int(window_size), out.ptr),
-                window=window_size, shape=dem.shape)
-    return out
+    return _one_call_dev("hdem_quadratic_f32_dev", dem, np.float32, out, np.float32,
+                         int(window_size), window=window_size)
 
 
 def groves_dev(img, groves, window_size=15, threshold=1.5, iterations=3, out=None,
@@ -1234,8 +1334,7 @@ def groves_dev(img, groves, window_size=15, threshold=1.5, iterations=3, out=Non
 
 def _host2d(a, dtype):
     a = np.ascontiguousarray(a, dtype=dtype)
-    if a.ndim != 2:
-        raise ValueError(f"expected a 2-D raster, got shape {a.shape}")
+    _need2d(a)
     return a
 
 
@@ -1246,129 +1345,6 @@ def d8(z):
     c.check(c.lib.hdem_d8_f32(c.handle, z.ctypes.data, z.shape[0], z.shape[1],
                               out.ctypes.data))
     return out
-
-
-def flowacc(codes, return_stats=False):
-    """D8 flow accumulation of a uint8 code raster (``hdem_flowacc_u8``): uint32."""
-    codes = np.asarray(codes)
-    if codes.dtype != np.uint8:
-        raise ValueError(f"flow accumulation takes uint8 D8 codes, got {codes.dtype}")
-    c = context()
-    codes = _host2d(codes, np.uint8)
-    out = host_empty(codes.shape, np.uint32)
-    st = FlowAccStats()
-    c.check(c.lib.hdem_flowacc_u8(c.handle, codes.ctypes.data, codes.shape[0], codes.shape[1],
-                                  out.ctypes.data, ctypes.byref(st)))
-    return (out, st.as_dict()) if return_stats else out
-
-
-def watershed(codes, seeds=None, compact=False):
-    """D8 watershed labels of a uint8 code raster (``hdem_watershed_u8``): the uint32
-    labels, the ``outlets`` of the compact numbering (``None`` otherwise) and the stats
-    dict.  ``seeds``: a uint32 raster of pour points of the codes' shape, or ``None``."""
-    codes = np.asarray(codes)
-    if codes.dtype != np.uint8:
-        raise ValueError(f"watershed labelling takes uint8 D8 codes, got {codes.dtype}")
-    codes = _host2d(codes, np.uint8)
-    if seeds is not None:
-        seeds = np.asarray(seeds)
-        if seeds.dtype != np.uint32:
-            raise ValueError(f"seeds are uint32, got {seeds.dtype}")
-        if seeds.shape != codes.shape:
-            raise ValueError(f"seeds are {seeds.shape}, the codes {codes.shape}")
-        if compact:
-            raise ValueError("compact labels number the outlets: no pour points with them")
-        seeds = np.ascontiguousarray(seeds)
-    c = context()
-    out = host_empty(codes.shape, np.uint32)
-    # every cell may be an outlet: room for all (untouched pages cost nothing), K are written
-    room = np.empty(codes.size, np.uint32) if compact else None
-    st = WatershedStats()
-    c.check(c.lib.hdem_watershed_u8(
-        c.handle, codes.ctypes.data, codes.shape[0], codes.shape[1],
-        seeds.ctypes.data if seeds is not None else None, WS_COMPACT if compact else 0,
-        out.ctypes.data, room.ctypes.data if compact else None, ctypes.byref(st)))
-    outlets = room[:st.basins].copy() if compact else None
-    return out, outlets, st.as_dict()
-
-
-def flowtrace(codes, streams=None, threshold=None, dem=None, cellsize=1.0, want=("distance",)):
-    """D8 flow trace of host arrays (``hdem_flowtrace_u8``; see :func:`flowtrace_dev`):
-    ``{name: ndarray}`` and the stats dict.  A bool ``streams`` array is a mask."""
-    for name, a in (("codes", codes), ("streams", streams), ("dem", dem)):
-        if a is not None and not isinstance(a, np.ndarray):
-            raise ValueError(f"{name} is a NumPy array, got {type(a)}")
-    if streams is not None and streams.dtype == np.bool_:
-        streams = streams.view(np.uint8)
-    kind, threshold, want = flowtrace_args(codes, streams, threshold, dem, cellsize, want)
-    codes = np.ascontiguousarray(codes)
-    streams = np.ascontiguousarray(streams) if streams is not None else None
-    dem = np.ascontiguousarray(dem) if dem is not None else None
-    c = context()
-    dtypes = dict(FT_OUTPUTS)
-    outs = {name: host_empty(codes.shape, dtypes[name]) for name in want}
-    st = FlowTraceStats()
-    c.check(c.lib.hdem_flowtrace_u8(
-        c.handle, codes.ctypes.data, codes.shape[0], codes.shape[1],
-        streams.ctypes.data if streams is not None else None, kind, threshold,
-        dem.ctypes.data if dem is not None else None, float(cellsize),
-        *[outs[n].ctypes.data if n in outs else None for n, _ in FT_OUTPUTS], 0,
-        ctypes.byref(st)))
-    return outs, st.as_dict()
-
-
-def resolve_flats(codes, dem, want_distance=False):
-    """D8 directions across flats of host arrays (``hdem_resolve_flats_u8``; see
-    :func:`resolve_flats_dev`): the codes, the distances or ``None``, the stats dict."""
-    for name, a in (("codes", codes), ("dem", dem)):
-        if a is not None and not isinstance(a, np.ndarray):
-            raise ValueError(f"{name} is a NumPy array, got {type(a)}")
-    resolve_flats_args(codes, dem)
-    codes, dem = np.ascontiguousarray(codes), np.ascontiguousarray(dem)
-    c = context()
-    out = host_empty(codes.shape, np.uint8)
-    dist = host_empty(codes.shape, np.uint32) if want_distance else None
-    st = ResolveFlatsStats()
-    c.check(c.lib.hdem_resolve_flats_u8(
-        c.handle, codes.ctypes.data, dem.ctypes.data, codes.shape[0], codes.shape[1],
-        out.ctypes.data, dist.ctypes.data if want_distance else None, 0, ctypes.byref(st)))
-    return out, dist, st.as_dict()
-
-
-def depressions(dem, filled, compact=True):
-    """Depression labels of host arrays (``hdem_depressions_f32``; see
-    :func:`depressions_dev`): the uint32 labels and the stats dict."""
-    for name, a in (("dem", dem), ("filled", filled)):
-        if not isinstance(a, np.ndarray):
-            raise ValueError(f"{name} is a NumPy array, got {type(a)}")
-    depressions_args(dem, filled)
-    dem, filled = np.ascontiguousarray(dem), np.ascontiguousarray(filled)
-    c = context()
-    out = host_empty(filled.shape, np.uint32)
-    st = DepressionsStats()
-    c.check(c.lib.hdem_depressions_f32(
-        c.handle, dem.ctypes.data, filled.ctypes.data, filled.shape[0], filled.shape[1],
-        DEPR_COMPACT if compact else 0, out.ctypes.data, ctypes.byref(st)))
-    return out, st.as_dict()
-
-
-def depression_table(dem, filled, labels, count, cellsize=1.0):
-    """The depression table of host arrays (``hdem_depression_table_f32``; see
-    :func:`depression_table_dev`)."""
-    for name, a in (("dem", dem), ("filled", filled), ("labels", labels)):
-        if not isinstance(a, np.ndarray):
-            raise ValueError(f"{name} is a NumPy array, got {type(a)}")
-    depressions_args(dem, filled, labels)
-    count = _depression_count(count)
-    dem, filled, labels = (np.ascontiguousarray(a) for a in (dem, filled, labels))
-    columns = {name: np.empty(count, dtype) for name, dtype in DEPR_COLUMNS}
-    if count:
-        c = context()
-        c.check(c.lib.hdem_depression_table_f32(
-            c.handle, dem.ctypes.data, filled.ctypes.data, labels.ctypes.data,
-            filled.shape[0], filled.shape[1], count,
-            *[columns[name].ctypes.data for name, _ in DEPR_COLUMNS]))
-    return depression_table_of(columns, cellsize)
 
 
 def sinkfill(z, eps=0.0, max_rounds=0, return_stats=False):

@@ -61,10 +61,70 @@ from .. import backend
 def _check_raster(name, raster, dtype, takes):
     """``raster`` (a host array or a device raster) is 2-D and of ``dtype``, or a ValueError
     in the words of the operator ``name``, which ``takes`` that kind of raster."""
-    if raster.dtype != dtype:
-        raise ValueError(f"{name} takes {takes}, got {raster.dtype}")
-    if len(raster.shape) != 2:
-        raise ValueError(f"{name} takes a 2-D raster, got {len(raster.shape)} dimensions")
+    backend._check(raster, dtype, f"{name} takes", takes,  # pylint: disable=protected-access
+                   flat=f"{name} takes")
+
+
+class _Given:  # pylint: disable=too-few-public-methods
+    """An operand given at construction (a dem, streams, a seeds raster): ``value`` is a NumPy
+    array or a device raster (a bool mask as bytes) or ``None``, checked when it comes with a
+    ``name`` to be that, 2-D and of one of ``dtypes``; ``host()`` and ``device(ctx)`` give it
+    in the form an operator needs, whichever it was given in."""
+
+    def __init__(self, operand, name=None, dtypes=()):
+        if name is not None and operand is not None:
+            if not (isinstance(operand, np.ndarray) or backend.is_device_raster(operand)):
+                raise ValueError(f"{name} is a NumPy array or a DeviceRaster, got "
+                                 f"{type(operand)}")
+            if len(operand.shape) != 2:
+                raise ValueError(f"{name} is a 2-D raster, got {len(operand.shape)} dimensions")
+            if np.dtype(operand.dtype) not in [np.dtype(k) for k in dtypes]:
+                raise ValueError(f"{name} has dtype {' or '.join(np.dtype(k).name for k in dtypes)}"
+                                 f", got {operand.dtype}")
+        if isinstance(operand, np.ndarray) and operand.dtype == np.bool_:
+            operand = operand.view(np.uint8)
+        self.value = operand
+
+    def host(self):
+        return self.value.to_host() if backend.is_device_raster(self.value) else self.value
+
+    def device(self, ctx):
+        """For the length of a ``with``: see ``backend.on_device``."""
+        return backend.on_device(self.value, ctx=ctx)
+
+    def stand_in(self):
+        """A 1 x 1 array of the operand's dtype, for the checks that come before a shape."""
+        return None if self.value is None else np.empty((1, 1), self.value.dtype)
+
+
+def _fill_d8(stack, raster, fill, flats):
+    """Fill + D8 of a device raster in one call (the certifying pass of the fill writes the
+    flow directions) with the operands of ``fill``, the ``SinkFill`` member, then
+    ``ResolveFlats`` on the codes in place when ``flats`` says so: the filled raster and the
+    codes, both entered in ``stack``, and the resolution's stats (``None`` without one)."""
+    filled, codes, fill.stats = backend.sinkfill_d8_dev(raster, eps=fill.epsilon,
+                                                        max_rounds=fill.max_rounds)
+    stack.enter_context(filled)
+    stack.enter_context(codes)
+    resolve_stats = None
+    if flats == "resolve":
+        _, _, resolve_stats = backend.resolve_flats_dev(codes, filled, out=codes)
+    return filled, codes, resolve_stats
+
+
+def _through_device(operator, image, kept=()):
+    """``operator.apply_device`` for a host array: upload, apply, download the result and the
+    rasters the operator left in its attributes ``kept``, host arrays afterwards."""
+    with backend.DeviceRaster.from_host(image, dtype=np.float32) as z, \
+            contextlib.ExitStack() as stack:
+        result = stack.enter_context(operator.apply_device(z))
+        rasters = [stack.enter_context(getattr(operator, name)) for name in kept]
+        for name in kept:
+            setattr(operator, name, None)
+        out = result.to_host()
+        for name, raster in zip(kept, rasters):
+            setattr(operator, name, raster.to_host())
+    return out
 
 
 class QuadraticFilter(Filter):  # pylint: disable=too-few-public-methods
@@ -445,16 +505,14 @@ class Watersheds(Filter):  # pylint: disable=too-few-public-methods
     def apply(self, image_to_filter):
         super().apply(image_to_filter)
         _check_raster("Watersheds", image_to_filter, np.uint8, "uint8 D8 codes")
-        seeds = self._host_seeds(image_to_filter.shape)
-        if seeds is not None and not isinstance(seeds, np.ndarray):
-            seeds = seeds.to_host()
+        seeds = _Given(self._host_seeds(image_to_filter.shape)).host()
         out, self.outlets, self.stats = backend.watershed(image_to_filter, seeds,
                                                           self.labels == "compact")
         return out
 
     def apply_device(self, raster):
         _check_raster("Watersheds", raster, np.uint8, "uint8 D8 codes")
-        with backend.on_device(self._host_seeds(raster.shape), np.uint32, raster.ctx) as seeds:
+        with _Given(self._host_seeds(raster.shape)).device(raster.ctx) as seeds:
             out, self.outlets, self.stats = backend.watershed_dev(raster, seeds,
                                                                   self.labels == "compact")
         return out
@@ -468,47 +526,30 @@ class _FlowTrace(Filter):  # pylint: disable=too-few-public-methods
     auto_device = True      # device form == host form for a uint8 code raster
 
     def _set_operands(self, streams, threshold, dem, cellsize):
-        for name, operand, kinds in (("streams", streams, (np.bool_, np.uint8, np.uint32)),
-                                     ("dem", dem, (np.float32,))):
-            if operand is None:
-                continue
-            if not (isinstance(operand, np.ndarray) or backend.is_device_raster(operand)):
-                raise ValueError(f"{name} is a NumPy array or a DeviceRaster, got "
-                                 f"{type(operand)}")
-            if len(operand.shape) != 2:
-                raise ValueError(f"{name} is a 2-D raster, got {len(operand.shape)} dimensions")
-            if np.dtype(operand.dtype) not in [np.dtype(k) for k in kinds]:
-                raise ValueError(f"{name} has dtype {' or '.join(np.dtype(k).name for k in kinds)}"
-                                 f", got {operand.dtype}")
-        if isinstance(streams, np.ndarray) and streams.dtype == np.bool_:
-            streams = streams.view(np.uint8)
-        self.streams, self.threshold, self.dem, self.cellsize = streams, threshold, dem, cellsize
+        self.streams = _Given(streams, "streams", (np.bool_, np.uint8, np.uint32)).value
+        self.dem = _Given(dem, "dem", (np.float32,)).value
+        self.threshold, self.cellsize = threshold, cellsize
         self.stats = {}
-        # everything but the shapes: a 1 x 1 stand-in for the codes
-        self._check(np.zeros((1, 1), np.uint8), shapes=False)
+        # everything but the shapes: 1 x 1 stand-ins for the codes and the operands
+        backend.flowtrace_args(np.zeros((1, 1), np.uint8), _Given(self.streams).stand_in(),
+                               threshold, _Given(self.dem).stand_in(), cellsize, ("distance",))
 
-    def _check(self, codes, want=("distance",), shapes=True):
-        class Like:  # pylint: disable=too-few-public-methods
-            def __init__(self, operand):
-                self.dtype = operand.dtype
-                self.shape = operand.shape if shapes else codes.shape
-        return backend.flowtrace_args(
-            codes, None if self.streams is None else Like(self.streams), self.threshold,
-            None if self.dem is None else Like(self.dem), self.cellsize, want)
+    def _check(self, codes, want):
+        return backend.flowtrace_args(codes, self.streams, self.threshold, self.dem,
+                                      self.cellsize, want)
 
     def _trace(self, image_to_filter, want):
         Filter.apply(self, image_to_filter)
         self._check(image_to_filter, want)
-        operands = [o.to_host() if backend.is_device_raster(o) else o
-                    for o in (self.streams, self.dem)]
-        outs, self.stats = backend.flowtrace(image_to_filter, operands[0], self.threshold,
-                                             operands[1], self.cellsize, want)
+        outs, self.stats = backend.flowtrace(
+            image_to_filter, _Given(self.streams).host(), self.threshold,
+            _Given(self.dem).host(), self.cellsize, want)
         return outs
 
     def _trace_device(self, raster, want):
         self._check(raster, want)
-        with backend.on_device(self.streams, ctx=raster.ctx) as streams, \
-                backend.on_device(self.dem, ctx=raster.ctx) as dem:
+        with _Given(self.streams).device(raster.ctx) as streams, \
+                _Given(self.dem).device(raster.ctx) as dem:
             outs, self.stats = backend.flowtrace_dev(raster, streams, self.threshold, dem,
                                                      self.cellsize, want)
         return outs
@@ -635,13 +676,7 @@ class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods
     def __init__(self, *, dem, keep_partial_results=False):
         if dem is None:
             raise ValueError("ResolveFlats needs the dem the codes were made on")
-        if not (isinstance(dem, np.ndarray) or backend.is_device_raster(dem)):
-            raise ValueError(f"dem is a NumPy array or a DeviceRaster, got {type(dem)}")
-        if len(dem.shape) != 2:
-            raise ValueError(f"dem is a 2-D raster, got {len(dem.shape)} dimensions")
-        if np.dtype(dem.dtype) != np.float32:
-            raise ValueError(f"dem has dtype float32, got {dem.dtype}")
-        self.dem = dem
+        self.dem = _Given(dem, "dem", (np.float32,)).value
         self.keep_partial_results = keep_partial_results
         self.stats = {}
         self.distance = None
@@ -649,27 +684,16 @@ class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
         backend.resolve_flats_args(image_to_filter, self.dem)
-        dem = self.dem.to_host() if backend.is_device_raster(self.dem) else self.dem
         out, self.distance, self.stats = backend.resolve_flats(
-            image_to_filter, dem, self.keep_partial_results)
+            image_to_filter, _Given(self.dem).host(), self.keep_partial_results)
         return out
 
     def apply_device(self, raster):
         backend.resolve_flats_args(raster, self.dem)
-        with backend.on_device(self.dem, np.float32, raster.ctx) as dem:
+        with _Given(self.dem).device(raster.ctx) as dem:
             out, self.distance, self.stats = backend.resolve_flats_dev(
                 raster, dem, self.keep_partial_results)
         return out
-
-
-def _check_cellsize(cellsize):
-    try:
-        cellsize = float(cellsize)
-    except (TypeError, ValueError):
-        raise ValueError(f"cellsize is a number, got {cellsize!r}") from None
-    if not np.isfinite(cellsize) or cellsize <= 0:
-        raise ValueError(f"cellsize must be finite and positive, got {cellsize}")
-    return cellsize
 
 
 class Depressions(Filter):  # pylint: disable=too-few-public-methods
@@ -713,12 +737,7 @@ class Depressions(Filter):  # pylint: disable=too-few-public-methods
     def __init__(self, *, dem, labels="compact", table=False, cellsize=1.0):
         if dem is None:
             raise ValueError("Depressions needs the dem the filled raster is compared with")
-        if not (isinstance(dem, np.ndarray) or backend.is_device_raster(dem)):
-            raise ValueError(f"dem is a NumPy array or a DeviceRaster, got {type(dem)}")
-        if len(dem.shape) != 2:
-            raise ValueError(f"dem is a 2-D raster, got {len(dem.shape)} dimensions")
-        if np.dtype(dem.dtype) != np.float32:
-            raise ValueError(f"dem has dtype float32, got {dem.dtype}")
+        dem = _Given(dem, "dem", (np.float32,)).value
         if labels not in ("first", "compact"):
             raise ValueError(f"labels is 'first' or 'compact', got {labels!r}")
         if table and labels != "compact":
@@ -727,7 +746,7 @@ class Depressions(Filter):  # pylint: disable=too-few-public-methods
         self.dem = dem
         self.labels = labels
         self.want_table = bool(table)
-        self.cellsize = _check_cellsize(cellsize)
+        self.cellsize = backend._cellsize(cellsize)  # pylint: disable=protected-access
         self.stats = {}
         self.count = None
         self.table = None
@@ -735,7 +754,7 @@ class Depressions(Filter):  # pylint: disable=too-few-public-methods
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
         backend.depressions_args(self.dem, image_to_filter)
-        dem = self.dem.to_host() if backend.is_device_raster(self.dem) else self.dem
+        dem = _Given(self.dem).host()
         self.table = None
         out, self.stats = backend.depressions(dem, image_to_filter, self.labels == "compact")
         self.count = self.stats["depressions"]
@@ -747,7 +766,7 @@ class Depressions(Filter):  # pylint: disable=too-few-public-methods
     def apply_device(self, raster):
         backend.depressions_args(self.dem, raster)
         self.table = None
-        with backend.on_device(self.dem, np.float32, raster.ctx) as dem, \
+        with _Given(self.dem).device(raster.ctx) as dem, \
                 backend.result_raster(None, raster.shape, np.uint32, raster.ctx) as out:
             _, self.stats = backend.depressions_dev(dem, raster, self.labels == "compact",
                                                     out=out)
@@ -775,19 +794,14 @@ class DepressionInventory(Filter):  # pylint: disable=too-few-public-methods
             raise ValueError(f"epsilon is a number, got {epsilon!r}") from None
         if not np.isfinite(self.epsilon) or self.epsilon < 0:
             raise ValueError(f"epsilon must be finite and not negative, got {epsilon}")
-        self.cellsize = _check_cellsize(cellsize)
+        self.cellsize = backend._cellsize(cellsize)  # pylint: disable=protected-access
         self.filled = self.table = self.count = None
         self.stats, self.fill_stats = {}, {}
 
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
         _check_raster("DepressionInventory", image_to_filter, np.float32, "a float32 DEM")
-        with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z, \
-                self.apply_device(z) as labels, self.filled as filled:
-            self.filled = None
-            out = labels.to_host()
-            self.filled = filled.to_host()
-        return out
+        return _through_device(self, image_to_filter, ("filled",))
 
     def apply_device(self, raster):
         _check_raster("DepressionInventory", raster, np.float32, "a float32 DEM")
@@ -829,16 +843,11 @@ class HydroConditioning(ComposedFilter):  # pylint: disable=too-few-public-metho
 
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
-        fill = self.filters[0]
         with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z, \
                 contextlib.ExitStack() as stack:
-            # one call: the certifying pass of the fill writes the flow directions
-            filled, codes, fill.stats = backend.sinkfill_d8_dev(
-                z, eps=fill.epsilon, max_rounds=fill.max_rounds)
-            stack.enter_context(filled)
-            stack.enter_context(codes)
-            if self.flats == "resolve":
-                _, _, self.resolve_stats = backend.resolve_flats_dev(codes, filled, out=codes)
+            filled, codes, resolve_stats = _fill_d8(stack, z, self.filters[0], self.flats)
+            if resolve_stats is not None:
+                self.resolve_stats = resolve_stats
             self.filled = filled.to_host()
             return codes.to_host()
 
@@ -942,29 +951,16 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
     def apply(self, image_to_filter):
         Filter.apply(self, image_to_filter)
         _check_raster("DemToHAND", image_to_filter, np.float32, "a float32 DEM")
-        with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z, \
-                contextlib.ExitStack() as stack:
-            hand = stack.enter_context(self.apply_device(z))
-            names = ("filled", "codes", "accumulation", "distance") \
-                if self.keep_partial_results else ()
-            kept = [stack.enter_context(getattr(self, name)) for name in names]
-            out = hand.to_host()
-            for name, raster in zip(names, kept):
-                setattr(self, name, raster.to_host())
-        return out
+        return _through_device(self, image_to_filter,
+                               ("filled", "codes", "accumulation", "distance")
+                               if self.keep_partial_results else ())
 
     def apply_device(self, raster):
         _check_raster("DemToHAND", raster, np.float32, "a float32 DEM")
         fill, _, accumulate = self.filters
         self.filled = self.codes = self.accumulation = self.distance = None
         with contextlib.ExitStack() as stack:
-            filled, codes, fill.stats = backend.sinkfill_d8_dev(
-                raster, eps=fill.epsilon, max_rounds=fill.max_rounds)
-            stack.enter_context(filled)
-            stack.enter_context(codes)
-            resolve_stats = None
-            if self.flats == "resolve":
-                _, _, resolve_stats = backend.resolve_flats_dev(codes, filled, out=codes)
+            filled, codes, resolve_stats = _fill_d8(stack, raster, fill, self.flats)
             acc, accumulate.stats = backend.flowacc_dev(codes)
             stack.enter_context(acc)
             trace = HeightAboveDrainage(dem=filled, streams=acc, threshold=self.threshold,
