@@ -22,7 +22,8 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      GrovesCorrection, GrovesCorrectionsIter,
                                      PostProcessingFinal, SinkFill,
                                      D8FlowDirection, FlowAccumulation, Watersheds,
-                                     FlowDistance, HeightAboveDrainage, ResolveFlats,
+                                     FlowDistance, HeightAboveDrainage, UpstreamFlowLength,
+                                     ResolveFlats,
                                      Depressions, DepressionInventory,
                                      HydroConditioning, DemToHAND,
                                      ExpandFilter, IsolatedPoints, BlanksFourier,

@@ -132,6 +132,15 @@ class DepressionsStats(_SizedStats):
         return fields
 
 
+class _UpstreamStats(_SizedStats):
+    """``hdem_upstream_stats`` (the binding is hydrodem_amd/upstream.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_hops", ctypes.c_int32),
+                ("exits", ctypes.c_int64), ("heads", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_tile", ctypes.c_float), ("ms_forest", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
 # columns of the depression table, in the order of the C ABI's pointers
 DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
@@ -230,6 +239,10 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp],
     "hdem_depression_table_f32_dev": [_vp, _vp, _vp, _vp, _i, _i, _c.c_int64,
                                       _vp, _vp, _vp, _vp, _vp],
+    "hdem_upstream_u8": [_vp, _vp, _i, _i, _c.c_double, _vp, _vp, _vp, _i,
+                         _c.POINTER(_UpstreamStats)],
+    "hdem_upstream_u8_dev": [_vp, _vp, _i, _i, _c.c_double, _vp, _vp, _vp, _i,
+                             _c.POINTER(_UpstreamStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

@@ -25,7 +25,8 @@ unchanged when ``filters`` resolves here.
 
 New operators (the reference has neither): ``SinkFill``,
 ``D8FlowDirection``, ``ResolveFlats``, ``FlowAccumulation``, ``Watersheds``, ``FlowDistance``,
-``HeightAboveDrainage`` and the chain ``DemToHAND``, shaped like every other ``Filter``.
+``HeightAboveDrainage``, ``UpstreamFlowLength`` and the chain ``DemToHAND``, shaped like every
+other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -56,6 +57,7 @@ from .extension_filters import (BitwiseXOR, BinaryErosion, Around,  # noqa: F401
 from ..sliding_window import (SlidingWindow, CircularWindow,  # noqa: F401
                               NoCenterWindow, IgnoreBorderInnerSliding)
 from .. import backend
+from .. import upstream as _upstream
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -629,6 +631,58 @@ class HeightAboveDrainage(_FlowTrace):  # pylint: disable=too-few-public-methods
 
     def apply_device(self, raster):
         return self._keep(self._trace_device(raster, self._want()))
+
+
+class UpstreamFlowLength(Filter):  # pylint: disable=too-few-public-methods
+    """Longest upstream D8 flow length (new operator).  Input: a uint8 H x W raster of ESRI D8
+    codes exactly as ``FlowAccumulation`` takes them.  Returns float32: the length of the
+    longest D8 path that ends in the cell, ``ncard * cellsize + ndiag * cellsize * sqrt(2)``
+    evaluated in float64 and rounded once (``FlowDistance``'s formula), 0 for a cell nothing
+    drains into.  ``(ncard, ndiag)``, the cardinal and diagonal steps of that path, solve
+    ``up(c) = max(up(d) + step(d))`` over the neighbours ``d`` whose code points at ``c``,
+    where pairs are ordered by ``ncard + ndiag * sqrt(2)`` decided exactly, in integers: two
+    different pairs never tie, and no rounded length is ever compared.
+
+    With ``keep_partial_results=True`` the same call also leaves ``ncard`` and ``ndiag``
+    (uint32) -- host arrays after ``apply``, device rasters (the caller's to free) after
+    ``apply_device``; otherwise both are ``None``.
+
+    ``ValueError`` for a dtype other than uint8, a raster that is not 2-D, a ``cellsize`` that
+    is not finite and positive (all before the device is touched), a byte that is not a D8
+    code, codes that form a cycle and more than 2^32 - 1 cells.  Exact, identical from run to
+    run.
+
+    Attributes
+    ----------
+    stats : dict
+        heads (cells without a donor), exits (nodes of the exit forest), max_hops (tile
+        crossings of the longest forest walk), tile_h / tile_w of the last call; phase times
+        when profiling is on.
+    """
+
+    auto_device = True      # device form == host form for a uint8 code raster
+
+    def __init__(self, *, cellsize=1.0, keep_partial_results=False):
+        self.cellsize = backend._cellsize(cellsize)  # pylint: disable=protected-access
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.ncard = self.ndiag = None
+
+    def _want(self):
+        return ("ncard", "ndiag", "length") if self.keep_partial_results else ("length",)
+
+    def _keep(self, outs):
+        self.ncard, self.ndiag = outs.get("ncard"), outs.get("ndiag")
+        return outs["length"]
+
+    def apply(self, image_to_filter):
+        super().apply(image_to_filter)
+        outs, self.stats = _upstream.upstream(image_to_filter, self.cellsize, self._want())
+        return self._keep(outs)
+
+    def apply_device(self, raster):
+        outs, self.stats = _upstream.upstream_dev(raster, self.cellsize, self._want())
+        return self._keep(outs)
 
 
 class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods

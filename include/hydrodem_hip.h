@@ -662,6 +662,55 @@ int hdem_depression_table_f32_dev(hdem_ctx *ctx, const float *dem, const float *
                                   uint32_t *first, uint32_t *area, float *level,
                                   float *max_depth, uint64_t *volume_q20);  /* device pointers */
 
+/* ---- A10  UpstreamFlowLength.apply  (new operator: longest upstream D8 flow length) --
+ * d8: uint8 ESRI codes exactly as hdem_flowacc_u8 takes them (0, or a code pointing outside
+ * the raster, is terminal; any byte that is not a code is invalid).
+ * A donor of c is a neighbour whose code points at c.  For every cell
+ *   up(c) = (0, 0)                                   if c has no donor
+ *   up(c) = max over donors d of  up(d) + step(d)    otherwise
+ *   step(d) = (1, 0) for E, S, W, N;  (0, 1) for SE, SW, NW, NE
+ * the (cardinal, diagonal) steps of the longest D8 path that ends in c.  Pairs (ncard, ndiag)
+ * are ordered by the real number ncard + ndiag * sqrt(2), and that order is decided exactly,
+ * in integers: with da = a1 - a2 and db = b1 - b2, both >= 0: greater unless both are 0; both
+ * <= 0: not greater; mixed signs: da^2 against 2 db^2.  sqrt(2) is irrational, so two
+ * different pairs never tie, and no float key is ever compared ((8119, 0) and (0, 5741) have
+ * the same float32 length).
+ * Outputs, all H x W, each may be NULL (not wanted), at least one must not be:
+ *   ncard     uint32   the components of up(c)
+ *   ndiag     uint32
+ *   length    float32  (float)((double)ncard * cellsize + (double)ndiag * (cellsize * sqrt(2.0))),
+ *                      one rounding per operation, no fused multiply-add: hdem_flowtrace_u8's
+ *                      distance formula
+ * cellsize must be finite and > 0.  flags must be 0.
+ * Exact integers, identical from run to run and independent of the schedule.
+ * HDEM_ERR_BAD_ARG, in bounded time, for an invalid byte, for codes that form a cycle
+ * ("N cells never drain"), for the argument combinations excluded above and -- before any
+ * allocation or launch -- for H * W > 2^32 - 1.  Every retry loop carries a cap;
+ * HDEM_ERR_NOT_CONVERGED if one is ever reached.  On error the contents of the outputs are
+ * unspecified.
+ * Workspace: 36 B per tile-perimeter slot, about 2.2 B per cell, from the context's arena.
+ * The _dev form synchronises the context's stream once to read its counters.  stats may be
+ * NULL; otherwise the caller sets stats->struct_size = sizeof(hdem_upstream_stats) first (48
+ * bytes in this version; a shorter struct is filled as far as it goes).  The three phase times
+ * are filled only while profiling is on (hdem_profile_enable); the call has no kernel id. */
+typedef struct hdem_upstream_stats {
+    uint32_t struct_size;   /* in: sizeof(hdem_upstream_stats), set by the caller           */
+    int32_t max_hops;       /* tile crossings of the longest walk over the exit forest      */
+    int64_t exits;          /* cells that drain into another tile: nodes of the exit forest */
+    int64_t heads;          /* cells without a donor                                        */
+    int32_t tile_h, tile_w;
+    float ms_tile;          /* phase A: in-tile walks, perimeter paths (HIP events; profiling) */
+    float ms_forest;        /* phase B: the exit forest                                     */
+    float ms_final;         /* phase C: seeded in-tile walks, outputs written               */
+    int32_t reserved;       /* 0                                                            */
+} hdem_upstream_stats;      /* sizeof == 48 */
+int hdem_upstream_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, double cellsize,
+                     uint32_t *ncard, uint32_t *ndiag, float *length, int flags,
+                     hdem_upstream_stats *stats);        /* host pointers, synchronous */
+int hdem_upstream_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, double cellsize,
+                         uint32_t *ncard, uint32_t *ndiag, float *length, int flags,
+                         hdem_upstream_stats *stats);    /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
