@@ -23,7 +23,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      PostProcessingFinal, SinkFill,
                                      D8FlowDirection, FlowAccumulation, Watersheds,
                                      FlowDistance, HeightAboveDrainage, UpstreamFlowLength,
-                                     ResolveFlats,
+                                     StreamOrder, DemToStreamOrder, ResolveFlats,
                                      Depressions, DepressionInventory,
                                      HydroConditioning, DemToHAND,
                                      ExpandFilter, IsolatedPoints, BlanksFourier,

@@ -141,6 +141,17 @@ class _UpstreamStats(_SizedStats):
                 ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class _StreamOrderStats(_SizedStats):
+    """``hdem_streamorder_stats`` (the binding is hydrodem_amd/streamorder.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_order", ctypes.c_int32),
+                ("stream_cells", ctypes.c_int64), ("heads", ctypes.c_int64),
+                ("junctions", ctypes.c_int64), ("links", ctypes.c_int64),
+                ("max_hops", ctypes.c_int32),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_nodes", ctypes.c_float), ("ms_walk", ctypes.c_float),
+                ("ms_gather", ctypes.c_float)]
+
+
 DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
 # columns of the depression table, in the order of the C ABI's pointers
 DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
@@ -243,6 +254,10 @@ SIGNATURES = {
                          _c.POINTER(_UpstreamStats)],
     "hdem_upstream_u8_dev": [_vp, _vp, _i, _i, _c.c_double, _vp, _vp, _vp, _i,
                              _c.POINTER(_UpstreamStats)],
+    "hdem_streamorder_u8": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _vp, _vp, _vp, _i,
+                            _c.POINTER(_StreamOrderStats)],
+    "hdem_streamorder_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _vp, _vp, _vp, _i,
+                                _c.POINTER(_StreamOrderStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

@@ -218,6 +218,10 @@ inline int d8_forest_rounds(const d8_forest_plan &p, const d8_forest_counters &h
     return r;
 }
 
+// hdem_flowtrace.hip: the bytes hdem_flowtrace_u8_dev takes from the head of the arena, for
+// an operator that calls it and keeps views of its own behind them
+size_t hdem_flowtrace_arena_bytes(int64_t tiles, int64_t nslots);
+
 inline int d8_report_invalid(unsigned long long bad)
 {
     HDEM_REQUIRE(!bad, HDEM_ERR_BAD_ARG,

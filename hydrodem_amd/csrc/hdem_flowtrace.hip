@@ -61,6 +61,8 @@ struct flowtrace_counters : d8_forest_counters {
     unsigned long long stops;         // stop cells (stream cells and terminal cells)
     unsigned long long unreached;     // cells whose path ends in a dry terminal
 };
+constexpr size_t FT_HEAD = 512;      // the counters' block at the head of the arena
+static_assert(sizeof(flowtrace_counters) <= FT_HEAD, "counters outgrew their block");
 
 // LDS word of A: pointer in bits 0-15, ncard in 16-31, ndiag in 32-47.  A stop or an exit
 // holds (itself, 0, 0), so composing "a then b" is one addition of b to a's counts.
@@ -324,6 +326,13 @@ int check_args(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *strea
 
 }  // namespace
 
+// The arena the trace takes for a raster of `tiles` tiles: an operator that calls it and keeps
+// views of its own in the arena puts them behind these bytes (hdem_d8tile.h).
+size_t hdem_flowtrace_arena_bytes(int64_t tiles, int64_t nslots)
+{
+    return FT_HEAD + (size_t)nslots * 32 + (size_t)tiles * TC * 6;
+}
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -345,9 +354,8 @@ extern "C" int hdem_flowtrace_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
 
     // arena: counters | two node arrays, 16 B per slot each | counts u32 per cell | target
     // u16 per cell
-    const size_t head = 512;
-    static_assert(sizeof(flowtrace_counters) <= head, "counters outgrew their block");
-    const size_t bytes = head + (size_t)nslots * 32 + (size_t)tiles * TC * 6;
+    const size_t head = FT_HEAD;
+    const size_t bytes = hdem_flowtrace_arena_bytes(tiles, nslots);
     char *ws = static_cast<char *>(hdem_arena(ctx, bytes));
     if (!ws) return HDEM_ERR_OOM;
     flowtrace_counters *cnt = reinterpret_cast<flowtrace_counters *>(ws);

@@ -25,8 +25,8 @@ unchanged when ``filters`` resolves here.
 
 New operators (the reference has neither): ``SinkFill``,
 ``D8FlowDirection``, ``ResolveFlats``, ``FlowAccumulation``, ``Watersheds``, ``FlowDistance``,
-``HeightAboveDrainage``, ``UpstreamFlowLength`` and the chain ``DemToHAND``, shaped like every
-other ``Filter``.
+``HeightAboveDrainage``, ``UpstreamFlowLength``, ``StreamOrder`` and the chains ``DemToHAND``
+and ``DemToStreamOrder``, shaped like every other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -58,6 +58,7 @@ from ..sliding_window import (SlidingWindow, CircularWindow,  # noqa: F401
                               NoCenterWindow, IgnoreBorderInnerSliding)
 from .. import backend
 from .. import upstream as _upstream
+from .. import streamorder as _streamorder
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -685,6 +686,78 @@ class UpstreamFlowLength(Filter):  # pylint: disable=too-few-public-methods
         return self._keep(outs)
 
 
+class StreamOrder(_FlowTrace):  # pylint: disable=too-few-public-methods
+    """Strahler stream order, Shreve magnitude and stream links (new operator).  Input: a uint8
+    H x W raster of ESRI D8 codes exactly as ``FlowAccumulation`` takes them.  ``streams`` is
+    the stream set as ``FlowDistance`` takes it: ``None`` (every cell is a stream cell), a
+    bool / uint8 mask of the codes' shape (non-zero = stream), a uint32 raster with
+    ``threshold`` (stream where ``>= threshold``: a ``FlowAccumulation`` result goes in as it
+    is), or a ``DeviceRaster`` of uint8 or uint32.
+
+    A stream donor of a cell is a neighbouring stream cell whose code points at it.  Off the
+    streams every result is 0.  On them, ``method="strahler"`` returns the uint8 order: 1
+    without a stream donor; else, with ``m`` the greatest order among the stream donors,
+    ``m + 1`` when two or more of them have it and ``m`` otherwise (the TauDEM / Whitebox rule
+    where more than two branches meet).  ``method="shreve"`` returns the uint32 magnitude: 1
+    without a stream donor, else the sum over the stream donors: the number of heads upstream.
+
+    With ``keep_partial_results=True`` the same call leaves ``order``, ``magnitude`` and
+    ``links`` (uint32: 1 + flat index of the last cell of the cell's link, the segment between
+    two junctions; ``Watersheds(pour_points=...)`` takes these ids and gives one catchment per
+    link) -- host arrays after ``apply``, device rasters (the caller's to free; the one
+    returned is among them) after ``apply_device``; otherwise they are ``None``.
+
+    ``ValueError`` for operands of another type, dtype or shape, ``threshold`` without a
+    uint32 raster, with a mask, or < 1, an unknown ``method`` (all before the device is
+    touched), a byte that is not a D8 code, codes that form a cycle, on or off the streams,
+    and more than 2^32 - 1 cells.  Exact, identical from run to run.
+
+    Attributes
+    ----------
+    stats : dict
+        stream_cells, heads (stream cells without a stream donor), junctions (two or more),
+        links, max_order, max_hops (links of the longest walk over the link graph),
+        tile_h / tile_w of the last call; phase times when profiling is on.
+    """
+
+    METHODS = {"strahler": "order", "shreve": "magnitude"}
+
+    def __init__(self, streams=None, *, threshold=None, method="strahler",
+                 keep_partial_results=False):
+        if method not in self.METHODS:
+            raise ValueError(f"method is 'strahler' or 'shreve', got {method!r}")
+        self._set_operands(streams, threshold, None, 1.0)
+        self.method = method
+        self.keep_partial_results = keep_partial_results
+        self.order = self.magnitude = self.links = None
+
+    def _want(self):
+        if self.method not in self.METHODS:
+            raise ValueError(f"method is 'strahler' or 'shreve', got {self.method!r}")
+        return ("order", "magnitude", "link") if self.keep_partial_results \
+            else (self.METHODS[self.method],)
+
+    def _keep(self, outs):
+        self.order = self.magnitude = self.links = None
+        if self.keep_partial_results:
+            self.order, self.magnitude, self.links = outs["order"], outs["magnitude"], outs["link"]
+        return outs[self.METHODS[self.method]]
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        want = self._want()
+        outs, self.stats = _streamorder.streamorder(
+            image_to_filter, _Given(self.streams).host(), self.threshold, want)
+        return self._keep(outs)
+
+    def apply_device(self, raster):
+        want = self._want()
+        _streamorder.streamorder_args(raster, self.streams, self.threshold, want)
+        with _Given(self.streams).device(raster.ctx) as streams:
+            outs, self.stats = _streamorder.streamorder_dev(raster, streams, self.threshold, want)
+        return self._keep(outs)
+
+
 class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods
     """D8 directions across flats (new operator).  Input: a uint8 H x W raster of ESRI D8 codes
     as ``D8FlowDirection`` returns them, and -- at construction -- the float32 ``dem`` they
@@ -1031,6 +1104,68 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
                 self.distance = trace.distance
                 stack.pop_all()                     # the caller's to free from here on
             return hand
+
+
+class DemToStreamOrder(ComposedFilter):  # pylint: disable=too-few-public-methods
+    """A float32 DEM to the Strahler order (or the Shreve magnitude) of its streams in one
+    device-resident chain: ``SinkFill(epsilon)`` and ``D8FlowDirection`` (one call, as in
+    ``HydroConditioning``), ``FlowAccumulation``, then ``StreamOrder`` with streams where the
+    accumulation is ``>= threshold``.  Nothing is downloaded in between.
+
+    ``stats`` maps ``SinkFill``, ``FlowAccumulation`` and ``StreamOrder`` to the stats of their
+    stage (``ResolveFlats`` too with ``flats="resolve"``, which runs that stage between the D8
+    and the accumulation as in ``DemToHAND``).  With ``keep_partial_results=True`` the last
+    call leaves ``codes``, ``accumulation``, ``order``, ``magnitude`` and ``links``: host arrays
+    after ``apply``, device rasters (the caller's to free; the one returned is among them) after
+    ``apply_device``; otherwise they are ``None``."""
+
+    KEPT = ("codes", "accumulation", "order", "magnitude", "links")
+
+    def __init__(self, *, threshold, epsilon=1e-3, flats="keep", method="strahler",
+                 keep_partial_results=False):
+        super().__init__()
+        self.flats = _check_flats(flats)
+        # the checks of the order's operands, on a stand-in of the type the chain makes
+        StreamOrder(np.zeros((1, 1), np.uint32), threshold=threshold, method=method)
+        self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection(), FlowAccumulation()]
+        self.threshold, self.method = threshold, method
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.codes = self.accumulation = self.order = self.magnitude = self.links = None
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("DemToStreamOrder", image_to_filter, np.float32, "a float32 DEM")
+        with backend.DeviceRaster.from_host(image_to_filter, dtype=np.float32) as z, \
+                contextlib.ExitStack() as stack:
+            result = stack.enter_context(self.apply_device(z))
+            out = result.to_host()
+            for name in self.KEPT if self.keep_partial_results else ():
+                raster = stack.enter_context(getattr(self, name))
+                setattr(self, name, out if raster is result else raster.to_host())
+        return out
+
+    def apply_device(self, raster):
+        _check_raster("DemToStreamOrder", raster, np.float32, "a float32 DEM")
+        fill, _, accumulate = self.filters
+        self.codes = self.accumulation = self.order = self.magnitude = self.links = None
+        with contextlib.ExitStack() as stack:
+            filled, codes, resolve_stats = _fill_d8(stack, raster, fill, self.flats)
+            acc, accumulate.stats = backend.flowacc_dev(codes)
+            stack.enter_context(acc)
+            order = StreamOrder(acc, threshold=self.threshold, method=self.method,
+                                keep_partial_results=self.keep_partial_results)
+            out = order.apply_device(codes)
+            self.stats = {"SinkFill": fill.stats, "FlowAccumulation": accumulate.stats,
+                          "StreamOrder": order.stats}
+            if resolve_stats is not None:
+                self.stats["ResolveFlats"] = resolve_stats
+            if self.keep_partial_results:
+                self.codes, self.accumulation = codes, acc
+                self.order, self.magnitude, self.links = order.order, order.magnitude, order.links
+                stack.pop_all()                     # the caller's to free from here on ...
+                filled.free()                       # ... but for the filled DEM
+            return out
 
 
 # ---------------------------------------------------------------------------

@@ -711,6 +711,66 @@ int hdem_upstream_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, double 
                          uint32_t *ncard, uint32_t *ndiag, float *length, int flags,
                          hdem_upstream_stats *stats);    /* device pointers */
 
+/* ---- A11  StreamOrder.apply  (new operator: Strahler order, Shreve magnitude, stream links) --
+ * d8: uint8 ESRI codes exactly as hdem_flowacc_u8 takes them (0, or a code pointing outside
+ * the raster, is terminal; any byte that is not a code is invalid).
+ * The stream set S is given as hdem_flowtrace_u8 takes its streams:
+ *   stream_kind == HDEM_FT_STREAMS_NONE     streams == NULL, threshold == 0: every cell is in S
+ *   stream_kind == HDEM_FT_STREAMS_MASK_U8  streams is uint8 H x W, non-zero = in S; threshold 0
+ *   stream_kind == HDEM_FT_STREAMS_ACC_U32  streams is uint32 H x W, in S where >= threshold;
+ *                                           threshold >= 1
+ * A stream donor of c is a neighbour in S whose code points at c.  For c not in S all three
+ * outputs are 0.  For c in S:
+ *   order(c)      1 without a stream donor; else, with m the greatest order among its stream
+ *                 donors, m + 1 when two or more of them have order m, else m (orders 2, 2, 2
+ *                 give 3; 2, 2, 3 give 3; eight donors of order 1 give 2)
+ *   magnitude(c)  1 without a stream donor, else the sum of its stream donors' magnitudes: the
+ *                 number of heads (stream cells without a stream donor) upstream, c included
+ *   link(c)       1 + the flat index of the last cell of c's link: the first cell b on c's D8
+ *                 path (c included) that is terminal, or whose receiver is not in S, or whose
+ *                 receiver has two or more stream donors.  Order and magnitude are constant on
+ *                 a link; the ids are pour points as hdem_watershed_u8 takes them
+ * Outputs, all H x W, each may be NULL (not wanted), at least one must not be:
+ *   order      uint8    (at most 33 for H * W <= 2^32 - 1)
+ *   magnitude  uint32
+ *   link       uint32
+ * flags must be 0.  Exact integers, identical from run to run and independent of the schedule.
+ * HDEM_ERR_BAD_ARG, in bounded time, for an invalid byte, for codes that form a cycle (a loop
+ * of stream cells, with or without a tributary joining it, and a loop that holds no stream
+ * cell; a loop that leaves the streams and comes back is cut where it leaves them, as
+ * hdem_flowtrace_u8 cuts a loop that holds a stream cell), for the argument combinations
+ * excluded above and -- before any allocation or launch -- for
+ * H * W > 2^32 - 1.  Every retry loop carries a cap; HDEM_ERR_NOT_CONVERGED if one is ever
+ * reached.  On error the contents of the outputs are unspecified.
+ * Workspace, from the context's arena: 10 B per cell (14 B when link is NULL) next to the
+ * flow trace's own 6 B per cell and 32 B per tile-perimeter slot.
+ * The _dev form synchronises the context's stream twice (after the first-stop trace, which
+ * is hdem_flowtrace_u8_dev's, and to read its own counters).  stats may be NULL; otherwise the
+ * caller sets stats->struct_size = sizeof(hdem_streamorder_stats) first (64 bytes in this
+ * version; a shorter struct is filled as far as it goes).  The three phase times are filled
+ * only while profiling is on (hdem_profile_enable); the call has no kernel id. */
+typedef struct hdem_streamorder_stats {
+    uint32_t struct_size;   /* in: sizeof(hdem_streamorder_stats), set by the caller          */
+    int32_t max_order;      /* the greatest order (0 without a stream cell)                   */
+    int64_t stream_cells;   /* cells in S                                                     */
+    int64_t heads;          /* stream cells without a stream donor                            */
+    int64_t junctions;      /* stream cells with two or more stream donors                    */
+    int64_t links;          /* links: nodes of the link graph                                 */
+    int32_t max_hops;       /* links of the longest walk over the link graph                  */
+    int32_t tile_h, tile_w;
+    float ms_nodes;         /* node pass + first stop of every cell (HIP events; profiling)   */
+    float ms_walk;          /* the walk over the link graph                                   */
+    float ms_gather;        /* outputs written                                                */
+} hdem_streamorder_stats;   /* sizeof == 64 */
+int hdem_streamorder_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *streams,
+                        int stream_kind, uint32_t threshold, uint8_t *order,
+                        uint32_t *magnitude, uint32_t *link, int flags,
+                        hdem_streamorder_stats *stats);      /* host pointers, synchronous */
+int hdem_streamorder_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *streams,
+                            int stream_kind, uint32_t threshold, uint8_t *order,
+                            uint32_t *magnitude, uint32_t *link, int flags,
+                            hdem_streamorder_stats *stats);  /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
