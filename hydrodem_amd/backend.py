@@ -182,6 +182,7 @@ SIGNATURES = {
     "hdem_malloc": [_vp, _c.c_size_t, _c.POINTER(_vp)],
     "hdem_free": [_vp, _vp],
     "hdem_trim": [_vp, _c.POINTER(_c.c_size_t)],
+    "hdem_set_scribble": [_vp, _i],
     "hdem_memcpy_h2d": [_vp, _vp, _vp, _c.c_size_t],
     "hdem_memcpy_d2h": [_vp, _vp, _vp, _c.c_size_t],
     "hdem_memcpy_d2d": [_vp, _vp, _vp, _c.c_size_t],
@@ -401,6 +402,20 @@ class Context:
         n = ctypes.c_size_t(0)
         self.check(self.lib.hdem_trim(self.handle, ctypes.byref(n)))
         return int(n.value)
+
+    @contextlib.contextmanager
+    def scribble(self, byte):
+        """Scribble mode for the length of a ``with`` block (``hdem_set_scribble``): every
+        block ``hdem_malloc`` hands out, every allocation of the library's own and the part of
+        the scratch arena an operator asks for are filled with ``byte`` (0 ... 255) first.  A
+        result that depends on ``byte`` comes from memory nobody wrote.  Off again on exit."""
+        if isinstance(byte, bool) or int(byte) != byte or not 0 <= int(byte) <= 255:
+            raise ValueError(f"the scribble byte is 0 ... 255, got {byte!r}")
+        self.check(self.lib.hdem_set_scribble(self.handle, int(byte)))
+        try:
+            yield self
+        finally:
+            self.check(self.lib.hdem_set_scribble(self.handle, -1))
 
     # -- timing ----------------------------------------------------------
     def profile(self, on=True):

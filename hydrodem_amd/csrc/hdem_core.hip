@@ -4,6 +4,7 @@
 #include <sys/mman.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -34,6 +35,57 @@ extern "C" int hdem_device_count(int *count)
         return HDEM_ERR_NO_DEVICE;
     }
     *count = n;
+    return HDEM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// scribble mode (hdem_set_scribble): a test mode, off by default
+// ---------------------------------------------------------------------------
+// The poison byte of a context is kept beside it, in a table keyed by the context, and
+// g_scribbling counts the contexts that have the mode on: with none, each of the three hooks
+// (hdem_arena, hdem_raw_alloc, hdem_malloc) costs the one branch on that counter.  Not a field
+// of hdem_ctx: hdem_internal.h is one of the sources that the benchmark's committed record of
+// the fill kernel's memory traffic is stamped with, and a test mode is no reason to retake it.
+namespace {
+
+std::atomic<int> g_scribbling{0};
+std::mutex g_scribble_lock;
+std::unordered_map<const hdem_ctx *, int> g_scribble_byte;
+
+int scribble_byte(const hdem_ctx *ctx)           // -1: off
+{
+    if (g_scribbling.load(std::memory_order_relaxed) == 0) return -1;
+    std::lock_guard<std::mutex> guard(g_scribble_lock);
+    const auto it = g_scribble_byte.find(ctx);
+    return it == g_scribble_byte.end() ? -1 : it->second;
+}
+
+void scribble_set(const hdem_ctx *ctx, int byte)
+{
+    std::lock_guard<std::mutex> guard(g_scribble_lock);
+    if (byte < 0) g_scribble_byte.erase(ctx);
+    else g_scribble_byte[ctx] = byte;
+    g_scribbling.store((int)g_scribble_byte.size(), std::memory_order_relaxed);
+}
+
+// `bytes` of `byte` at p on the context's stream, waited for: no copy on another stream and
+// no later kernel can overtake the fill
+int scribble(hdem_ctx *ctx, int byte, void *p, size_t bytes)
+{
+    if (!bytes) return HDEM_OK;
+    HDEM_HIP_CHECK(hipMemsetAsync(p, byte, bytes, ctx->stream));
+    HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return HDEM_OK;
+}
+
+}  // namespace
+
+extern "C" int hdem_set_scribble(hdem_ctx *ctx, int byte)
+{
+    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
+    HDEM_REQUIRE(byte >= -1 && byte <= 255, HDEM_ERR_BAD_ARG,
+                 "the scribble byte is -1 (off) or 0 ... 255, got %d", byte);
+    scribble_set(ctx, byte);
     return HDEM_OK;
 }
 
@@ -90,24 +142,32 @@ extern "C" int hdem_shutdown(hdem_ctx *ctx)
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->host_counts) (void)hipHostFree(ctx->host_counts);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
+    scribble_set(ctx, -1);
     delete ctx;
     return HDEM_OK;
 }
 
+// A call made inside another user's (the flow trace under the stream order) asks for no more
+// than the head the outer one left it: in scribble mode exactly the first `bytes` are
+// poisoned, at every call, and the outer user's views behind them stay as they are.
 void *hdem_arena(hdem_ctx *ctx, size_t bytes)
 {
-    if (ctx->arena_bytes >= bytes) return ctx->arena;
-    if (ctx->arena) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(ctx->arena);
-        ctx->arena = nullptr;
-        ctx->arena_bytes = 0;
+    if (ctx->arena_bytes < bytes) {
+        if (ctx->arena) {
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipFree(ctx->arena);
+            ctx->arena = nullptr;
+            ctx->arena_bytes = 0;
+        }
+        // (hdem_raw_alloc poisons the fresh block too; the fill below is the one that counts)
+        if (hdem_raw_alloc(ctx, bytes, &ctx->arena) != HDEM_OK) {
+            ctx->arena = nullptr;
+            return nullptr;
+        }
+        ctx->arena_bytes = bytes;
     }
-    if (hdem_raw_alloc(ctx, bytes, &ctx->arena) != HDEM_OK) {
-        ctx->arena = nullptr;
-        return nullptr;
-    }
-    ctx->arena_bytes = bytes;
+    const int byte = scribble_byte(ctx);
+    if (byte >= 0 && scribble(ctx, byte, ctx->arena, bytes) != HDEM_OK) return nullptr;
     return ctx->arena;
 }
 
@@ -165,6 +225,13 @@ int hdem_raw_alloc(hdem_ctx *ctx, size_t bytes, void **dptr)
         hdem_set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? HDEM_ERR_OOM : HDEM_ERR_HIP;
     }
+    const int byte = scribble_byte(ctx);
+    if (byte >= 0)
+        if (int rc = scribble(ctx, byte, *dptr, bytes ? bytes : 1)) {
+            (void)hipFree(*dptr);
+            *dptr = nullptr;
+            return rc;
+        }
     return HDEM_OK;
 }
 
@@ -227,7 +294,9 @@ extern "C" int hdem_malloc(hdem_ctx *ctx, size_t bytes, void **dptr)
         ctx->pool_events.push_back(b.ready);
         ctx->pool_live[b.p] = {b.bytes, ctx->stream};
         *dptr = b.p;
-        return HDEM_OK;
+        // (behind the wait for `ready`, on the same stream; the block's whole size)
+        const int byte = scribble_byte(ctx);
+        return byte >= 0 ? scribble(ctx, byte, b.p, b.bytes) : HDEM_OK;
     }
     hipError_t e = hipMalloc(dptr, bytes);
     if (e == hipErrorOutOfMemory && !ctx->pool_free.empty()) {
@@ -241,7 +310,8 @@ extern "C" int hdem_malloc(hdem_ctx *ctx, size_t bytes, void **dptr)
         return e == hipErrorOutOfMemory ? HDEM_ERR_OOM : HDEM_ERR_HIP;
     }
     ctx->pool_live[*dptr] = {bytes, ctx->stream};
-    return HDEM_OK;
+    const int byte = scribble_byte(ctx);
+    return byte >= 0 ? scribble(ctx, byte, *dptr, bytes) : HDEM_OK;
 }
 
 extern "C" int hdem_free(hdem_ctx *ctx, void *dptr)

@@ -73,6 +73,15 @@ int hdem_synchronize(hdem_ctx *ctx);
 int hdem_malloc(hdem_ctx *ctx, size_t bytes, void **dptr);
 int hdem_free(hdem_ctx *ctx, void *dptr);
 int hdem_trim(hdem_ctx *ctx, size_t *released);
+/* Scribble mode, for tests (off by default; byte = -1 turns it off again, 0 ... 255 on).
+ * While it is on the library fills, with that byte, every block hdem_malloc hands out (fresh
+ * or from the cache, its whole size), every allocation it makes for itself, and -- at each
+ * call of an operator that uses it -- exactly the part of the context's scratch arena the
+ * operator asks for.  Each fill runs on the context's stream and is waited for.  The sink
+ * fill's workspace and its coarse and hub buffers carry state from call to call and are only
+ * filled when they are allocated.  An operator whose result depends on the byte reads memory
+ * it never wrote; with the mode off the only cost is a branch at those three places. */
+int hdem_set_scribble(hdem_ctx *ctx, int byte);
 int hdem_memcpy_h2d(hdem_ctx *ctx, void *dst, const void *src, size_t bytes);
 int hdem_memcpy_d2h(hdem_ctx *ctx, void *dst, const void *src, size_t bytes);
 int hdem_memcpy_d2d(hdem_ctx *ctx, void *dst, const void *src, size_t bytes);

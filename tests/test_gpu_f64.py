@@ -11,6 +11,8 @@ import pytest
 import hydrodem_amd as hd
 
 pytestmark = pytest.mark.gpu
+FFT_RTOL = 1e-13     # complex128 forward transform, relative to the largest magnitude
+IFFT_RTOL = 1e-12    # ... and back, relative to the largest input
 
 
 @pytest.fixture(scope="module")
@@ -23,10 +25,10 @@ def test_fourier_transform_in_double(gold, built):
     got = hd.FourierTransform().apply(x)
     assert got.dtype == np.complex128
     scale = np.abs(gold["fft"]).max()
-    assert np.abs(got - gold["fft"]).max() <= 1e-13 * scale         # (float32: ~1e-7)
+    assert np.abs(got - gold["fft"]).max() <= FFT_RTOL * scale        # (float32: ~1e-7)
     back = hd.FourierITransform().apply(got)
     assert back.dtype == np.complex128
-    assert np.abs(back - gold["ifft"]).max() <= 1e-12 * np.abs(x).max()
+    assert np.abs(back - gold["ifft"]).max() <= IFFT_RTOL * np.abs(x).max()
     assert np.abs(back.real - x).max() <= 1e-10                      # the digits float32 drops
     c = gold["c"]
     assert np.abs(hd.FourierTransform().apply(c) - gold["c_fft"]).max() <= 1e-13 * np.abs(gold["c_fft"]).max()

@@ -338,6 +338,11 @@ def _groves_compare(got, want64, highlight, thr=1.5, delta=1e-3):
     return int((bad & border).sum())
 
 
+def _groves_excused_limit(img):
+    """How many threshold-borderline cells a three-pass groves run may have."""
+    return max(2, img.size // 20000)
+
+
 def test_groves_golden(golden):
     g = golden("groves.npz")
     one = hd.GrovesCorrection(g["groves"]).apply(g["img"])
@@ -372,7 +377,7 @@ def test_groves_matches_reference_restatement(shape):
     want = c_oracle.groves_ref(img, groves, 3)
     _, stages = oracle.groves_exact64(img, groves, 3)
     excused = _groves_compare(got, want, [s[0] for s in stages])
-    assert excused <= max(2, img.size // 20000)
+    assert excused <= _groves_excused_limit(img)
 
 
 def test_groves_real_data_known_answer(golden):
