@@ -23,7 +23,8 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      PostProcessingFinal, SinkFill,
                                      D8FlowDirection, FlowAccumulation, Watersheds,
                                      FlowDistance, HeightAboveDrainage, UpstreamFlowLength,
-                                     StreamOrder, DemToStreamOrder, ResolveFlats,
+                                     StreamOrder, DemToStreamOrder, StreamNetwork,
+                                     DemToStreamNetwork, ResolveFlats,
                                      Depressions, DepressionInventory,
                                      HydroConditioning, DemToHAND,
                                      ExpandFilter, IsolatedPoints, BlanksFourier,

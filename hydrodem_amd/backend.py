@@ -152,6 +152,16 @@ class _StreamOrderStats(_SizedStats):
                 ("ms_gather", ctypes.c_float)]
 
 
+class _StreamLinksStats(_SizedStats):
+    """``hdem_streamlinks_stats`` (the binding is hydrodem_amd/streamnet.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_int32),
+                ("links", ctypes.c_int64), ("stream_cells", ctypes.c_int64),
+                ("catchment_cells", ctypes.c_int64), ("tops", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_rank", ctypes.c_float), ("ms_trace", ctypes.c_float),
+                ("ms_tile", ctypes.c_float), ("ms_final", ctypes.c_float)]
+
+
 DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
 # columns of the depression table, in the order of the C ABI's pointers
 DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
@@ -259,6 +269,12 @@ SIGNATURES = {
                             _c.POINTER(_StreamOrderStats)],
     "hdem_streamorder_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _vp, _vp, _vp, _i,
                                 _c.POINTER(_StreamOrderStats)],
+    "hdem_streamlinks_u8": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _vp, _vp, _vp, _vp,
+                            _c.c_double, _c.c_int64] + [_vp] * 13 +
+                           [_i, _c.POINTER(_StreamLinksStats)],
+    "hdem_streamlinks_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _vp, _vp, _vp, _vp,
+                                _c.c_double, _c.c_int64] + [_vp] * 13 +
+                               [_i, _c.POINTER(_StreamLinksStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

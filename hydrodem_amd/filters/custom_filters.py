@@ -25,8 +25,9 @@ unchanged when ``filters`` resolves here.
 
 New operators (the reference has neither): ``SinkFill``,
 ``D8FlowDirection``, ``ResolveFlats``, ``FlowAccumulation``, ``Watersheds``, ``FlowDistance``,
-``HeightAboveDrainage``, ``UpstreamFlowLength``, ``StreamOrder`` and the chains ``DemToHAND``
-and ``DemToStreamOrder``, shaped like every other ``Filter``.
+``HeightAboveDrainage``, ``UpstreamFlowLength``, ``StreamOrder``, ``StreamNetwork`` and the
+chains ``DemToHAND``, ``DemToStreamOrder`` and ``DemToStreamNetwork``, shaped like every other
+``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -59,6 +60,7 @@ from ..sliding_window import (SlidingWindow, CircularWindow,  # noqa: F401
 from .. import backend
 from .. import upstream as _upstream
 from .. import streamorder as _streamorder
+from .. import streamnet as _streamnet
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -758,6 +760,97 @@ class StreamOrder(_FlowTrace):  # pylint: disable=too-few-public-methods
         return self._keep(outs)
 
 
+class StreamNetwork(_FlowTrace):  # pylint: disable=too-few-public-methods
+    """The stream network as a table, one row per link (new operator).  Input: a uint8 H x W
+    raster of ESRI D8 codes; ``streams`` and ``threshold`` are the stream set as ``StreamOrder``
+    takes it.  Runs ``StreamOrder`` and then gathers the links (the segments between two
+    junctions) into ``table``, a dict of host arrays with one entry per link, numbered in
+    ascending flat index of the link's last cell: ``end`` and ``top`` (flat indices of the last
+    and first cell), ``down`` (the row of the link it drains into, ``0xFFFFFFFF`` for none),
+    ``order``, ``magnitude``, ``cells``, ``ncard`` / ``ndiag`` (cardinal and diagonal steps from
+    ``top`` to ``end``, plus the step out of ``end`` when ``down`` is a link, so that lengths
+    add up along ``down``), ``length`` (``ncard * cellsize + ndiag * cellsize * sqrt(2)`` in
+    float64, rounded once), ``catchment`` (cells, on or off the streams, whose first stream
+    cell lies in the link) and, with a float32 ``dem``, ``z_top`` / ``z_end``.  ``columns``
+    picks among them (default: all that the operands allow); without ``catchment`` no flow
+    trace runs.
+
+    Returns the ``row`` raster (uint32: 1 + row on the cells of a link, 0 off the streams; pour
+    points for ``Watersheds`` whose labels index the table): a host array from ``apply``, a
+    device raster (the caller's to free) from ``apply_device``.  ``count`` is the number of
+    links.  With ``keep_partial_results=True`` the call also leaves ``order``, ``magnitude``
+    and ``links`` as ``StreamOrder`` does.
+
+    ``ValueError`` for everything ``StreamOrder`` refuses, an unknown column and ``z_top`` /
+    ``z_end`` without ``dem`` (all before the device is touched).  Exact, identical from run
+    to run.
+
+    Attributes
+    ----------
+    stats : dict
+        links, stream_cells, catchment_cells (cells that reach a stream), tops, tile_h / tile_w
+        of the last call, phase times when profiling is on, and ``order_stats``, the stats of
+        the stream order.
+    """
+
+    KEPT = ("order", "magnitude", "links")
+
+    def __init__(self, streams=None, *, threshold=None, dem=None, cellsize=1.0, columns=None,
+                 keep_partial_results=False):
+        self._set_operands(streams, threshold, dem, cellsize)
+        self.columns = columns
+        self.keep_partial_results = keep_partial_results
+        self.table, self.count = None, 0
+        self.order = self.magnitude = self.links = None
+        # everything but the shapes: 1 x 1 stand-ins for the rasters of the two calls
+        one = np.zeros((1, 1), np.uint8)
+        self._check_table(one, np.zeros((1, 1), np.uint32), one, np.zeros((1, 1), np.uint32),
+                          _Given(self.streams).stand_in(), _Given(self.dem).stand_in())
+
+    def _check_table(self, codes, link, order, magnitude, streams, dem):
+        return _streamnet.streamnet_args(codes, streams, self.threshold, link, order, magnitude,
+                                         dem, self.cellsize, 0, self.columns, True)
+
+    def _check_codes(self, codes):
+        """The checks of both calls before either runs: the order's, then the table's on
+        stand-ins of the shape the order's rasters will have."""
+        _streamorder.streamorder_args(codes, self.streams, self.threshold, "link")
+        like = lambda dtype: np.broadcast_to(np.zeros((), dtype), codes.shape)  # noqa: E731
+        self._check_table(codes, like(np.uint32), like(np.uint8), like(np.uint32), self.streams,
+                          self.dem)
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        self._check_codes(image_to_filter)
+        with contextlib.ExitStack() as stack:
+            codes = stack.enter_context(backend.DeviceRaster.from_host(image_to_filter))
+            row = stack.enter_context(self.apply_device(codes))
+            for name in self.KEPT if self.keep_partial_results else ():
+                raster = stack.enter_context(getattr(self, name))
+                setattr(self, name, raster.to_host())
+            return row.to_host()
+
+    def apply_device(self, raster):
+        self._check_codes(raster)
+        self.order = self.magnitude = self.links = None
+        with _Given(self.streams).device(raster.ctx) as streams, \
+                _Given(self.dem).device(raster.ctx) as dem, contextlib.ExitStack() as stack:
+            outs, order_stats = _streamorder.streamorder_dev(
+                raster, streams, self.threshold, ("order", "magnitude", "link"))
+            for out in outs.values():
+                stack.enter_context(out)
+            self.count = order_stats["links"]
+            self.table, row, stats = _streamnet.streamlinks_dev(
+                raster, outs["link"], self.count, streams, self.threshold, outs["order"],
+                outs["magnitude"], dem, self.cellsize, self.columns, want_row=True)
+            self.stats = dict(stats, order_stats=order_stats)
+            if self.keep_partial_results:
+                self.order, self.magnitude, self.links = (outs["order"], outs["magnitude"],
+                                                          outs["link"])
+                stack.pop_all()                     # the caller's to free from here on
+        return row
+
+
 class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods
     """D8 directions across flats (new operator).  Input: a uint8 H x W raster of ESRI D8 codes
     as ``D8FlowDirection`` returns them, and -- at construction -- the float32 ``dem`` they
@@ -1166,6 +1259,52 @@ class DemToStreamOrder(ComposedFilter):  # pylint: disable=too-few-public-method
                 stack.pop_all()                     # the caller's to free from here on ...
                 filled.free()                       # ... but for the filled DEM
             return out
+
+
+class DemToStreamNetwork(ComposedFilter):  # pylint: disable=too-few-public-methods
+    """A float32 DEM to the table of its stream network in one device-resident chain:
+    ``SinkFill(epsilon)`` and ``D8FlowDirection`` (one call, as in ``HydroConditioning``),
+    ``FlowAccumulation``, then ``StreamNetwork`` with streams where the accumulation is
+    ``>= threshold`` and the **filled** DEM for the elevation columns, so that ``z_top >= z_end``
+    on every link.  Nothing is downloaded in between.
+
+    Returns the ``row`` raster as ``StreamNetwork`` does and leaves ``table`` and ``count``;
+    ``stats`` maps ``SinkFill``, ``FlowAccumulation`` and ``StreamNetwork`` to the stats of their
+    stage (``ResolveFlats`` too with ``flats="resolve"``, which runs that stage between the D8
+    and the accumulation as in ``DemToHAND``)."""
+
+    def __init__(self, threshold, *, epsilon=1e-3, flats="keep", cellsize=1.0, columns=None):
+        super().__init__()
+        self.flats = _check_flats(flats)
+        # the checks of the table's operands, on stand-ins of the types the chain makes
+        StreamNetwork(np.zeros((1, 1), np.uint32), threshold=threshold,
+                      dem=np.zeros((1, 1), np.float32), cellsize=cellsize, columns=columns)
+        self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection(), FlowAccumulation()]
+        self.threshold, self.cellsize, self.columns = threshold, cellsize, columns
+        self.stats = {}
+        self.table, self.count = None, 0
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("DemToStreamNetwork", image_to_filter, np.float32, "a float32 DEM")
+        return _through_device(self, image_to_filter)
+
+    def apply_device(self, raster):
+        _check_raster("DemToStreamNetwork", raster, np.float32, "a float32 DEM")
+        fill, _, accumulate = self.filters
+        with contextlib.ExitStack() as stack:
+            filled, codes, resolve_stats = _fill_d8(stack, raster, fill, self.flats)
+            acc, accumulate.stats = backend.flowacc_dev(codes)
+            stack.enter_context(acc)
+            network = StreamNetwork(acc, threshold=self.threshold, dem=filled,
+                                    cellsize=self.cellsize, columns=self.columns)
+            row = network.apply_device(codes)
+            self.table, self.count = network.table, network.count
+            self.stats = {"SinkFill": fill.stats, "FlowAccumulation": accumulate.stats,
+                          "StreamNetwork": network.stats}
+            if resolve_stats is not None:
+                self.stats["ResolveFlats"] = resolve_stats
+            return row
 
 
 # ---------------------------------------------------------------------------

@@ -780,6 +780,94 @@ int hdem_streamorder_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, cons
                             uint32_t *magnitude, uint32_t *link, int flags,
                             hdem_streamorder_stats *stats);  /* device pointers */
 
+/* ---- A12  StreamNetwork.apply  (new operator: the stream network as a table, one row per link) --
+ * d8, streams, stream_kind, threshold: the codes and the stream set S exactly as A11 takes
+ * them; stream donors, nin(c) (their number), links and link ends as A11 defines them.
+ * link (required): the uint32 H x W link raster hdem_streamorder_u8 wrote for these codes and
+ * this S; K = its hdem_streamorder_stats.links.  order_raster (uint8), magnitude_raster
+ * (uint32) of that call and dem (float32), all H x W, may be NULL; cellsize is finite and > 0.
+ * The links are numbered 0 ... K - 1 in ascending flat index of their end cell b, the cell c
+ * with link[c] == 1 + c.  Row r of every column describes link r.  The columns, K entries each:
+ *   end        uint32   flat index of b (the link id is 1 + end)
+ *   top        uint32   flat index of the link's first cell: its one cell with nin != 1 (a head,
+ *                       nin = 0, or a junction cell, nin >= 2)
+ *   down       uint32   the row of the link that holds b's receiver when that receiver is in S;
+ *                       0xFFFFFFFF when b is terminal or its receiver is off S
+ *   order      uint8    order_raster[b]      (needs order_raster)
+ *   magnitude  uint32   magnitude_raster[b]  (needs magnitude_raster)
+ *   cells      uint32   the number of cells of the link
+ *   ncard      uint32   cardinal and diagonal steps of the D8 path from top to b, plus b's own
+ *   ndiag      uint32   step when down is a link: every step between two stream cells belongs
+ *                       to exactly one link, ncard + ndiag == cells - 1 + (down is a link), and
+ *                       lengths add up along down
+ *   length     float32  (float)((double)ncard * cellsize + (double)ndiag * (cellsize * sqrt(2.0))),
+ *                       one rounding per operation, no fused multiply-add: hdem_flowtrace_u8's
+ *                       distance formula
+ *   catchment  uint32   the number of cells, on or off S, whose first stream cell on their D8
+ *                       path (themselves included) lies in the link: the area of the catchment
+ *                       hdem_watershed_u8 draws with the link ids as pour points.  A cell whose
+ *                       path never meets a stream counts nowhere
+ *   z_top      float32  dem[top]   (needs dem; NaN passes through)
+ *   z_end      float32  dem[end]
+ * and one raster, row (uint32 H x W): 1 + r on the cells of link r, 0 off the streams -- the
+ * compact link ids, pour points whose watershed labels index the table.
+ * Each column and row may be NULL (not wanted), at least one of the thirteen must not be.
+ * flags must be 0.  K == 0 is legal: row is zeroed when wanted and nothing else is launched.
+ * Every column is an integer sum, a count or a gather: exact, identical from run to run and
+ * independent of the schedule.
+ * HDEM_ERR_BAD_ARG -- before any allocation or launch -- for H * W > 2^32 - 1, unknown flags, a
+ * cellsize that is not finite and > 0, K outside 0 ... H * W, z_top or z_end without dem,
+ * order or magnitude without its raster, and no output at all.  HDEM_ERR_BAD_ARG in bounded
+ * time (counters read at the call's synchronisations; there is no walk) for an invalid byte
+ * and with "the links do not belong to these codes and streams" for a link raster that fails
+ * one of: link[c] == 0 off S; on S a link id that is not 0, lies inside the raster and names a
+ * cell that is its own end; a stream cell that is no end hands its id to a receiver in S; a
+ * stream cell with one stream donor carries that donor's id (so no end drains into a cell with
+ * nin < 2); the number of ends and the number of stream cells with nin != 1 both equal K.  A
+ * rank is compared with K before it indexes a column: a wrong K writes nowhere outside them.
+ * HDEM_ERR_NOT_CONVERGED if a probe of the per-tile table ever reaches its cap (the table
+ * size).  On error the contents of the outputs are unspecified.
+ * Workspace, from the context's arena: 12 B per 64 cells (0.19 B per cell); with catchment and
+ * a stream set other than every cell, 4 B per cell next to the flow trace's own 6 B per cell
+ * and 32 B per tile-perimeter slot; 8 B per link when length is wanted without ncard and ndiag.
+ * The _dev form synchronises the context's stream once to read its counters, and once more
+ * inside hdem_flowtrace_u8_dev when that runs (catchment wanted, stream_kind not
+ * HDEM_FT_STREAMS_NONE: where every cell is a stream cell, each is its own first stream cell).
+ * stats may be NULL; otherwise the caller sets stats->struct_size =
+ * sizeof(hdem_streamlinks_stats) first (64 bytes in this version; a shorter struct is filled as
+ * far as it goes).  The four step times are filled only while profiling is on
+ * (hdem_profile_enable); the call has no kernel id. */
+typedef struct hdem_streamlinks_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_streamlinks_stats), set by the caller         */
+    int32_t reserved;        /* 0                                                             */
+    int64_t links;           /* cells that are their own end: K for a link raster that fits   */
+    int64_t stream_cells;    /* cells in S                                                    */
+    int64_t catchment_cells; /* cells that reach a stream (the sum of catchment); counted     */
+                             /* only when catchment is wanted                                 */
+    int64_t tops;            /* stream cells with nin != 1: K again                           */
+    int32_t tile_h, tile_w;
+    float ms_rank;           /* ends, scan (HIP events; profiling)                            */
+    float ms_trace;          /* first stream cell of every cell; 0 when it does not run       */
+    float ms_tile;           /* the tile pass                                                 */
+    float ms_final;          /* the end pass and length                                       */
+} hdem_streamlinks_stats;    /* sizeof == 64 */
+int hdem_streamlinks_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *streams,
+                        int stream_kind, uint32_t threshold, const uint32_t *link,
+                        const uint8_t *order_raster, const uint32_t *magnitude_raster,
+                        const float *dem, double cellsize, int64_t K, uint32_t *end,
+                        uint32_t *top, uint32_t *down, uint8_t *order, uint32_t *magnitude,
+                        uint32_t *cells, uint32_t *ncard, uint32_t *ndiag, float *length,
+                        uint32_t *catchment, float *z_top, float *z_end, uint32_t *row,
+                        int flags, hdem_streamlinks_stats *stats);  /* host pointers, synchronous */
+int hdem_streamlinks_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *streams,
+                            int stream_kind, uint32_t threshold, const uint32_t *link,
+                            const uint8_t *order_raster, const uint32_t *magnitude_raster,
+                            const float *dem, double cellsize, int64_t K, uint32_t *end,
+                            uint32_t *top, uint32_t *down, uint8_t *order, uint32_t *magnitude,
+                            uint32_t *cells, uint32_t *ncard, uint32_t *ndiag, float *length,
+                            uint32_t *catchment, float *z_top, float *z_end, uint32_t *row,
+                            int flags, hdem_streamlinks_stats *stats);  /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
