@@ -24,7 +24,8 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      D8FlowDirection, FlowAccumulation, Watersheds,
                                      FlowDistance, HeightAboveDrainage, UpstreamFlowLength,
                                      StreamOrder, DemToStreamOrder, StreamNetwork,
-                                     DemToStreamNetwork, ResolveFlats,
+                                     DemToStreamNetwork, ZonalStatistics, DemToBasins,
+                                     ResolveFlats,
                                      Depressions, DepressionInventory,
                                      HydroConditioning, DemToHAND,
                                      ExpandFilter, IsolatedPoints, BlanksFourier,

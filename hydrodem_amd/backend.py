@@ -162,6 +162,18 @@ class _StreamLinksStats(_SizedStats):
                 ("ms_tile", ctypes.c_float), ("ms_final", ctypes.c_float)]
 
 
+class _ZonalStats(_SizedStats):
+    """``hdem_zonal_stats`` (the binding is hydrodem_amd/zonal.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_int32),
+                ("zones", ctypes.c_int64), ("unzoned", ctypes.c_int64),
+                ("clamped", ctypes.c_int64), ("overflow", ctypes.c_int64),
+                ("over_range", ctypes.c_int64), ("capped", ctypes.c_int64),
+                ("max_id", ctypes.c_uint32),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_rank", ctypes.c_float), ("ms_tile", ctypes.c_float),
+                ("ms_final", ctypes.c_float)]
+
+
 DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
 # columns of the depression table, in the order of the C ABI's pointers
 DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
@@ -275,6 +287,15 @@ SIGNATURES = {
     "hdem_streamlinks_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _vp, _vp, _vp, _vp,
                                 _c.c_double, _c.c_int64] + [_vp] * 13 +
                                [_i, _c.POINTER(_StreamLinksStats)],
+    "hdem_zonal_count_u32": [_vp, _vp, _i, _i, _c.POINTER(_c.c_int64),
+                             _c.POINTER(_ZonalStats)],
+    "hdem_zonal_count_u32_dev": [_vp, _vp, _i, _i, _c.POINTER(_c.c_int64),
+                                 _c.POINTER(_ZonalStats)],
+    "hdem_zonal_table_u32": [_vp, _vp, _i, _i, _vp, _i, _i, _c.c_int64] + [_vp] * 13 +
+                            [_i, _c.POINTER(_ZonalStats)],
+    "hdem_zonal_table_u32_dev": [_vp, _vp, _i, _i, _vp, _i, _i, _c.c_int64] + [_vp] * 13 +
+                                [_i, _c.POINTER(_ZonalStats)],
+    "hdem_zonal_broadcast_dev": [_vp, _vp, _i, _i, _c.c_int64, _vp, _c.c_uint32, _vp],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

@@ -61,6 +61,7 @@ from .. import backend
 from .. import upstream as _upstream
 from .. import streamorder as _streamorder
 from .. import streamnet as _streamnet
+from .. import zonal as _zonal
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -851,6 +852,97 @@ class StreamNetwork(_FlowTrace):  # pylint: disable=too-few-public-methods
         return row
 
 
+class ZonalStatistics(Filter):  # pylint: disable=too-few-public-methods
+    """Zonal statistics as a table (new operator).  Input: a uint32 H x W raster of zone ids, 0
+    where a cell belongs to no zone -- the labels of ``Watersheds``, the ``row`` raster of
+    ``StreamNetwork``, the labels of ``Depressions`` -- and, at construction, optionally a
+    raster of ``values`` of the same shape (float32, uint32 or uint8; array or
+    ``DeviceRaster``).  Ids lie in 1 ... H * W, which every label raster of this library
+    satisfies; arbitrary pour-point labels are relabelled first (``np.unique`` with
+    ``return_inverse``).
+
+    Returns the table, a dict of host arrays with one entry per zone present, in ascending id
+    (the order of ``np.unique``): ``id``, ``count``, ``first`` (smallest flat index),
+    ``row_min`` / ``row_max`` / ``col_min`` / ``col_max`` (the bounding box, inclusive) and,
+    with values, ``valid`` (cells that are not NaN), ``min`` / ``max`` (in the values' type;
+    -0.0 sorts below +0.0 and infinities take part; NaN, or 0 for the integer types, where
+    ``valid`` is 0), ``at_min`` / ``at_max`` (flat index of a cell holding them, the smallest on
+    ties, ``0xFFFFFFFF`` where ``valid`` is 0) and ``sum``: the exact uint64 sum of integer
+    values; for float32 the int64 sum of ``q(v) = clamp(rint(v * 2**frac_bits), +-(2**31 - 1))``
+    (``frac_bits`` in 0 ... 30; the default 16 holds ``|v| < 32768`` at a resolution of
+    1.5e-5; cells that clamp are counted in ``stats["clamped"]``).  ``mean`` is not computed on
+    the device: it is derived here in float64 as ``sum / 2**frac_bits / valid`` (integer
+    values: ``sum / valid``), NaN where ``valid`` is 0, when both columns are there.
+    ``columns`` picks among the device columns (default: all that the operands allow).  Exact,
+    identical from run to run and from ``apply`` and ``apply_device``.
+
+    ``broadcast(column, fill=0)`` is the raster form: every cell gets its zone's entry of a
+    column of the last table (by name, or an array of K 4-byte entries), ``fill`` where the id
+    is 0 -- a host array after ``apply``, a device raster (the caller's to free) after
+    ``apply_device``.
+
+    ``ValueError`` for zones that are not a 2-D uint32 raster, values of another shape or dtype,
+    unknown columns, a value column without values, ``frac_bits`` out of range (all before the
+    device is touched) and an id above H * W (the message names how many cells and the largest
+    id).
+
+    Attributes
+    ----------
+    stats : dict
+        zones (K), unzoned (cells with id 0), clamped, overflow (cells that went past their
+        tile's table), over_range, capped, max_id, tile_h / tile_w of the last call; phase times
+        when profiling is on.
+    table : dict of numpy.ndarray, or None
+        the table of the last call.
+    """
+
+    auto_device = True      # device form == host form for a uint32 raster
+
+    def __init__(self, values=None, columns=None, frac_bits=16):
+        self.values = _Given(values, "values", tuple(_zonal.VALUE_TYPES)).value
+        self.columns, self.frac_bits = columns, frac_bits
+        self.stats, self.table = {}, None
+        self._zones = None
+        # everything but the shapes, on 1 x 1 stand-ins
+        _zonal.zonal_args(np.zeros((1, 1), np.uint32), _Given(self.values).stand_in(),
+                          columns, frac_bits)
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _zonal.zonal_args(image_to_filter, self.values, self.columns, self.frac_bits)
+        self.table, self.stats = _zonal.zonal(image_to_filter, _Given(self.values).host(),
+                                              self.columns, self.frac_bits)
+        self._zones = image_to_filter
+        return self.table
+
+    def apply_device(self, raster):
+        _zonal.zonal_args(raster, self.values, self.columns, self.frac_bits)
+        with _Given(self.values).device(raster.ctx) as values:
+            self.table, self.stats = _zonal.zonal_dev(raster, values, self.columns,
+                                                      self.frac_bits)
+        self._zones = raster
+        return self.table
+
+    def broadcast(self, column, fill=0):
+        """The raster whose cells hold their zone's entry of ``column`` (see the class)."""
+        if self._zones is None:
+            raise ValueError("broadcast follows apply or apply_device: there is no table yet")
+        if isinstance(column, str):
+            if column not in self.table:
+                raise ValueError(f"the last table has no column {column!r}: it has "
+                                 f"{list(self.table)}")
+            column = self.table[column]
+        column = np.asarray(column)
+        if column.shape != (self.stats["zones"],):
+            raise ValueError(f"a column has one entry per zone ({self.stats['zones']}), got "
+                             f"shape {column.shape}")
+        if backend.is_device_raster(self._zones):
+            return _zonal.zonal_broadcast_dev(self._zones, column, fill)
+        with backend.DeviceRaster.from_host(self._zones) as zones, \
+                _zonal.zonal_broadcast_dev(zones, column, fill) as out:
+            return out.to_host()
+
+
 class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods
     """D8 directions across flats (new operator).  Input: a uint8 H x W raster of ESRI D8 codes
     as ``D8FlowDirection`` returns them, and -- at construction -- the float32 ``dem`` they
@@ -1305,6 +1397,52 @@ class DemToStreamNetwork(ComposedFilter):  # pylint: disable=too-few-public-meth
             if resolve_stats is not None:
                 self.stats["ResolveFlats"] = resolve_stats
             return row
+
+
+class DemToBasins(ComposedFilter):  # pylint: disable=too-few-public-methods
+    """A float32 DEM to the table of its drainage basins in one device-resident chain:
+    ``SinkFill(epsilon)`` and ``D8FlowDirection`` (one call, as in ``HydroConditioning``),
+    ``Watersheds(labels="compact")``, then ``ZonalStatistics`` of the labels with the DEM itself
+    as values: per basin its area, bounding box, lowest and highest point and where they are,
+    and the sum behind its mean elevation.  Nothing is downloaded in between.
+
+    Returns the compact labels as ``Watersheds`` does and leaves ``table`` and ``count``; the
+    table carries one more column, ``outlet`` (the flat index of the basin's terminal cell:
+    label ``k`` is row ``k - 1``).  ``stats`` maps ``SinkFill``, ``Watersheds`` and
+    ``ZonalStatistics`` to the stats of their stage (``ResolveFlats`` too with
+    ``flats="resolve"``, which runs that stage behind the D8 as in ``DemToHAND``)."""
+
+    def __init__(self, *, epsilon=1e-3, flats="keep", columns=None, frac_bits=16):
+        super().__init__()
+        self.flats = _check_flats(flats)
+        # the checks of the table's operands, on a stand-in of the type the chain is given
+        ZonalStatistics(np.zeros((1, 1), np.float32), columns, frac_bits)
+        self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection(),
+                        Watersheds(labels="compact")]
+        self.columns, self.frac_bits = columns, frac_bits
+        self.stats = {}
+        self.table, self.count = None, 0
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("DemToBasins", image_to_filter, np.float32, "a float32 DEM")
+        return _through_device(self, image_to_filter)
+
+    def apply_device(self, raster):
+        _check_raster("DemToBasins", raster, np.float32, "a float32 DEM")
+        fill, _, basins = self.filters
+        with contextlib.ExitStack() as stack:
+            _, codes, resolve_stats = _fill_d8(stack, raster, fill, self.flats)
+            with backend.result_raster(None, raster.shape, np.uint32, raster.ctx) as labels:
+                _, outlets, basins.stats = backend.watershed_dev(codes, None, True, out=labels)
+                zonal = ZonalStatistics(raster, self.columns, self.frac_bits)
+                self.table = dict(zonal.apply_device(labels), outlet=outlets.copy())
+                self.count = zonal.stats["zones"]
+                self.stats = {"SinkFill": fill.stats, "Watersheds": basins.stats,
+                              "ZonalStatistics": zonal.stats}
+                if resolve_stats is not None:
+                    self.stats["ResolveFlats"] = resolve_stats
+            return labels
 
 
 # ---------------------------------------------------------------------------

@@ -868,6 +868,96 @@ int hdem_streamlinks_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, cons
                             uint32_t *catchment, float *z_top, float *z_end, uint32_t *row,
                             int flags, hdem_streamlinks_stats *stats);  /* device pointers */
 
+/* ---- A13  ZonalStatistics.apply  (new operator: zonal statistics, one row per zone) --
+ * zones: a uint32 H x W label raster, 0 = no zone.  The ids lie in 1 ... H * W, which every
+ * label raster of this library satisfies (outlet labels 1 + flat index, compact labels, link
+ * ids, the row raster of A12, depression labels in both modes); a caller with arbitrary
+ * pour-point labels relabels first.  values (may be NULL): an H x W raster of value_type.
+ * The K ids present are numbered 0 ... K - 1 in ascending order (the order of np.unique); row r
+ * of every column describes the r-th id.  The columns, K entries each:
+ *   id         uint32   the zone's id
+ *   count      uint32   its cells
+ *   first      uint32   its smallest flat index y * W + x
+ *   row_min, row_max, col_min, col_max   uint32   its bounding box, inclusive
+ * and, with values:
+ *   valid      uint32   its cells whose value is not NaN (integer types: == count)
+ *   min, max   the value type   ordered by the order-preserving integer key of float32 (-0.0
+ *                       below +0.0, +-inf take part); NaN (float32) or 0 (integer types) for a
+ *                       zone with valid == 0
+ *   at_min, at_max   uint32   the flat index of a cell that holds the min / max, the smallest
+ *                       on ties; 0xFFFFFFFF where valid == 0.  Gathered as one 64-bit word per
+ *                       row: key << 32 | index under an unsigned min, key << 32 | ~index under
+ *                       an unsigned max
+ *   sum        uint64   the exact sum of uint8 / uint32 values; for float32 the int64 sum of
+ *                       q(v) = clamp(llrint((double)v * 2^frac_bits), +-(2^31 - 1)), rounding
+ *                       to nearest even; NaN cells add nothing, cells that clamp are counted
+ *                       (stats.clamped).  2^32 - 1 cells of 2^31 cannot overflow it.
+ * frac_bits is 0 ... 30 (16 resolves 1.5e-5 and holds |v| < 32768); it is ignored for the
+ * integer types.  The mean is not a column: sum / 2^frac_bits / valid.
+ * hdem_zonal_count_u32 returns K (in *K, may be NULL, and in stats.zones); the table call takes
+ * it, as A12 takes its count, and redoes the ranks (one more read of zones, one bitmap) rather
+ * than keeping state in the context between two calls.  Every column pointer may be NULL (not
+ * wanted), at least one must not be; flags must be 0.  K == 0 is legal when the raster holds no
+ * zone: nothing is written.  Every column is a count, a min, a max or an integer sum: exact,
+ * identical from run to run, independent of the schedule and of what the workspace held.
+ * hdem_zonal_broadcast_dev: out[c] = column[row of zones[c]] for a column of K 4-byte words
+ * (device pointer), fill where zones[c] == 0: the raster form.
+ * HDEM_ERR_BAD_ARG -- before any allocation or launch -- for H * W > 2^32 - 1, unknown flags or
+ * value type, values without a type or a type without values, a value column without values,
+ * frac_bits or K out of range, no column at all.  HDEM_ERR_BAD_ARG in bounded time (counters
+ * read at the call's one synchronisation; there is no walk) for an id above H * W (the message
+ * names the number of cells and the largest id) and for a K that is not the number of ids
+ * present; a rank is compared with K before it indexes a column, so such a call writes nothing
+ * outside the columns.  HDEM_ERR_NOT_CONVERGED if a probe of the per-tile id set ever reaches
+ * its cap (its size, which a tile cannot fill).  On error the contents of the outputs are
+ * unspecified.
+ * Workspace, from the context's arena: 12 B per 64 cells (0.19 B per cell), 16 B per zone when
+ * min, max, at_min or at_max is wanted.  Each _dev call synchronises the context's stream once.
+ * stats may be NULL; otherwise the caller sets stats->struct_size = sizeof(hdem_zonal_stats)
+ * first (80 bytes in this version; a shorter struct is filled as far as it goes).  The step
+ * times are filled only while profiling is on; the calls have no kernel id. */
+typedef enum hdem_zonal_value_type {
+    HDEM_ZONAL_NONE = 0,
+    HDEM_ZONAL_F32 = 1,
+    HDEM_ZONAL_U32 = 2,
+    HDEM_ZONAL_U8 = 3
+} hdem_zonal_value_type;
+typedef struct hdem_zonal_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_zonal_stats), set by the caller               */
+    int32_t reserved;        /* 0                                                             */
+    int64_t zones;           /* K: the ids present                                            */
+    int64_t unzoned;         /* cells with id 0                                               */
+    int64_t clamped;         /* float32 cells whose q(v) was clamped (table call, sum or not) */
+    int64_t overflow;        /* cells whose run found no slot in its tile's table and added   */
+                             /* to the columns directly (legal; table call)                   */
+    int64_t over_range;      /* cells with an id above H * W: refused                         */
+    int64_t capped;          /* probes of the id set that reached their cap: refused          */
+    uint32_t max_id;         /* the largest id                                                */
+    int32_t tile_h, tile_w;
+    float ms_rank;           /* bitmap, counts, scan (HIP events; profiling)                  */
+    float ms_tile;           /* column init and the tile pass                                 */
+    float ms_final;          /* min / max unpacking and the ids                               */
+} hdem_zonal_stats;          /* sizeof == 80 */
+int hdem_zonal_count_u32(hdem_ctx *ctx, const uint32_t *zones, int H, int W, int64_t *K,
+                         hdem_zonal_stats *stats);  /* host pointers, synchronous */
+int hdem_zonal_count_u32_dev(hdem_ctx *ctx, const uint32_t *zones, int H, int W, int64_t *K,
+                             hdem_zonal_stats *stats);  /* device pointer */
+int hdem_zonal_table_u32(hdem_ctx *ctx, const uint32_t *zones, int H, int W, const void *values,
+                         int value_type, int frac_bits, int64_t K, uint32_t *id, uint32_t *count,
+                         uint32_t *first, uint32_t *row_min, uint32_t *row_max, uint32_t *col_min,
+                         uint32_t *col_max, uint32_t *valid, void *min, void *max,
+                         uint32_t *at_min, uint32_t *at_max, void *sum, int flags,
+                         hdem_zonal_stats *stats);  /* host pointers, synchronous */
+int hdem_zonal_table_u32_dev(hdem_ctx *ctx, const uint32_t *zones, int H, int W,
+                             const void *values, int value_type, int frac_bits, int64_t K,
+                             uint32_t *id, uint32_t *count, uint32_t *first, uint32_t *row_min,
+                             uint32_t *row_max, uint32_t *col_min, uint32_t *col_max,
+                             uint32_t *valid, void *min, void *max, uint32_t *at_min,
+                             uint32_t *at_max, void *sum, int flags,
+                             hdem_zonal_stats *stats);  /* device pointers */
+int hdem_zonal_broadcast_dev(hdem_ctx *ctx, const uint32_t *zones, int H, int W, int64_t K,
+                             const void *column, uint32_t fill, void *out);  /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
