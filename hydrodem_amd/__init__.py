@@ -25,6 +25,8 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      FlowDistance, HeightAboveDrainage, UpstreamFlowLength,
                                      StreamOrder, DemToStreamOrder, StreamNetwork,
                                      DemToStreamNetwork, ZonalStatistics, DemToBasins,
+                                     TerrainAttributes, Slope, Aspect, WetnessIndex,
+                                     DemToWetness,
                                      ResolveFlats,
                                      Depressions, DepressionInventory,
                                      HydroConditioning, DemToHAND,

@@ -174,6 +174,13 @@ class _ZonalStats(_SizedStats):
                 ("ms_final", ctypes.c_float)]
 
 
+class _TerrainStats(_SizedStats):
+    """``hdem_terrain_stats`` (the binding is hydrodem_amd/terrain.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("ms_total", ctypes.c_float),
+                ("nan_cells", ctypes.c_int64), ("flat_cells", ctypes.c_int64),
+                ("floored_cells", ctypes.c_int64), ("invalid_codes", ctypes.c_int64)]
+
+
 DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
 # columns of the depression table, in the order of the C ABI's pointers
 DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
@@ -296,6 +303,10 @@ SIGNATURES = {
     "hdem_zonal_table_u32_dev": [_vp, _vp, _i, _i, _vp, _i, _i, _c.c_int64] + [_vp] * 13 +
                                 [_i, _c.POINTER(_ZonalStats)],
     "hdem_zonal_broadcast_dev": [_vp, _vp, _i, _i, _c.c_int64, _vp, _c.c_uint32, _vp],
+    "hdem_terrain_f32": [_vp, _vp, _i, _i, _vp, _vp] + [_c.c_double] * 4 + [_vp] * 8 +
+                        [_i, _c.POINTER(_TerrainStats)],
+    "hdem_terrain_f32_dev": [_vp, _vp, _i, _i, _vp, _vp] + [_c.c_double] * 4 + [_vp] * 8 +
+                            [_i, _c.POINTER(_TerrainStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

@@ -62,6 +62,7 @@ from .. import upstream as _upstream
 from .. import streamorder as _streamorder
 from .. import streamnet as _streamnet
 from .. import zonal as _zonal
+from .. import terrain as _terrain
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -943,6 +944,143 @@ class ZonalStatistics(Filter):  # pylint: disable=too-few-public-methods
             return out.to_host()
 
 
+class TerrainAttributes(Filter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """Slope, aspect and what is built on them, from one read of the DEM (new operator).
+    Input: a float32 H x W DEM, NaN where there is no data.  ``want`` names outputs of
+    ``hydrodem_amd.terrain.TERRAIN_OUTPUTS``, all float32:
+
+    ``dzdx`` / ``dzdy``  Horn's gradient over the 3 x 3 window (x eastwards, y southwards),
+                         differences first, times ``z_factor / (8 dx)`` and ``z_factor / (8 dy)``;
+                         a neighbour outside the raster or NaN takes the centre's value (ArcGIS)
+    ``tangent``          ``sqrt(dzdx^2 + dzdy^2)``: the percent slope / 100
+    ``degrees``          ``atan(tangent)`` in degrees
+    ``aspect``           compass direction of the steepest descent in degrees clockwise from
+                         north, in [0, 360); -1 where the gradient is 0
+    ``d8_slope``         drop to the cell the D8 code points at over the length of that step,
+                         0 for code 0 and for a code pointing outside; needs ``codes``
+    ``twi``              ``ln(a / max(t, min_slope))`` with ``a = accumulation * sqrt(dx dy)``,
+                         the specific catchment area; needs ``accumulation``
+    ``spi``              ``a * t``; needs ``accumulation``
+
+    ``t`` is the tangent (``slope="horn"``) or the D8 slope (``slope="d8"``, TauDEM's choice).
+    A NaN cell is NaN in every output.  ``cellsize``: a number or ``(dy, dx)``.  ``codes`` (uint8
+    ESRI D8 codes) and ``accumulation`` (uint32, ``FlowAccumulation``'s raster) are given at
+    construction, as arrays or device rasters of the DEM's shape.
+
+    Returns the first output of ``want``.  With ``keep_partial_results=True`` the same launch
+    also writes the other outputs of ``want`` and leaves them in the attributes of their names
+    -- host arrays after ``apply``, device rasters (the caller's to free) after
+    ``apply_device``; otherwise only the first is computed and the attributes are ``None``.
+
+    ``ValueError`` for a dtype other than float32, a raster that is not 2-D, operands of
+    another shape or dtype, unknown outputs, an output without the operand it needs, a
+    ``cellsize``, ``z_factor`` or ``min_slope`` that is not finite and positive (all before the
+    device is touched) and a ``codes`` byte that is no D8 code.
+
+    Attributes
+    ----------
+    stats : dict
+        nan_cells, flat_cells (aspect -1), floored_cells (cells whose slope was below
+        ``min_slope``, counted when ``twi`` is computed), invalid_codes of the last call;
+        ms_total when profiling is on.
+    """
+
+    auto_device = True      # device form == host form for a float32 raster
+
+    def __init__(self, want=("degrees",), cellsize=1.0, z_factor=1.0, codes=None,
+                 accumulation=None, min_slope=1e-3, slope="horn", keep_partial_results=False):
+        self.want = (want,) if isinstance(want, str) else tuple(want)
+        self.cellsize, self.z_factor = cellsize, z_factor
+        self.codes = _Given(codes, "codes", (np.uint8,)).value
+        self.accumulation = _Given(accumulation, "accumulation", (np.uint32,)).value
+        self.min_slope, self.slope = min_slope, slope
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        for name in _terrain.TERRAIN_OUTPUTS:
+            setattr(self, name, None)
+        # everything but the shapes, on 1 x 1 stand-ins
+        self._args(np.zeros((1, 1), np.float32), _Given(self.codes).stand_in(),
+                   _Given(self.accumulation).stand_in())
+
+    def _args(self, dem, codes, accumulation):
+        return _terrain.terrain_args(dem, self.want, self.cellsize, self.z_factor, codes,
+                                     accumulation, self.min_slope, self.slope)
+
+    def _want(self):
+        return self.want if self.keep_partial_results else self.want[:1]
+
+    def _keep(self, outs):
+        for name in _terrain.TERRAIN_OUTPUTS:
+            setattr(self, name, outs.get(name) if name != self.want[0] else None)
+        return outs[self.want[0]]
+
+    def _run(self, run, dem, codes, accumulation):
+        outs, self.stats = run(dem, self._want(), self.cellsize, self.z_factor, codes,
+                               accumulation, self.min_slope, self.slope)
+        return self._keep(outs)
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        self._args(image_to_filter, self.codes, self.accumulation)
+        return self._run(_terrain.terrain, image_to_filter, _Given(self.codes).host(),
+                         _Given(self.accumulation).host())
+
+    def apply_device(self, raster):
+        self._args(raster, self.codes, self.accumulation)
+        with _Given(self.codes).device(raster.ctx) as codes, \
+                _Given(self.accumulation).device(raster.ctx) as accumulation:
+            return self._run(_terrain.terrain_dev, raster, codes, accumulation)
+
+
+class Slope(TerrainAttributes):  # pylint: disable=too-few-public-methods
+    """Horn's slope of a float32 DEM (``TerrainAttributes``): ``units`` is ``"degrees"``,
+    ``"percent"`` (the tangent times 100, by the element-wise device operator) or
+    ``"tangent"``."""
+
+    UNITS = ("degrees", "percent", "tangent")
+
+    def __init__(self, units="degrees", cellsize=1.0, z_factor=1.0):
+        if units not in self.UNITS:
+            raise ValueError(f"units is 'degrees', 'percent' or 'tangent', got {units!r}")
+        super().__init__(want=("degrees" if units == "degrees" else "tangent",),
+                         cellsize=cellsize, z_factor=z_factor)
+        self.units = units
+
+    def apply(self, image_to_filter):
+        if self.units != "percent":
+            return super().apply(image_to_filter)
+        Filter.apply(self, image_to_filter)
+        self._args(image_to_filter, None, None)
+        return _through_device(self, image_to_filter)
+
+    def apply_device(self, raster):
+        first = super().apply_device(raster)
+        if self.units != "percent":
+            return first
+        with first:
+            return backend.elementwise_dev(backend.EW_MUL, first, 100.0)
+
+
+class Aspect(TerrainAttributes):  # pylint: disable=too-few-public-methods
+    """The aspect of a float32 DEM (``TerrainAttributes``): degrees clockwise from north of the
+    steepest descent of Horn's gradient, -1 where the gradient is 0."""
+
+    def __init__(self, cellsize=1.0, z_factor=1.0):
+        super().__init__(want=("aspect",), cellsize=cellsize, z_factor=z_factor)
+
+
+class WetnessIndex(TerrainAttributes):  # pylint: disable=too-few-public-methods
+    """The topographic wetness index ``ln(a / max(tan b, min_slope))`` of a float32 DEM and its
+    uint32 ``accumulation`` raster (``TerrainAttributes``): ``a`` is the accumulation times
+    ``sqrt(dx dy)``, ``tan b`` Horn's tangent, or the D8 slope along ``codes`` with
+    ``slope="d8"``."""
+
+    def __init__(self, accumulation=None, codes=None, cellsize=1.0, z_factor=1.0,
+                 min_slope=1e-3, slope="horn"):
+        super().__init__(want=("twi",), cellsize=cellsize, z_factor=z_factor, codes=codes,
+                         accumulation=accumulation, min_slope=min_slope, slope=slope)
+
+
 class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods
     """D8 directions across flats (new operator).  Input: a uint8 H x W raster of ESRI D8 codes
     as ``D8FlowDirection`` returns them, and -- at construction -- the float32 ``dem`` they
@@ -1289,6 +1427,62 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
                 self.distance = trace.distance
                 stack.pop_all()                     # the caller's to free from here on
             return hand
+
+
+class DemToWetness(ComposedFilter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """A float32 DEM to its topographic wetness index in one device-resident chain:
+    ``SinkFill(epsilon)`` and ``D8FlowDirection`` (one call, as in ``HydroConditioning``),
+    ``FlowAccumulation``, then ``WetnessIndex`` on the **filled** DEM with that accumulation
+    (and, with ``slope="d8"``, the slope along those codes).  Nothing is downloaded in
+    between.  ``flats`` as in ``DemToHAND``.
+
+    ``stats`` maps ``SinkFill``, ``FlowAccumulation`` and ``WetnessIndex`` (and
+    ``ResolveFlats``) to the stats of their stage.  With ``keep_partial_results=True`` the last
+    call leaves ``filled``, ``codes``, ``accumulation`` and ``tangent`` (Horn's, written by the
+    wetness launch): host arrays after ``apply``, device rasters (the caller's to free) after
+    ``apply_device``; otherwise they are ``None``."""
+
+    def __init__(self, *, epsilon=1e-3, flats="keep", cellsize=1.0, min_slope=1e-3,
+                 slope="horn", keep_partial_results=False):
+        super().__init__()
+        self.flats = _check_flats(flats)
+        # the checks of the last stage's operands, on stand-ins of the types the chain makes
+        _terrain.terrain_args(np.zeros((1, 1), np.float32), ("tangent", "twi"), cellsize, 1.0,
+                              np.zeros((1, 1), np.uint8), np.zeros((1, 1), np.uint32),
+                              min_slope, slope)
+        self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection(), FlowAccumulation()]
+        self.cellsize, self.min_slope, self.slope = cellsize, min_slope, slope
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.filled = self.codes = self.accumulation = self.tangent = None
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("DemToWetness", image_to_filter, np.float32, "a float32 DEM")
+        return _through_device(self, image_to_filter,
+                               ("filled", "codes", "accumulation", "tangent")
+                               if self.keep_partial_results else ())
+
+    def apply_device(self, raster):
+        _check_raster("DemToWetness", raster, np.float32, "a float32 DEM")
+        fill, _, accumulate = self.filters
+        self.filled = self.codes = self.accumulation = self.tangent = None
+        with contextlib.ExitStack() as stack:
+            filled, codes, resolve_stats = _fill_d8(stack, raster, fill, self.flats)
+            acc, accumulate.stats = backend.flowacc_dev(codes)
+            stack.enter_context(acc)
+            outs, stats = _terrain.terrain_dev(
+                filled, ("tangent", "twi") if self.keep_partial_results else ("twi",),
+                self.cellsize, 1.0, codes, acc, self.min_slope, self.slope)
+            self.stats = {"SinkFill": fill.stats, "FlowAccumulation": accumulate.stats,
+                          "WetnessIndex": stats}
+            if resolve_stats is not None:
+                self.stats["ResolveFlats"] = resolve_stats
+            if self.keep_partial_results:
+                self.filled, self.codes, self.accumulation = filled, codes, acc
+                self.tangent = outs["tangent"]
+                stack.pop_all()                     # the caller's to free from here on
+            return outs["twi"]
 
 
 class DemToStreamOrder(ComposedFilter):  # pylint: disable=too-few-public-methods

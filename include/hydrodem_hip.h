@@ -958,6 +958,67 @@ int hdem_zonal_table_u32_dev(hdem_ctx *ctx, const uint32_t *zones, int H, int W,
 int hdem_zonal_broadcast_dev(hdem_ctx *ctx, const uint32_t *zones, int H, int W, int64_t K,
                              const void *column, uint32_t fill, void *out);  /* device pointers */
 
+/* ---- A14  TerrainAttributes.apply  (new operator: slope, aspect, D8 slope, wetness index) ----
+ * dem: float32 H x W, NaN is nodata, +-inf are ordinary values.  One launch of a radius-1
+ * stencil writes any subset of eight float32 H x W rasters from one read of the DEM.
+ * Window of a cell e, rows growing southwards:   a b c / d e f / g h i.
+ * Edge rule: a neighbour outside the raster or NaN takes the value of e; a NaN e gives NaN in
+ * every output.
+ * Float32 throughout, one rounding per operation in exactly this order, no fused multiply-add;
+ * the scale factors are computed in double and rounded once: rx = (float)(z_factor / (8 dx)),
+ * ry = (float)(z_factor / (8 dy)).
+ *   gx = ((c - a) + ((f - d) + (f - d))) + (i - g)        dzdx = gx * rx
+ *   gy = ((g - a) + ((h - b) + (h - b))) + (i - c)        dzdy = gy * ry
+ *   s2 = dzdx * dzdx + dzdy * dzdy                         tangent = sqrtf(s2)
+ *   degrees = atanf(tangent) * (float)(180 / pi)
+ *   aspect  = atan2f(-dzdx, dzdy) * (float)(180 / pi), + 360.0f where negative, 0 where that
+ *             rounds to 360, -1 where dzdx == 0 && dzdy == 0: the compass direction of the
+ *             steepest descent, clockwise from north
+ *   d8_slope = (e - z_r) * rd with z_r the raw value of the cell the D8 code of e points at (not
+ *             centre-replaced: NaN if it is NaN) and rd = (float)(z_factor / dx), (z_factor / dy)
+ *             or (z_factor / sqrt(dx^2 + dy^2)) for an E / W, N / S or diagonal step; 0 for
+ *             code 0 and for a code pointing outside the raster
+ *   a   = (float)acc * (float)sqrt(dx * dy)                t = tangent, or d8_slope with
+ *                                                          HDEM_TERRAIN_TWI_D8
+ *   twi = logf(a / (t < min_slope ? min_slope : t))        (a NaN t stays NaN)
+ *   spi = a * t
+ * acc (uint32, hdem_flowacc_u8's raster) and d8 (uint8 ESRI codes) are optional inputs: twi and
+ * spi need acc, d8_slope and HDEM_TERRAIN_TWI_D8 need d8.  Every output pointer may be NULL (not
+ * wanted: no store, no math-library call), at least one must not be.
+ * HDEM_ERR_BAD_ARG before any launch: no output, twi / spi without acc, d8_slope or the flag
+ * without d8, unknown flags, dx, dy, z_factor or min_slope not finite and > 0, an output that
+ * overlaps an input or another output.  HDEM_ERR_BAD_ARG after the launch when d8 was read and
+ * holds a byte that is no D8 code (stats.invalid_codes says in how many cells); the outputs
+ * are unspecified then.
+ * dzdx, dzdy, d8_slope and tangent (sqrtf is correctly rounded) are the same bits from run to
+ * run and equal to the formulas above evaluated in IEEE float32; degrees, aspect and twi carry
+ * the error of the device math library's atanf, atan2f and logf.  A subset of the outputs
+ * holds the bytes the call for all of them writes.
+ * No workspace but 32 bytes of counters from the context's arena.  The _dev form synchronises
+ * the context's stream once to read them.  stats may be NULL; otherwise the caller sets
+ * stats->struct_size = sizeof(hdem_terrain_stats) first (40 bytes in this version; a shorter
+ * struct is filled as far as it goes).  ms_total is filled only while profiling is on
+ * (hdem_profile_enable); the call has no kernel id. */
+#define HDEM_TERRAIN_TWI_D8 1    /* twi and spi take d8_slope as their t */
+typedef struct hdem_terrain_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_terrain_stats), set by the caller             */
+    float ms_total;          /* the launch (HIP events; profiling)                            */
+    int64_t nan_cells;       /* cells whose dem is NaN                                        */
+    int64_t flat_cells;      /* cells with dzdx == 0 && dzdy == 0 (aspect -1)                 */
+    int64_t floored_cells;   /* cells whose t was below min_slope (counted when twi is wanted) */
+    int64_t invalid_codes;   /* cells whose d8 byte is no D8 code: refused                    */
+} hdem_terrain_stats;        /* sizeof == 40 */
+int hdem_terrain_f32(hdem_ctx *ctx, const float *dem, int H, int W, const uint32_t *acc,
+                     const uint8_t *d8, double dx, double dy, double z_factor, double min_slope,
+                     float *dzdx, float *dzdy, float *tangent, float *degrees, float *aspect,
+                     float *d8_slope, float *twi, float *spi, int flags,
+                     hdem_terrain_stats *stats);        /* host pointers, synchronous */
+int hdem_terrain_f32_dev(hdem_ctx *ctx, const float *dem, int H, int W, const uint32_t *acc,
+                         const uint8_t *d8, double dx, double dy, double z_factor,
+                         double min_slope, float *dzdx, float *dzdy, float *tangent,
+                         float *degrees, float *aspect, float *d8_slope, float *twi, float *spi,
+                         int flags, hdem_terrain_stats *stats);    /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
