@@ -9,9 +9,10 @@
 // centre), a = r1/den, b = -(r2+r3)/den.  It is separable:
 //     out = sum_y ( a * R2[y] + (a v_y^2 + b) * R0[y] ),
 //     R0[y] = sum_x d[y][x],  R2[y] = sum_x d[y][x] v_x^2,
-// and because sum K = 1 it is evaluated on d = w - c0 (c0 = one cell near the
-// tile centre), which keeps float32 accumulation ~1e-6 m from exact math (the
-// reference itself sits 5e-5 m from exact math: float32 s1).
+// and because sum K = 1 it is evaluated on d = w - c0 (c0 = the median of five
+// cells of the strip or tile, strip_offset), which keeps float32 accumulation
+// ~1e-6 of the elevation from exact math (the reference itself sits 5e-5 m from
+// exact math at 100 m: float32 s1).
 //
 // Two kernels evaluate it: groves_stream_kernel (ws = 3, 9, 15: the production
 // window) and the tiled groves_kernel below for the other odd sizes up to 31.
@@ -44,6 +45,39 @@ struct quad_coef {
     float cy[WS_MAX];   // a v_k^2 + b
 };
 
+// The offset c0 of a strip or tile of h x w cells at (y0, x0), and the magnitude from which a
+// staged d = w - c0 is unlike the strip.  The contract: a finite cell influences
+// only the outputs whose window holds it -- so c0 must not be whatever one cell holds (a void
+// coded -32768 there put every output of the strip on d = w + 32768: 3e-2 m off).  c0 is the
+// median of five cells spread over the extent, cells that are no number counted as +inf: up to
+// two voids or nodata cells among them leave it a cell of the terrain; with three of them
+// no numbers it is 0 and `lim` is 0.  lim = 4 max(|c0|, distance to the nearer neighbour
+// of the median among the five): a strip of the streaming kernel that stages a |d| of that
+// size is walked again in the plain form (strip_walk<PLAIN = true>).  The size follows the
+// datum, not the relief: terrain a few metres above zero with hills of ten times that in the
+// strip, and every strip that holds a void, is walked twice (what that costs).
+__device__ __forceinline__ void strip_offset(const float *__restrict__ img, int W, int y0, int x0,
+                                             int h, int w, float &c0, float &lim)
+{
+    const size_t ra = (size_t)(y0 + h / 4) * W, rb = (size_t)(y0 + h / 2) * W,
+                 rc = (size_t)(y0 + 3 * h / 4) * W;
+    const int xa = x0 + w / 4, xb = x0 + w / 2, xc = x0 + 3 * w / 4;
+    float s[5] = {img[ra + xa], img[ra + xc], img[rb + xb], img[rc + xa], img[rc + xc]};
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        if (!(fabsf(s[k]) < HDEM_INF)) s[k] = HDEM_INF;
+#define HDEM_CE(a, b) { const float lo = fminf(s[a], s[b]); s[b] = fmaxf(s[a], s[b]); s[a] = lo; }
+    HDEM_CE(0, 1) HDEM_CE(3, 4) HDEM_CE(2, 4) HDEM_CE(2, 3) HDEM_CE(1, 4)
+    HDEM_CE(0, 3) HDEM_CE(0, 2) HDEM_CE(1, 3) HDEM_CE(1, 2)
+#undef HDEM_CE
+    if (!(s[2] < HDEM_INF)) { c0 = 0.0f; lim = 0.0f; return; }
+    c0 = s[2];
+    // (a neighbour that is no number says nothing about the terrain: with two voids below the
+    // median and two no-numbers above it the distance to the void must not set the size)
+    const float below = c0 - s[1], above = s[3] < HDEM_INF ? s[3] - c0 : 0.0f;
+    lim = 4.0f * fmaxf(fabsf(c0), fminf(below, above));
+}
+
 template <int WS>
 __global__ __launch_bounds__(NT) void groves_kernel(const float *__restrict__ img,
                                                    const uint8_t *__restrict__ groves,
@@ -62,9 +96,10 @@ __global__ __launch_bounds__(NT) void groves_kernel(const float *__restrict__ im
     const int bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
     const int x0 = bx * GTW, y0 = by * GTH;
 
-    // tile offset: any finite value near the window works (sum K = 1)
-    float c0 = img[(size_t)min(y0 + GTH / 2, H - 1) * W + min(x0 + GTW / 2, W - 1)];
-    if (!(fabsf(c0) < HDEM_INF)) c0 = 0.0f;
+    // tile offset: any finite value of the terrain's size works (sum K = 1); the sums below are
+    // taken per output from the staged cells, so nothing else couples one output to another
+    float c0, lim;
+    strip_offset(img, W, y0, x0, min(GTH, H - y0), min(GTW, W - x0), c0, lim);
 
     // phase 0: stage d = w - c0 (coordinates clamped; cells that would read
     // outside the raster only feed ring outputs, which are overwritten by img)
@@ -173,42 +208,34 @@ constexpr int SR_ROWS = 128;     // strip height (output rows) unless the launch
 // waits for ALL outstanding memory operations (s_waitcnt vmcnt(0)) five times per row, which
 // drains the rows that were fetched ahead -- the general form runs that way, on the raster's
 // last strip column only.
-template <int WS, bool FULL>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void groves_stream_kernel(const float *__restrict__ img,
-                                                          const uint8_t *__restrict__ groves,
-                                                          int H, int W, float thr,
-                                                          int strips_x, int nstrips, int strip_rows,
-                                                          int sx0, quad_coef cf, float *__restrict__ out)
-{
-    constexpr int P = WS / 2;
-    constexpr int PADL = (P + 3) / 4 * 4;                 // interior starts 16-byte aligned
-    constexpr int OFF = PADL - P;                         // first needed float, from the aligned read
-    constexpr int NRD = (OFF + 4 + 2 * P + 3) / 4;        // ds_read_b128 per lane per row
-    constexpr int RB = (PADL + SW_COLS + P + 3) / 4 * 4 + 4;   // row buffer (floats)
-    constexpr int PF = WS % 5 == 0 ? 5 : 3;               // rows in flight (divides the unroll)
+template <int WS>
+struct stream_geom {
+    static constexpr int P = WS / 2;
+    static constexpr int PADL = (P + 3) / 4 * 4;          // interior starts 16-byte aligned
+    static constexpr int OFF = PADL - P;                  // first needed float, from the aligned read
+    static constexpr int NRD = (OFF + 4 + 2 * P + 3) / 4; // ds_read_b128 per lane per row
+    static constexpr int RB = (PADL + SW_COLS + P + 3) / 4 * 4 + 4;   // row buffer (floats)
+    static constexpr int PF = WS % 5 == 0 ? 5 : 3;        // rows in flight (divides the unroll)
     static_assert(WS % PF == 0 || WS < PF, "prefetch ring must divide the unroll");
-    constexpr int NSLOT = 8;                              // >= p + 1 rows of history (ws <= 15)
+    static constexpr int NSLOT = 8;                       // >= p + 1 rows of history (ws <= 15)
     static_assert(P + 1 <= NSLOT, "row ring too short");
-    __shared__ __attribute__((aligned(16))) float rows[4][NSLOT][RB];
-    // the lane's own four raw cells of the same rows: the epilogue needs the untouched centre
-    // value (the row buffer holds d = w - c0, subtracted once by the lane that wrote the cell
-    // instead of by every lane that reads it: 5 instead of 20 subtractions per lane-row)
-    __shared__ __attribute__((aligned(16))) float raw[4][NSLOT][SW_COLS];
+};
 
-    // (the wave index as a scalar: strip origin, row addresses and range tests are then scalar
-    // code instead of per-lane vector arithmetic)
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int strip = blockIdx.x * 4 + wave;
-    if (strip >= nstrips) return;
-    const int sy = strip / strips_x, sx = sx0 + strip - sy * strips_x;
-    const int x0 = sx * SW_COLS, y0 = sy * strip_rows;
+// One wave's walk down its strip at (y0, x0); `rb` / `rw` its row ring and raw-cell ring in
+// LDS.  PLAIN = false is the fast form and
+// returns whether the strip has to be walked again in the plain one (see below).
+template <int WS, bool FULL, bool PLAIN>
+__device__ __forceinline__ bool strip_walk(float *rb, float *rw, const float *__restrict__ img,
+                                           const uint8_t *__restrict__ groves,
+                                           float *__restrict__ out, int H, int W, float thr,
+                                           int strip_rows, int y0, int x0, int lane, float c0,
+                                           float lim, const quad_coef &cf)
+{
+    typedef stream_geom<WS> G;
+    constexpr int P = G::P, PADL = G::PADL, OFF = G::OFF, NRD = G::NRD, RB = G::RB, PF = G::PF,
+                  NSLOT = G::NSLOT;
     const int x = x0 + 4 * lane;
-    float *rb = &rows[wave][0][0];
-    float *rw = &raw[wave][0][0];
     const bool vec_ok = FULL || x + 4 <= W;
-
-    float c0 = img[(size_t)min(y0 + strip_rows / 2, H - 1) * W + min(x0 + SW_COLS / 2, W - 1)];
-    if (!(fabsf(c0) < HDEM_INF)) c0 = 0.0f;
 
     // halo column of this lane (lanes 0..2p-1): left halo x0-p+lane, right x0+256+(lane-p)
     const bool has_halo = lane < 2 * P;
@@ -233,11 +260,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void gr
         hv = has_halo ? row[hx] : 0.0f;
     };
 
-    // accumulators as float2 pairs: the vertical update is v_pk_add + v_pk_fma
     typedef float f2 __attribute__((ext_vector_type(2)));
-    f2 acc[WS][2];
-#pragma unroll
-    for (int j = 0; j < WS; ++j) { acc[j][0] = (f2){0.0f, 0.0f}; acc[j][1] = (f2){0.0f, 0.0f}; }
 
     // groves bytes of the output row that completes at step i (row y0 + i - 2p), fetched
     // PF steps ahead like the image rows: nothing in the loop waits on a fresh load
@@ -258,6 +281,53 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void gr
         return g;
     };
 
+    // One row ahead through LDS: iteration i puts row i + 1 into its slot and asks for the
+    // 4 + 2p values around the lane's columns, and works on row i, whose values arrived during
+    // iteration i - 1 -- the LDS round trip is off the row's critical path.
+    // Two devices below carry a value from one
+    // output to the next -- the moments slide along the row, the R2 box sum runs through a
+    // block prefix -- and a cell of 1e30, a void of -32768 or a NaN that went through them
+    // reached outputs up to three columns and ws - 1 rows beyond its window (1.3e-3 m for the
+    // void, NaN for the NaN).  A strip that holds such a cell is walked again in the plain
+    // forms (see below: the launch of PLAIN = true).
+    unsigned long long unlike = 0;                        // lanes that staged such a cell
+    auto stage_row = [&](int i, const hdem_f4 &v, float hv) {
+        float *slot = rb + (i & (NSLOT - 1)) * RB;          // d = w - c0 of image row i
+        *reinterpret_cast<hdem_f4 *>(rw + (i & (NSLOT - 1)) * SW_COLS + 4 * lane) = v;
+        const hdem_f4 dv = {v[0] - c0, v[1] - c0, v[2] - c0, v[3] - c0};
+        *reinterpret_cast<hdem_f4 *>(slot + PADL + 4 * lane) = dv;
+        const float hd = hv - c0;
+        if (has_halo) slot[hidx] = hd;
+        // (a maximum drops a NaN: those are found in the prefix, at the end of every block)
+        if (!PLAIN) {
+            const float size = fmaxf(fmaxf(fmaxf(fabsf(dv[0]), fabsf(dv[1])), fabsf(dv[2])),
+                                     fmaxf(fabsf(dv[3]), (FULL || has_halo) ? fabsf(hd) : 0.0f));
+            unlike |= __builtin_amdgcn_ballot_w64(!(size < lim));
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+    auto read_row = [&](int i, float (&d)[NRD * 4]) {
+        const float *slot = rb + (i & (NSLOT - 1)) * RB;
+#pragma unroll
+        for (int k = 0; k < NRD; ++k) {
+            const hdem_f4 q = *reinterpret_cast<const hdem_f4 *>(slot + 4 * lane + 4 * k);
+            d[4 * k] = q[0]; d[4 * k + 1] = q[1];
+            d[4 * k + 2] = q[2]; d[4 * k + 3] = q[3];
+        }
+    };
+    // The walk down the strip.  PLAIN = false is the fast form; at its end it says whether any
+    // lane has staged a cell unlike the strip (|d| >= lim) or a block's prefix was no number
+    // (a NaN or an infinity went into it): the strip is then walked once more in the plain
+    // form -- the moments of every output from its own window, R2 straight into the
+    // accumulators, nothing carried from one output to the next -- which writes every output
+    // of the strip again.  A finite cell then influences
+    // only the outputs whose window holds it.
+    const int NROWS = strip_rows + 2 * P;
+    // accumulators as float2 pairs: the vertical update is v_pk_add + v_pk_fma
+    f2 acc[WS][2];
+#pragma unroll
+    for (int j = 0; j < WS; ++j) { acc[j][0] = (f2){0.0f, 0.0f}; acc[j][1] = (f2){0.0f, 0.0f}; }
     // R2 enters all ws pending output rows with weight 1 -- a vertical box sum.  Instead of ws
     // packed adds per row: one running prefix PT of the rows' R2 inside the current block of ws
     // rows (the unrolled loop body).  A slot is opened at -PT, takes +PT(end of block) when the
@@ -271,33 +341,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void gr
 #pragma unroll
     for (int k = 0; k < PF; ++k) { load_row(k, pre[k], preh[k]); preg[k] = load_mask(k); }
 
-    // One row ahead through LDS: iteration i puts row i + 1 into its slot and asks for the
-    // 4 + 2p values around the lane's columns, and works on row i, whose values arrived during
-    // iteration i - 1 -- the LDS round trip is off the row's critical path.
-    auto stage_row = [&](int i, const hdem_f4 &v, float hv) {
-        float *slot = rb + (i & (NSLOT - 1)) * RB;          // d = w - c0 of image row i
-        *reinterpret_cast<hdem_f4 *>(rw + (i & (NSLOT - 1)) * SW_COLS + 4 * lane) = v;
-        const hdem_f4 dv = {v[0] - c0, v[1] - c0, v[2] - c0, v[3] - c0};
-        *reinterpret_cast<hdem_f4 *>(slot + PADL + 4 * lane) = dv;
-        if (has_halo) slot[hidx] = hv - c0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    auto read_row = [&](int i, float (&d)[NRD * 4]) {
-        const float *slot = rb + (i & (NSLOT - 1)) * RB;
-#pragma unroll
-        for (int k = 0; k < NRD; ++k) {
-            const hdem_f4 q = *reinterpret_cast<const hdem_f4 *>(slot + 4 * lane + 4 * k);
-            d[4 * k] = q[0]; d[4 * k + 1] = q[1];
-            d[4 * k + 2] = q[2]; d[4 * k + 3] = q[3];
-        }
-    };
     float d[NRD * 4];
     stage_row(0, pre[0], preh[0]);
     load_row(PF, pre[0], preh[0]);
     read_row(0, d);
 
-    const int NROWS = strip_rows + 2 * P;
     for (int base = 0; base < NROWS; base += WS) {
 #pragma unroll
         for (int u = 0; u < WS; ++u) {
@@ -321,9 +369,28 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void gr
             // (a leaves the window, e enters): 78 operations per lane-row instead of 120.
             // The offsets d = w - c0 are a few metres, M2 ~ 1e5: 1e-5 m after the a = 3e-4.
             float r0[4], r2[4];
-            {
-                constexpr float V0 = 1.0f - WS / 2.0f, NN = (float)WS, N2 = (float)(WS * WS - 2 * WS);
-                const float a0 = cf.a * (V0 * V0), a1 = cf.a * (2.0f * V0);
+            constexpr float V0 = 1.0f - WS / 2.0f, NN = (float)WS, N2 = (float)(WS * WS - 2 * WS);
+            const float a0 = cf.a * (V0 * V0), a1 = cf.a * (2.0f * V0);
+            if (PLAIN) {
+                // the moments of every output from its own window: a cell stays out of the
+                // outputs whose window it left
+#pragma unroll
+                for (int o = 0; o < 4; ++o) {
+                    float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < WS; ++k) {
+                        const float x = d[OFF + o + k];
+                        m0 += x;
+                        m1 = fmaf((float)k, x, m1);
+                        m2 = fmaf((float)(k * k), x, m2);
+                    }
+                    r0[o] = m0;
+                    r2[o] = fmaf(a0, m0, fmaf(a1, m1, cf.a * m2));
+                    // (one output after the other: interleaved, the four sets of moments push
+                    // the kernel past its registers and the fast walk pays for the spills too)
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            } else {
                 float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
 #pragma unroll
                 for (int k = 0; k < WS; ++k) {
@@ -352,7 +419,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void gr
                 // (all the adds, then all the fmas: written as add-then-fma per slot the
                 // compiler reuses one temporary, and a packed fma that consumes the packed
                 // add just before it needs a wait state -- 30 s_nop per row)
-                pt[p2] += t;
+                if (PLAIN) {
+                    // R2 straight into the slots: no prefix (it stays 0) that could carry a
+                    // row into a slot that opens after it
+#pragma unroll
+                    for (int j = 0; j < WS; ++j) acc[j][p2] += t;
+                } else {
+                    pt[p2] += t;
+                }
 #pragma unroll
                 for (int j = 0; j < WS; ++j) {
                     // output row (i - j) sits in slot (u - j) mod WS and takes weight cy[j]
@@ -366,6 +440,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void gr
             if (u == WS - 1) {
                 // the block ends: its R2 total goes to every open slot (the completing one
                 // opened with the block), and the prefix starts again
+                if (!PLAIN) {                             // a NaN or an infinity went into it
+                    const float all = (pt[0][0] + pt[0][1]) + (pt[1][0] + pt[1][1]);
+                    unlike |= __builtin_amdgcn_ballot_w64(!(fabsf(all) < HDEM_INF));
+                }
 #pragma unroll
                 for (int j = 0; j < WS; ++j) { acc[j][0] += pt[0]; acc[j][1] += pt[1]; }
                 pt[0] = (f2){0.0f, 0.0f};
@@ -412,6 +490,46 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void gr
             for (int k = 0; k < NRD * 4; ++k) d[k] = dn[k];
         }
     }
+    // (asked once, after the walk: an exit from inside the loop costs the fast form registers)
+    return !PLAIN && unlike != 0;
+}
+
+// The kernel.  PLAIN = false walks every strip in the fast form and leaves in `redo` which
+// strips have to be walked again; a launch of PLAIN = true behind it walks those (a launch of
+// its own: inlined behind the fast walk, the plain one cost the kernel its registers -- 159
+// spilled -- and a strip with nothing to redo leaves at once).
+template <int WS, bool FULL, bool PLAIN>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void groves_stream_kernel(const float *__restrict__ img,
+                                                          const uint8_t *__restrict__ groves,
+                                                          int H, int W, float thr,
+                                                          int strips_x, int nstrips, int strip_rows,
+                                                          int sx0, quad_coef cf, uint8_t *redo,
+                                                          float *__restrict__ out)
+{
+    typedef stream_geom<WS> G;
+    __shared__ __attribute__((aligned(16))) float rows[4][G::NSLOT][G::RB];
+    // the lane's own four raw cells of the same rows: the epilogue needs the untouched centre
+    // value (the row buffer holds d = w - c0, subtracted once by the lane that wrote the cell
+    // instead of by every lane that reads it: 5 instead of 20 subtractions per lane-row)
+    __shared__ __attribute__((aligned(16))) float raw[4][G::NSLOT][SW_COLS];
+
+    // (the wave index as a scalar: strip origin, row addresses and range tests are then scalar
+    // code instead of per-lane vector arithmetic)
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int strip = blockIdx.x * 4 + wave;
+    if (strip >= nstrips) return;
+    if (PLAIN && !redo[strip]) return;
+    const int sy = strip / strips_x, sx = sx0 + strip - sy * strips_x;
+    const int x0 = sx * SW_COLS, y0 = sy * strip_rows;
+    float *rb = &rows[wave][0][0];
+    float *rw = &raw[wave][0][0];
+
+    float c0, lim;
+    strip_offset(img, W, y0, x0, min(strip_rows, H - y0), min(SW_COLS, W - x0), c0, lim);
+
+    const bool again = strip_walk<WS, FULL, PLAIN>(rb, rw, img, groves, out, H, W, thr, strip_rows,
+                                                   y0, x0, lane, c0, lim, cf);
+    if (!PLAIN && lane == 0) redo[strip] = again;
 }
 
 int make_coef(int ws, quad_coef *cf)
@@ -435,7 +553,7 @@ int make_coef(int ws, quad_coef *cf)
 
 template <int WS>
 void launch_ws(hdem_ctx *ctx, const float *img, const uint8_t *groves, int H, int W,
-               float thr, const quad_coef &cf, float *out)
+               float thr, const quad_coef &cf, uint8_t *redo, float *out)
 {
     if constexpr (WS == 15 || WS == 9 || WS == 3) {      // streaming form (prefetch ring | ws)
         // Strip height: every strip is one wave's serial walk, and the machine holds 8 of them
@@ -456,13 +574,27 @@ void launch_ws(hdem_ctx *ctx, const float *img, const uint8_t *groves, int H, in
         const int sy = (H + rows - 1) / rows;
         // strip columns that lie inside the raster take the branch-free form (see the kernel)
         const int fx = (W % 4 == 0 && ((uintptr_t)groves % 4 == 0)) ? W / SW_COLS : 0;
+        // (one byte of `redo` per strip: the branch-free columns' strips first)
+        uint8_t *redo_rest = redo + (size_t)fx * sy;
         if (fx > 0)
-            hipLaunchKernelGGL((groves_stream_kernel<WS, true>), dim3((fx * sy + 3) / 4), dim3(NT), 0,
-                               ctx->stream, img, groves, H, W, thr, fx, fx * sy, rows, 0, cf, out);
+            hipLaunchKernelGGL((groves_stream_kernel<WS, true, false>), dim3((fx * sy + 3) / 4),
+                               dim3(NT), 0, ctx->stream, img, groves, H, W, thr, fx, fx * sy, rows,
+                               0, cf, redo, out);
         if (sx > fx)
-            hipLaunchKernelGGL((groves_stream_kernel<WS, false>), dim3(((sx - fx) * sy + 3) / 4),
-                               dim3(NT), 0, ctx->stream, img, groves, H, W, thr, sx - fx,
-                               (sx - fx) * sy, rows, fx, cf, out);
+            hipLaunchKernelGGL((groves_stream_kernel<WS, false, false>),
+                               dim3(((sx - fx) * sy + 3) / 4), dim3(NT), 0, ctx->stream, img,
+                               groves, H, W, thr, sx - fx, (sx - fx) * sy, rows, fx, cf, redo_rest,
+                               out);
+        // the strips that hold a cell unlike their surroundings, once more in the plain form
+        if (fx > 0)
+            hipLaunchKernelGGL((groves_stream_kernel<WS, true, true>), dim3((fx * sy + 3) / 4),
+                               dim3(NT), 0, ctx->stream, img, groves, H, W, thr, fx, fx * sy, rows,
+                               0, cf, redo, out);
+        if (sx > fx)
+            hipLaunchKernelGGL((groves_stream_kernel<WS, false, true>),
+                               dim3(((sx - fx) * sy + 3) / 4), dim3(NT), 0, ctx->stream, img,
+                               groves, H, W, thr, sx - fx, (sx - fx) * sy, rows, fx, cf, redo_rest,
+                               out);
         return;
     }
     int tx = (W + GTW - 1) / GTW, ty = (H + GTH - 1) / GTH;
@@ -471,11 +603,11 @@ void launch_ws(hdem_ctx *ctx, const float *img, const uint8_t *groves, int H, in
 }
 
 int launch_pass(hdem_ctx *ctx, const float *img, const uint8_t *groves, int H, int W,
-                int ws, float thr, const quad_coef &cf, float *out)
+                int ws, float thr, const quad_coef &cf, uint8_t *redo, float *out)
 {
     hdem_scoped_timer tm(ctx, HDEM_K_GROVES, (int64_t)H * W);
     switch (ws) {
-#define HDEM_WS_CASE(N) case N: launch_ws<N>(ctx, img, groves, H, W, thr, cf, out); break;
+#define HDEM_WS_CASE(N) case N: launch_ws<N>(ctx, img, groves, H, W, thr, cf, redo, out); break;
         HDEM_WS_CASE(3) HDEM_WS_CASE(5) HDEM_WS_CASE(7)
         HDEM_WS_CASE(9) HDEM_WS_CASE(11) HDEM_WS_CASE(13) HDEM_WS_CASE(15)
         HDEM_WS_CASE(17) HDEM_WS_CASE(19) HDEM_WS_CASE(21) HDEM_WS_CASE(23)
@@ -486,6 +618,14 @@ int launch_pass(hdem_ctx *ctx, const float *img, const uint8_t *groves, int H, i
             return HDEM_ERR_BAD_ARG;
     }
     return HDEM_OK;
+}
+
+// One byte per strip of the streaming kernel at its smallest strip height (the other windows
+// take the tiled kernel, which has nothing to redo: one byte).
+size_t redo_bytes(int ws, int H, int W)
+{
+    if (ws != 3 && ws != 9 && ws != 15) return 1;
+    return (size_t)((W + SW_COLS - 1) / SW_COLS) * ((H + 95) / 96);
 }
 
 // the shared window rule between what only these kernels ask of a window
@@ -516,11 +656,14 @@ extern "C" int hdem_groves_f32_dev(hdem_ctx *ctx, const float *img, const uint8_
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     quad_coef cf;
     make_coef(ws, &cf);
+    hdem_dbuf redo;
+    if (int rc = redo.alloc(ctx, redo_bytes(ws, H, W))) return rc;
     // ping-pong so that the last pass lands in `out`
     const float *src = img;
     for (int it = 0; it < iters; ++it) {
         float *dst = ((iters - 1 - it) % 2 == 0) ? out : scratch;
-        if (int rc = launch_pass(ctx, src, groves, H, W, ws, thr, cf, dst)) return rc;
+        if (int rc = launch_pass(ctx, src, groves, H, W, ws, thr, cf, redo.as<uint8_t>(), dst))
+            return rc;
         src = dst;
     }
     HDEM_HIP_CHECK(hipGetLastError());
@@ -536,7 +679,10 @@ extern "C" int hdem_quadratic_f32_dev(hdem_ctx *ctx, const float *dem, int H, in
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     quad_coef cf;
     make_coef(ws, &cf);
-    if (int rc = launch_pass(ctx, dem, nullptr, H, W, ws, 0.0f, cf, out)) return rc;
+    hdem_dbuf redo;
+    if (int rc = redo.alloc(ctx, redo_bytes(ws, H, W))) return rc;
+    if (int rc = launch_pass(ctx, dem, nullptr, H, W, ws, 0.0f, cf, redo.as<uint8_t>(), out))
+        return rc;
     HDEM_HIP_CHECK(hipGetLastError());
     return HDEM_OK;
 }
