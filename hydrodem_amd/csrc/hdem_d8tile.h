@@ -5,6 +5,8 @@
 // B's result.  What A, B and C do, and with how many threads, is each operator's own.
 // Watersheds and the flow trace resolve their forest by pointer jumping and share its
 // schedule, its count of unresolved nodes and its counters; flow accumulation counts arrivals.
+// Every tiled operator, the ones without a forest too, takes the tile of a workgroup, the event
+// timer, the stream-set check and the stats helpers from here.
 #pragma once
 
 #include "hdem_internal.h"
@@ -18,6 +20,18 @@ constexpr int PER = 4 * TS - 4;       // perimeter slots per tile
 constexpr int DOUBLINGS = 12;         // 2^12 >= the longest path inside a tile (4095 steps)
 constexpr int MAX_ROUNDS = 32;        // forest launches: slots < 2^31
 constexpr uint16_t T_EXIT = 0x8000;   // per-cell target: perimeter slot of the exit reached
+
+// float -> uint32 whose unsigned order is the floats' order: -0.0 below +0.0.
+// What the depression table and the zonal statistics gather a float minimum or maximum as.
+__device__ __forceinline__ uint32_t key_of(float f)
+{
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : b | 0x80000000u;
+}
+__device__ __forceinline__ float float_of(uint32_t k)
+{
+    return __uint_as_float((k & 0x80000000u) ? k & 0x7FFFFFFFu : ~k);
+}
 
 // bit b of a code -> (dy, dx), packed (d + 1) in 4 bits per entry; odd bits are diagonal
 __device__ __forceinline__ int code_dy(int b) { return ((0x00012221u >> (4 * b)) & 3) - 1; }
@@ -150,34 +164,65 @@ inline int d8_grid_of(const char *op, int H, int W, d8_grid *g)
     return HDEM_OK;
 }
 
-// HIP-event times of the phases A, B, C, taken when the context profiles and the caller wants
-// stats.  The events go with the object, whichever way the call returns.
-struct d8_phase_timer {
-    hipEvent_t ev[4] = {};
+// HIP-event times between N marks on the context's stream, taken when the context profiles and
+// the caller wants stats.  The events go with the object, whichever way the call returns.
+template <int N>
+struct hdem_event_timer {
+    hipEvent_t ev[N] = {};
     hipStream_t stream;
     bool on;
-    d8_phase_timer(const hdem_ctx *ctx, bool wanted)
+    hdem_event_timer(const hdem_ctx *ctx, bool wanted)
         : stream(ctx->stream), on(ctx->profiling && wanted) {}
-    d8_phase_timer(const d8_phase_timer &) = delete;
-    ~d8_phase_timer()
+    hdem_event_timer(const hdem_event_timer &) = delete;
+    ~hdem_event_timer()
     {
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
     int start()
     {
-        for (int k = 0; on && k < 4; ++k) HDEM_HIP_CHECK(hipEventCreate(&ev[k]));
+        for (int k = 0; on && k < N; ++k) HDEM_HIP_CHECK(hipEventCreate(&ev[k]));
         return HDEM_OK;
     }
     void mark(int k) { if (on) (void)hipEventRecord(ev[k], stream); }
-    void read(float *ms_tile, float *ms_forest, float *ms_final) const   // after a synchronise
+    float ms(int from, int to) const   // after a synchronise; 0 when the timer is off
     {
-        if (!on) return;
-        (void)hipEventElapsedTime(ms_tile, ev[0], ev[1]);
-        (void)hipEventElapsedTime(ms_forest, ev[1], ev[2]);
-        (void)hipEventElapsedTime(ms_final, ev[2], ev[3]);
+        float t = 0.f;
+        if (on) (void)hipEventElapsedTime(&t, ev[from], ev[to]);
+        return t;
+    }
+    // the phases A, B, C between four marks; what they point at stays when the timer is off
+    void read(float *ms_a, float *ms_b, float *ms_c) const
+    {
+        static_assert(N >= 4, "three phases take four marks");
+        if (on) *ms_a = ms(0, 1), *ms_b = ms(1, 2), *ms_c = ms(2, 3);
     }
 };
+
+// The stream set of the flow trace, the stream order and the stream network: what `streams` and
+// `threshold` must be for each HDEM_FT_STREAMS_* kind.
+inline int d8_check_streams(const void *streams, int stream_kind, uint32_t threshold)
+{
+    switch (stream_kind) {
+    case HDEM_FT_STREAMS_NONE:
+        HDEM_REQUIRE(!streams && !threshold, HDEM_ERR_BAD_ARG,
+                     "streams and threshold must be null and 0 with HDEM_FT_STREAMS_NONE");
+        break;
+    case HDEM_FT_STREAMS_MASK_U8:
+        HDEM_REQUIRE(streams, HDEM_ERR_BAD_ARG, "the stream mask is null");
+        HDEM_REQUIRE(!threshold, HDEM_ERR_BAD_ARG,
+                     "a uint8 stream mask takes no threshold (got %u)", threshold);
+        break;
+    case HDEM_FT_STREAMS_ACC_U32:
+        HDEM_REQUIRE(streams, HDEM_ERR_BAD_ARG, "the stream raster is null");
+        HDEM_REQUIRE(threshold >= 1, HDEM_ERR_BAD_ARG,
+                     "a uint32 stream raster needs a threshold >= 1");
+        break;
+    default:
+        HDEM_REQUIRE(false, HDEM_ERR_BAD_ARG, "unknown stream kind %d", stream_kind);
+    }
+    return HDEM_OK;
+}
 
 // What the caller's stats struct has room for (its struct_size) is filled, and nothing beyond.
 template <class Stats>

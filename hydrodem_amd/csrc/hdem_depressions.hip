@@ -26,9 +26,10 @@
 //   C2  (depr_final_kernel)   streaming: label -> tile root -> root.  Only true roots are
 //       written and roots do not change in C, so whatever a racing reader sees is an ancestor.
 //       Compact mode: also one bit per cell "is a root" and the count per 64-cell word.
-//   N   (depr_scan_* / depr_relabel_kernel)  compact mode: exclusive scan of the word counts
-//       (block sums, one workgroup over the sums, apply), then rank of a root = scanned count
-//       of its word + popcount of the bits in front of it; label = 1 + rank of the cell's root.
+//   N   (hdem_scan.h / depr_relabel_kernel)  compact mode: the shared exclusive scan of the word
+//       counts (chunk sums, one workgroup over the sums, apply), then rank of a root = scanned
+//       count of its word + popcount of the bits in front of it; label = 1 + rank of the
+//       cell's root.
 // Table (hdem_depression_table_f32): one pass over dem, filled and compact labels; a
 // workgroup gathers its tile per label in an LDS hash table (a tile holds at most 1 024
 // components, the table has 1 024 slots), then one global atomic per (tile, label, column).
@@ -38,16 +39,13 @@
 // Workspace (arena): compact mode 12 B per 64 cells (bitmap + counts); first mode and the
 // table 512 B.
 #include "hdem_d8tile.h"
+#include "hdem_scan.h"
 
 namespace {
 
 constexpr int NT = 256;               // threads of the seam, roots, final and table workgroups
 constexpr int ANT = 512;              // threads of the tile workgroup (8 rows per pass)
 constexpr uint32_t NONE = 0xFFFFFFFFu;
-constexpr int SCAN_NT = 256;
-constexpr int SCAN_PER = 16;          // elements per thread of the scan
-constexpr int SCAN_CHUNK = SCAN_NT * SCAN_PER;
-constexpr int ONE_NT = 1024;          // the one workgroup over the block sums
 constexpr int SLOTS = 1024;           // hash slots of the table kernel: >= components per tile
 constexpr size_t HEAD = 512;          // bytes of the counter block in front of the arena
 
@@ -348,82 +346,6 @@ __global__ __launch_bounds__(NT) void depr_final_kernel(int H, int W, int tiles_
     }
 }
 
-// N: exclusive scan of count[0 .. n), in place.  sums: one workgroup per chunk; one: the one
-// workgroup over the chunk sums; apply: the scan inside each chunk plus its offset.
-__global__ __launch_bounds__(SCAN_NT) void depr_scan_sums_kernel(const uint32_t *__restrict__ count,
-                                                                 int64_t n,
-                                                                 uint32_t *__restrict__ sums)
-{
-    __shared__ uint32_t s_sum;
-    if (threadIdx.x == 0) s_sum = 0;
-    __syncthreads();
-    const int64_t lo = (int64_t)blockIdx.x * SCAN_CHUNK;
-    uint32_t sum = 0;
-    for (int k = 0; k < SCAN_PER; ++k) {
-        const int64_t i = lo + k * SCAN_NT + threadIdx.x;
-        if (i < n) sum += count[i];
-    }
-    for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
-    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&s_sum, sum);
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = s_sum;
-}
-
-__global__ __launch_bounds__(ONE_NT) void depr_scan_one_kernel(uint32_t *__restrict__ sums,
-                                                               int64_t n)
-{
-    __shared__ uint32_t part[ONE_NT];
-    const int tid = threadIdx.x;
-    const int64_t chunk = (n + ONE_NT - 1) / ONE_NT;
-    const int64_t lo = tid * chunk < n ? tid * chunk : n;
-    const int64_t hi = lo + chunk < n ? lo + chunk : n;
-    uint32_t sum = 0;
-    for (int64_t t = lo; t < hi; ++t) sum += sums[t];
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < ONE_NT; d <<= 1) {
-        const uint32_t add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[tid] - sum;
-    for (int64_t t = lo; t < hi; ++t) {
-        const uint32_t v = sums[t];
-        sums[t] = run;
-        run += v;
-    }
-}
-
-__global__ __launch_bounds__(SCAN_NT) void depr_scan_apply_kernel(uint32_t *__restrict__ count,
-                                                                  int64_t n,
-                                                                  const uint32_t *__restrict__ sums)
-{
-    __shared__ uint32_t part[SCAN_NT];
-    const int tid = threadIdx.x;
-    // a thread takes SCAN_PER consecutive elements
-    const int64_t lo = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)tid * SCAN_PER;
-    uint32_t v[SCAN_PER];
-    uint32_t sum = 0;
-    for (int k = 0; k < SCAN_PER; ++k) {
-        v[k] = lo + k < n ? count[lo + k] : 0u;
-        sum += v[k];
-    }
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < SCAN_NT; d <<= 1) {
-        const uint32_t add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = sums[blockIdx.x] + part[tid] - sum;
-    for (int k = 0; k < SCAN_PER; ++k) {
-        if (lo + k < n) count[lo + k] = run;
-        run += v[k];
-    }
-}
-
 // label 1 + first -> 1 + rank of that root.  A thread reads no label but its own cell's.
 __global__ __launch_bounds__(NT) void depr_relabel_kernel(int64_t cells, int W, int tiles_x,
                                                           const unsigned long long *__restrict__ bits,
@@ -437,24 +359,13 @@ __global__ __launch_bounds__(NT) void depr_relabel_kernel(int64_t cells, int W, 
         const uint32_t r = l - 1u;
         const uint32_t ry = r / (uint32_t)W, rx = r - ry * (uint32_t)W;
         const size_t w = (size_t)ry * tiles_x + rx / TS;
-        out[c] = 1u + before[w] + (uint32_t)__popcll(bits[w] & ((1ull << (rx % TS)) - 1));
+        out[c] = 1u + hdem_rank_in(bits[w], (int)(rx % TS), before[w]);
     }
 }
 
 // ---------------------------------------------------------------------------
 // the table
 // ---------------------------------------------------------------------------
-// float -> uint32 whose unsigned order is the floats' order
-__device__ __forceinline__ uint32_t key_of(float f)
-{
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : b | 0x80000000u;
-}
-__device__ __forceinline__ float float_of(uint32_t k)
-{
-    return __uint_as_float((k & 0x80000000u) ? k & 0x7FFFFFFFu : ~k);
-}
-
 __global__ __launch_bounds__(NT) void depr_table_init_kernel(int64_t K, uint32_t *first,
                                                              uint32_t *area, uint32_t *level,
                                                              uint32_t *depth,
@@ -637,20 +548,15 @@ extern "C" int hdem_depressions_f32_dev(hdem_ctx *ctx, const float *dem, const f
     hdem_depressions_stats st = {};
     d8_publish(stats, st);
 
-    // arena: counters | root bits u64 per word | counts u32 per word | chunk sums u32
+    // arena: counters | the rank table of the root bits (compact mode)
     const int64_t words = compact ? (int64_t)H * g.tiles_x : 0;
-    const int64_t chunks = (words + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    const size_t bytes = HEAD + (size_t)words * 8 + hdem_round16((size_t)words * 4) +
-                         (size_t)chunks * 4;
-    char *ws = static_cast<char *>(hdem_arena(ctx, bytes));
+    char *ws = static_cast<char *>(hdem_arena(ctx, HEAD + hdem_rank_table_bytes(words)));
     if (!ws) return HDEM_ERR_OOM;
     depr_counters *cnt = reinterpret_cast<depr_counters *>(ws);
-    unsigned long long *bits = reinterpret_cast<unsigned long long *>(ws + HEAD);
-    uint32_t *count = reinterpret_cast<uint32_t *>(bits + words);
-    uint32_t *sums = reinterpret_cast<uint32_t *>(ws + HEAD + (size_t)words * 8 +
-                                                   hdem_round16((size_t)words * 4));
+    hdem_rank_table rank;
+    hdem_rank_table_at(ws + HEAD, words, &rank);
 
-    d8_phase_timer phases(ctx, stats != nullptr);
+    hdem_event_timer<4> phases(ctx, stats != nullptr);
     if (int rc = phases.start()) return rc;
 
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, HEAD, ctx->stream));
@@ -670,20 +576,15 @@ extern "C" int hdem_depressions_f32_dev(hdem_ctx *ctx, const float *dem, const f
                            labels, cnt);
     if (compact) {
         hipLaunchKernelGGL(depr_final_kernel<true>, grid, dim3(NT), 0, ctx->stream, H, W,
-                           g.tiles_x, labels, bits, count, cnt);
-        hipLaunchKernelGGL(depr_scan_sums_kernel, dim3((unsigned)chunks), dim3(SCAN_NT), 0,
-                           ctx->stream, count, words, sums);
-        hipLaunchKernelGGL(depr_scan_one_kernel, dim3(1), dim3(ONE_NT), 0, ctx->stream, sums,
-                           chunks);
-        hipLaunchKernelGGL(depr_scan_apply_kernel, dim3((unsigned)chunks), dim3(SCAN_NT), 0,
-                           ctx->stream, count, words, sums);
+                           g.tiles_x, labels, rank.bits, rank.count, cnt);
+        hdem_scan_exclusive(ctx->stream, rank.count, words, rank.sums);
         const int relabel_grid =
             (int)std::min<int64_t>((cells + NT - 1) / NT, (int64_t)ctx->num_cus * 8);
         hipLaunchKernelGGL(depr_relabel_kernel, dim3(relabel_grid), dim3(NT), 0, ctx->stream,
-                           cells, W, g.tiles_x, bits, count, labels);
+                           cells, W, g.tiles_x, rank.bits, rank.count, labels);
     } else {
         hipLaunchKernelGGL(depr_final_kernel<false>, grid, dim3(NT), 0, ctx->stream, H, W,
-                           g.tiles_x, labels, bits, count, cnt);
+                           g.tiles_x, labels, rank.bits, rank.count, cnt);
     }
     phases.mark(3);
     HDEM_HIP_CHECK(hipGetLastError());

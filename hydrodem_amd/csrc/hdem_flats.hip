@@ -309,7 +309,7 @@ extern "C" int hdem_resolve_flats_u8_dev(hdem_ctx *ctx, const uint8_t *d8, const
     uint32_t *stamp = active + tiles, *list = stamp + tiles;
     uint32_t *work = dist ? dist : list + tiles;
 
-    d8_phase_timer phases(ctx, stats != nullptr);
+    hdem_event_timer<4> phases(ctx, stats != nullptr);
     if (int rc = phases.start()) return rc;
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(flats_counters), ctx->stream));
     const dim3 grid((unsigned)tiles);

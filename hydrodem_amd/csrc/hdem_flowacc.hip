@@ -272,7 +272,7 @@ extern "C" int hdem_flowacc_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int 
     int32_t *tgt = link + nslots;
     int32_t *next = tgt + nslots;
 
-    d8_phase_timer phases(ctx, stats != nullptr);
+    hdem_event_timer<4> phases(ctx, stats != nullptr);
     if (int rc = phases.start()) return rc;
 
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(flowacc_counters), ctx->stream));

@@ -301,24 +301,7 @@ int check_args(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *strea
     HDEM_REQUIRE(stop || ncard || ndiag || distance || hand, HDEM_ERR_BAD_ARG,
                  "no output wanted: give at least one of stop, ncard, ndiag, distance, hand");
     HDEM_REQUIRE(!hand || dem, HDEM_ERR_BAD_ARG, "hand needs the dem it is measured on");
-    switch (stream_kind) {
-    case HDEM_FT_STREAMS_NONE:
-        HDEM_REQUIRE(!streams && !threshold, HDEM_ERR_BAD_ARG,
-                     "streams and threshold must be null and 0 with HDEM_FT_STREAMS_NONE");
-        break;
-    case HDEM_FT_STREAMS_MASK_U8:
-        HDEM_REQUIRE(streams, HDEM_ERR_BAD_ARG, "the stream mask is null");
-        HDEM_REQUIRE(!threshold, HDEM_ERR_BAD_ARG,
-                     "a uint8 stream mask takes no threshold (got %u)", threshold);
-        break;
-    case HDEM_FT_STREAMS_ACC_U32:
-        HDEM_REQUIRE(streams, HDEM_ERR_BAD_ARG, "the stream raster is null");
-        HDEM_REQUIRE(threshold >= 1, HDEM_ERR_BAD_ARG,
-                     "a uint32 stream raster needs a threshold >= 1");
-        break;
-    default:
-        HDEM_REQUIRE(false, HDEM_ERR_BAD_ARG, "unknown stream kind %d", stream_kind);
-    }
+    if (int rc = d8_check_streams(streams, stream_kind, threshold)) return rc;
     HDEM_REQUIRE(std::isfinite(cellsize) && cellsize > 0.0, HDEM_ERR_BAD_ARG,
                  "cellsize must be finite and positive, got %g", cellsize);
     return d8_check_stats(stats, "hdem_flowtrace_stats");
@@ -364,7 +347,7 @@ extern "C" int hdem_flowtrace_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
     uint32_t *counts = reinterpret_cast<uint32_t *>(node[1] + nslots);
     uint16_t *target = reinterpret_cast<uint16_t *>(counts + (size_t)tiles * TC);
 
-    d8_phase_timer phases(ctx, stats != nullptr);
+    hdem_event_timer<4> phases(ctx, stats != nullptr);
     if (int rc = phases.start()) return rc;
 
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(flowtrace_counters), ctx->stream));

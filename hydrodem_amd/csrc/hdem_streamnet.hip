@@ -5,12 +5,11 @@
 // flat index of the last cell, the *end*, of c's link), K = the number of links, and, as the
 // columns ask for them, the order and magnitude rasters and a dem.  The links are numbered
 // 0 ... K - 1 in ascending flat index of their end; row r of every column describes link r.
-//   1  (streamnet_ends_kernel, streamnet_scan_*)  ends and ranks.  One bit per cell "is its own
+//   1  (streamnet_ends_kernel, hdem_scan.h)  ends and ranks.  One bit per cell "is its own
 //      end" in 64-cell words (a tile row is a wave: one ballot), the count per word, an
 //      exclusive scan of the counts; rank of an end = scanned count of its word + popcount of
-//      the bits in front of it.  The three scan kernels are those of hdem_depressions.hip
-//      (DESIGN 3.14 step N), kept as a private copy here so that the objects of that file stay
-//      byte for byte what they were.
+//      the bits in front of it.  The scan, the rank lookup and the table's views are the shared
+//      ones of hdem_scan.h.
 //   2  hdem_flowtrace_u8_dev with the caller's streams and `stop` alone: the first stream cell
 //      of every cell.  Only when `catchment` is wanted, and not when every cell is a stream
 //      cell (a cell is then its own first stream cell and there is nothing to trace).
@@ -35,6 +34,7 @@
 // cells behind the flow trace's own bytes when step 2 runs, 8 B per link when `length` is
 // wanted without `ncard` and `ndiag`.
 #include "hdem_d8tile.h"
+#include "hdem_scan.h"
 
 #include <cmath>
 
@@ -43,10 +43,6 @@ namespace {
 constexpr int NT = 256;               // threads per workgroup, all kernels but the scan's one
 constexpr int HL = TS + 2;            // staged rasters: the tile and one ring
 constexpr uint32_t NONE = 0xFFFFFFFFu;
-constexpr int SCAN_NT = 256;
-constexpr int SCAN_PER = 16;          // elements per thread of the scan
-constexpr int SCAN_CHUNK = SCAN_NT * SCAN_PER;
-constexpr int ONE_NT = 1024;          // the one workgroup over the block sums
 constexpr int SLOTS = 4096;           // table slots of the tile kernel: a cell adds to one row
 constexpr size_t HEAD = 256;          // bytes of the counter block
 
@@ -104,80 +100,6 @@ __global__ __launch_bounds__(NT) void streamnet_ends_kernel(int H, int W, int ti
     if (tid == 0 && s_ends) atomicAdd(&cnt->ends, (unsigned long long)s_ends);
 }
 
-// Exclusive scan of count[0 .. n), in place.  sums: one workgroup per chunk; one: the one
-// workgroup over the chunk sums; apply: the scan inside each chunk plus its offset.
-__global__ __launch_bounds__(SCAN_NT) void streamnet_scan_sums_kernel(
-    const uint32_t *__restrict__ count, int64_t n, uint32_t *__restrict__ sums)
-{
-    __shared__ uint32_t s_sum;
-    if (threadIdx.x == 0) s_sum = 0;
-    __syncthreads();
-    const int64_t lo = (int64_t)blockIdx.x * SCAN_CHUNK;
-    uint32_t sum = 0;
-    for (int k = 0; k < SCAN_PER; ++k) {
-        const int64_t i = lo + k * SCAN_NT + threadIdx.x;
-        if (i < n) sum += count[i];
-    }
-    for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
-    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&s_sum, sum);
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = s_sum;
-}
-
-__global__ __launch_bounds__(ONE_NT) void streamnet_scan_one_kernel(uint32_t *__restrict__ sums,
-                                                                    int64_t n)
-{
-    __shared__ uint32_t part[ONE_NT];
-    const int tid = threadIdx.x;
-    const int64_t chunk = (n + ONE_NT - 1) / ONE_NT;
-    const int64_t lo = tid * chunk < n ? tid * chunk : n;
-    const int64_t hi = lo + chunk < n ? lo + chunk : n;
-    uint32_t sum = 0;
-    for (int64_t t = lo; t < hi; ++t) sum += sums[t];
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < ONE_NT; d <<= 1) {
-        const uint32_t add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[tid] - sum;
-    for (int64_t t = lo; t < hi; ++t) {
-        const uint32_t v = sums[t];
-        sums[t] = run;
-        run += v;
-    }
-}
-
-__global__ __launch_bounds__(SCAN_NT) void streamnet_scan_apply_kernel(
-    uint32_t *__restrict__ count, int64_t n, const uint32_t *__restrict__ sums)
-{
-    __shared__ uint32_t part[SCAN_NT];
-    const int tid = threadIdx.x;
-    // a thread takes SCAN_PER consecutive elements
-    const int64_t lo = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)tid * SCAN_PER;
-    uint32_t v[SCAN_PER];
-    uint32_t sum = 0;
-    for (int k = 0; k < SCAN_PER; ++k) {
-        v[k] = lo + k < n ? count[lo + k] : 0u;
-        sum += v[k];
-    }
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < SCAN_NT; d <<= 1) {
-        const uint32_t add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = sums[blockIdx.x] + part[tid] - sum;
-    for (int k = 0; k < SCAN_PER; ++k) {
-        if (lo + k < n) count[lo + k] = run;
-        run += v[k];
-    }
-}
-
 // The row of link id l (1 + flat index of its end), or false: l is 0, points outside the
 // raster or at a cell that is not its own end, or its rank is not below K.
 __device__ __forceinline__ bool row_of(uint32_t l, uint32_t cells, int W, int tiles_x, uint32_t K,
@@ -187,12 +109,7 @@ __device__ __forceinline__ bool row_of(uint32_t l, uint32_t cells, int W, int ti
     if (l == 0u || l - 1u >= cells) return false;
     const uint32_t e = l - 1u;
     const uint32_t ey = e / (uint32_t)W, ex = e - ey * (uint32_t)W;
-    const size_t w = (size_t)ey * tiles_x + ex / TS;
-    const unsigned long long b = bits[w];
-    const int sh = (int)(ex % TS);
-    if (!((b >> sh) & 1ull)) return false;
-    r = before[w] + (uint32_t)__popcll(b & ((1ull << sh) - 1ull));
-    return r < K;
+    return hdem_rank_of(bits, before, (size_t)ey * tiles_x + ex / TS, (int)(ex % TS), K, r);
 }
 
 // 3.  STREAMS as in hdem_streamorder.hip.  first: 1 + the first stream cell of every cell, or
@@ -411,7 +328,7 @@ __global__ __launch_bounds__(NT) void streamnet_end_kernel(int64_t words, stream
     if (w >= words) return;
     const unsigned long long m = a.bits[w];
     if (!((m >> lane) & 1ull)) return;
-    const uint32_t r = a.before[w] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    const uint32_t r = hdem_rank_in(m, lane, a.before[w]);
     if (r >= a.K) return;                        // (more ends than K: counted, refused)
     end_row<STREAMS>(a, r, (int)(w / a.tiles_x), (int)(w % a.tiles_x) * TS + lane);
 }
@@ -475,24 +392,7 @@ int check_args(hdem_ctx *ctx, const streamnet_call &a, d8_grid *g)
     if (int rc = d8_grid_of("the stream network", a.H, a.W, g)) return rc;
     HDEM_REQUIRE(!a.flags, HDEM_ERR_BAD_ARG, "unknown stream network flags 0x%x", a.flags);
     HDEM_REQUIRE(a.link, HDEM_ERR_BAD_ARG, "the link raster is null");
-    switch (a.stream_kind) {
-    case HDEM_FT_STREAMS_NONE:
-        HDEM_REQUIRE(!a.streams && !a.threshold, HDEM_ERR_BAD_ARG,
-                     "streams and threshold must be null and 0 with HDEM_FT_STREAMS_NONE");
-        break;
-    case HDEM_FT_STREAMS_MASK_U8:
-        HDEM_REQUIRE(a.streams, HDEM_ERR_BAD_ARG, "the stream mask is null");
-        HDEM_REQUIRE(!a.threshold, HDEM_ERR_BAD_ARG,
-                     "a uint8 stream mask takes no threshold (got %u)", a.threshold);
-        break;
-    case HDEM_FT_STREAMS_ACC_U32:
-        HDEM_REQUIRE(a.streams, HDEM_ERR_BAD_ARG, "the stream raster is null");
-        HDEM_REQUIRE(a.threshold >= 1, HDEM_ERR_BAD_ARG,
-                     "a uint32 stream raster needs a threshold >= 1");
-        break;
-    default:
-        HDEM_REQUIRE(false, HDEM_ERR_BAD_ARG, "unknown stream kind %d", a.stream_kind);
-    }
+    if (int rc = d8_check_streams(a.streams, a.stream_kind, a.threshold)) return rc;
     HDEM_REQUIRE(std::isfinite(a.cellsize) && a.cellsize > 0.0, HDEM_ERR_BAD_ARG,
                  "cellsize must be finite and positive, got %g", a.cellsize);
     HDEM_REQUIRE(a.K >= 0 && a.K <= (int64_t)a.H * a.W, HDEM_ERR_BAD_ARG,
@@ -509,48 +409,23 @@ int check_args(hdem_ctx *ctx, const streamnet_call &a, d8_grid *g)
     return d8_check_stats(a.stats, "hdem_streamlinks_stats");
 }
 
-// HIP-event times of the four steps, as d8_phase_timer takes its three
-struct step_timer {
-    hipEvent_t ev[6] = {};
-    hipStream_t stream;
-    bool on;
-    step_timer(const hdem_ctx *ctx, bool wanted) : stream(ctx->stream), on(ctx->profiling && wanted) {}
-    step_timer(const step_timer &) = delete;
-    ~step_timer()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    int start()
-    {
-        for (int k = 0; on && k < 6; ++k) HDEM_HIP_CHECK(hipEventCreate(&ev[k]));
-        return HDEM_OK;
-    }
-    void mark(int k) { if (on) (void)hipEventRecord(ev[k], stream); }
-    float ms(int from, int to) const
-    {
-        float t = 0.f;
-        if (on) (void)hipEventElapsedTime(&t, ev[from], ev[to]);
-        return t;
-    }
-};
+typedef hdem_event_timer<6> step_timer;   // marks around the four steps
 
 template <int STREAMS>
 void launch_tile_and_end(hdem_ctx *ctx, const streamnet_call &a, const d8_grid &g, int64_t words,
-                         const uint32_t *first, const unsigned long long *bits,
-                         const uint32_t *before, uint32_t *ncard, uint32_t *ndiag,
-                         streamnet_counters *cnt, step_timer &steps)
+                         const uint32_t *first, const hdem_rank_table &rank, uint32_t *ncard,
+                         uint32_t *ndiag, streamnet_counters *cnt, step_timer &steps)
 {
     const uint32_t K = (uint32_t)a.K;
     hipLaunchKernelGGL(streamnet_tile_kernel<STREAMS>, dim3((unsigned)g.tiles), dim3(NT), 0,
                        ctx->stream, a.d8, a.streams, a.threshold, a.link, first, a.dem, a.H, a.W,
-                       g.tiles_x, K, bits, before, a.top, a.z_top, a.cells, ncard, ndiag,
+                       g.tiles_x, K, rank.bits, rank.count, a.top, a.z_top, a.cells, ncard, ndiag,
                        a.catchment, a.row, cnt);
     steps.mark(4);
     if (!(a.end || a.down || a.order || a.magnitude || a.z_end)) return;
     const streamnet_end_args e = {a.H, a.W, g.tiles_x, K, a.d8, a.streams, a.threshold, a.link,
-                                  a.order_in, a.magnitude_in, a.dem, bits, before, a.end, a.down,
-                                  a.order, a.magnitude, a.z_end, cnt};
+                                  a.order_in, a.magnitude_in, a.dem, rank.bits, rank.count, a.end,
+                                  a.down, a.order, a.magnitude, a.z_end, cnt};
     // measured: at 0.03 and 0.37 ends per word the thread form is 3 to 5 times
     // faster, at 34 the wave form 6 times; the crossover in between was not located
     if (a.K >= 2 * words)
@@ -577,21 +452,17 @@ int streamlinks_dev(hdem_ctx *ctx, const streamnet_call &a, const d8_grid &g)
     }
     const size_t n = (size_t)a.K;
 
-    // arena: the flow trace's bytes and first u32 per cell (when it runs) | counters | end bits
-    // u64 per word | counts u32 per word | chunk sums u32 | ncard, ndiag u32 per link (when
-    // length is wanted and they are not)
+    // arena: the flow trace's bytes and first u32 per cell (when it runs) | counters | the rank
+    // table of the end bits | ncard, ndiag u32 per link (when length is wanted and they are not)
     const bool traced = a.catchment && a.stream_kind != HDEM_FT_STREAMS_NONE;
     const size_t trace = traced ? hdem_round16(hdem_flowtrace_arena_bytes(g.tiles, g.nslots)) : 0;
     const size_t first_bytes = traced ? hdem_round16((size_t)cells * 4) : 0;
     const int64_t words = (int64_t)a.H * g.tiles_x;
-    const int64_t chunks = (words + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    const size_t bits_bytes = hdem_round16((size_t)words * 8);
-    const size_t count_bytes = hdem_round16((size_t)words * 4);
-    const size_t sums_bytes = hdem_round16((size_t)chunks * 4);
+    const size_t table_bytes = hdem_rank_table_bytes(words);
     const size_t col_bytes = hdem_round16(n * 4);
     const bool own_card = a.length && !a.ncard, own_diag = a.length && !a.ndiag;
-    const size_t bytes = trace + first_bytes + HEAD + bits_bytes + count_bytes + sums_bytes +
-                         (own_card ? col_bytes : 0) + (own_diag ? col_bytes : 0);
+    const size_t bytes = trace + first_bytes + HEAD + table_bytes + (own_card ? col_bytes : 0) +
+                         (own_diag ? col_bytes : 0);
     char *ws = static_cast<char *>(hdem_arena(ctx, bytes));
     if (!ws) return HDEM_ERR_OOM;
     char *at = ws + trace;
@@ -599,12 +470,9 @@ int streamlinks_dev(hdem_ctx *ctx, const streamnet_call &a, const d8_grid &g)
     at += first_bytes;
     streamnet_counters *cnt = reinterpret_cast<streamnet_counters *>(at);
     at += HEAD;
-    unsigned long long *bits = reinterpret_cast<unsigned long long *>(at);
-    at += bits_bytes;
-    uint32_t *count = reinterpret_cast<uint32_t *>(at);
-    at += count_bytes;
-    uint32_t *sums = reinterpret_cast<uint32_t *>(at);
-    at += sums_bytes;
+    hdem_rank_table rank;
+    hdem_rank_table_at(at, words, &rank);
+    at += table_bytes;
     uint32_t *ncard = a.ncard, *ndiag = a.ndiag;
     if (own_card) ncard = reinterpret_cast<uint32_t *>(at), at += col_bytes;
     if (own_diag) ndiag = reinterpret_cast<uint32_t *>(at), at += col_bytes;
@@ -615,13 +483,8 @@ int streamlinks_dev(hdem_ctx *ctx, const streamnet_call &a, const d8_grid &g)
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, HEAD, ctx->stream));
     steps.mark(0);
     hipLaunchKernelGGL(streamnet_ends_kernel, dim3((unsigned)g.tiles), dim3(NT), 0, ctx->stream,
-                       a.H, a.W, g.tiles_x, a.link, bits, count, cnt);
-    hipLaunchKernelGGL(streamnet_scan_sums_kernel, dim3((unsigned)chunks), dim3(SCAN_NT), 0,
-                       ctx->stream, count, words, sums);
-    hipLaunchKernelGGL(streamnet_scan_one_kernel, dim3(1), dim3(ONE_NT), 0, ctx->stream, sums,
-                       chunks);
-    hipLaunchKernelGGL(streamnet_scan_apply_kernel, dim3((unsigned)chunks), dim3(SCAN_NT), 0,
-                       ctx->stream, count, words, sums);
+                       a.H, a.W, g.tiles_x, a.link, rank.bits, rank.count, cnt);
+    hdem_scan_exclusive(ctx->stream, rank.count, words, rank.sums);
     steps.mark(1);
     HDEM_HIP_CHECK(hipGetLastError());
     // the first stream cell of every cell; the trace takes the head of the arena, refuses
@@ -637,11 +500,11 @@ int streamlinks_dev(hdem_ctx *ctx, const streamnet_call &a, const d8_grid &g)
         if (column) HDEM_HIP_CHECK(hipMemsetAsync(column, 0, n * 4, ctx->stream));
     steps.mark(3);
     if (a.stream_kind == HDEM_FT_STREAMS_NONE)
-        launch_tile_and_end<0>(ctx, a, g, words, first, bits, count, ncard, ndiag, cnt, steps);
+        launch_tile_and_end<0>(ctx, a, g, words, first, rank, ncard, ndiag, cnt, steps);
     else if (a.stream_kind == HDEM_FT_STREAMS_MASK_U8)
-        launch_tile_and_end<1>(ctx, a, g, words, first, bits, count, ncard, ndiag, cnt, steps);
+        launch_tile_and_end<1>(ctx, a, g, words, first, rank, ncard, ndiag, cnt, steps);
     else
-        launch_tile_and_end<2>(ctx, a, g, words, first, bits, count, ncard, ndiag, cnt, steps);
+        launch_tile_and_end<2>(ctx, a, g, words, first, rank, ncard, ndiag, cnt, steps);
     if (a.length)
         hipLaunchKernelGGL(streamnet_length_kernel, dim3((unsigned)((a.K + NT - 1) / NT)),
                            dim3(NT), 0, ctx->stream, (uint32_t)a.K, ncard, ndiag, a.cellsize,

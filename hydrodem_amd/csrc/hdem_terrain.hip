@@ -187,27 +187,6 @@ __global__ __launch_bounds__(NT) void terrain_kernel(const terrain_args p)
         atomicAdd(&p.cnt[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
 
-// HIP-event time of the launch, taken when the context profiles and the caller wants stats.
-struct launch_timer {
-    hipEvent_t ev[2] = {};
-    hipStream_t stream;
-    bool on;
-    launch_timer(const hdem_ctx *ctx, bool wanted) : stream(ctx->stream), on(ctx->profiling && wanted) {}
-    launch_timer(const launch_timer &) = delete;
-    ~launch_timer()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    int start()
-    {
-        for (int k = 0; on && k < 2; ++k) HDEM_HIP_CHECK(hipEventCreate(&ev[k]));
-        return HDEM_OK;
-    }
-    void mark(int k) { if (on) (void)hipEventRecord(ev[k], stream); }
-    void read(float *ms) const { if (on) (void)hipEventElapsedTime(ms, ev[0], ev[1]); }   // after a synchronise
-};
-
 inline bool positive(double v) { return std::isfinite(v) && v > 0.0; }
 
 struct span {
@@ -312,7 +291,7 @@ extern "C" int hdem_terrain_f32_dev(hdem_ctx *ctx, const float *dem, int H, int 
     p.vec_codes = use_d8 && W % 4 == 0 && (uintptr_t)d8 % 4 == 0;
     p.cnt = cnt;
 
-    launch_timer timer(ctx, stats != nullptr);
+    hdem_event_timer<2> timer(ctx, stats != nullptr);   // around the launch
     if (int rc = timer.start()) return rc;
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, C_COUNT * sizeof(unsigned long long), ctx->stream));
     timer.mark(0);
@@ -335,7 +314,7 @@ extern "C" int hdem_terrain_f32_dev(hdem_ctx *ctx, const float *dem, int H, int 
     st.flat_cells = (int64_t)host[C_FLAT];
     st.floored_cells = (int64_t)host[C_FLOORED];
     st.invalid_codes = (int64_t)host[C_INVALID];
-    timer.read(&st.ms_total);
+    st.ms_total = timer.ms(0, 1);
     d8_publish(stats, st);
     return d8_report_invalid(host[C_INVALID]);
 }

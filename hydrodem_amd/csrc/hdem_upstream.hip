@@ -454,7 +454,7 @@ extern "C" int hdem_upstream_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int
     uint32_t *pathw = reinterpret_cast<uint32_t *>(next + nslots);
     uint32_t *off = pathw + nslots;
 
-    d8_phase_timer phases(ctx, stats != nullptr);
+    hdem_event_timer<4> phases(ctx, stats != nullptr);
     if (int rc = phases.start()) return rc;
 
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(upstream_counters), ctx->stream));

@@ -17,8 +17,8 @@
 //      frame cell is a stop like any other, so the word of a seeded cell that an exit of the
 //      neighbouring tile drains into is resolved by the tile that owns it: no tile looks at
 //      the seeds of its halo.
-//   S  (watershed_scan_kernel)   compact mode only: exclusive scan of the tiles' terminal
-//      counts; a terminal's label is 1 + offset of its tile + its rank inside the tile.
+//   S  (hdem_scan.h, its one workgroup)  compact mode only: exclusive scan of the tiles'
+//      terminal counts; a terminal's label is 1 + offset of its tile + its rank inside the tile.
 //   B  (watershed_forest_kernel) in-place pointer jumping over the slot words, up to 4 jumps
 //      per node and launch.  A word is (resolved << 32 | label or next slot), read and written
 //      whole, and a node only ever replaces its pointer by its pointer's pointer, so whatever
@@ -29,6 +29,7 @@
 //   C  (watershed_final_kernel)  per tile, streaming: the tile's 252 resolved words in LDS,
 //      2 B per cell in, 4 B per cell out.  Counts what never resolved (a cycle).
 #include "hdem_d8tile.h"
+#include "hdem_scan.h"
 
 namespace {
 
@@ -37,7 +38,6 @@ constexpr int TNT = 512;              // threads per tile workgroup (8 cells eac
                                       // 1.35x as long with 256 and 1.43x with 1024)
 constexpr int JUMPS = 4;              // forest jumps per node and launch (B at 16384^2:
                                       // 0.47 ms with 1, 0.39 with 4, 0.49 with 16)
-constexpr int SCAN_NT = 1024;
 constexpr uint16_t EXIT = 0xFFFE;     // rl[]: receiver in a neighbouring tile, cell not seeded
 constexpr uint16_t STOP = 0xFFFF;     // rl[]: terminal, seeded, or outside the raster
 constexpr uint16_t T_RANK = 0x4000;   // per-cell target, compact mode: a terminal's own rank
@@ -182,33 +182,6 @@ __global__ __launch_bounds__(TNT) void watershed_tile_kernel(
     }
 }
 
-// S: exclusive scan of the tiles' terminal counts, in place; one workgroup.
-__global__ __launch_bounds__(SCAN_NT) void watershed_scan_kernel(uint32_t *__restrict__ count,
-                                                                 int64_t tiles)
-{
-    __shared__ uint32_t part[SCAN_NT];
-    const int tid = threadIdx.x;
-    const int64_t chunk = (tiles + SCAN_NT - 1) / SCAN_NT;
-    const int64_t lo = tid * chunk < tiles ? tid * chunk : tiles;
-    const int64_t hi = lo + chunk < tiles ? lo + chunk : tiles;
-    uint32_t sum = 0;
-    for (int64_t t = lo; t < hi; ++t) sum += count[t];
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < SCAN_NT; d <<= 1) {
-        const uint32_t add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[tid] - sum;
-    for (int64_t t = lo; t < hi; ++t) {
-        const uint32_t n = count[t];
-        count[t] = run;
-        run += n;
-    }
-}
-
 // B: one round of pointer jumping over the slot words.  Grid-stride.
 __global__ __launch_bounds__(NT) void watershed_forest_kernel(int64_t nslots, int round,
                                                               uint64_t *__restrict__ word,
@@ -343,7 +316,7 @@ extern "C" int hdem_watershed_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
     uint32_t *tile_offset = reinterpret_cast<uint32_t *>(word + nslots);
     uint16_t *target = reinterpret_cast<uint16_t *>(tile_offset + tiles);
 
-    d8_phase_timer phases(ctx, stats != nullptr);
+    hdem_event_timer<4> phases(ctx, stats != nullptr);
     if (int rc = phases.start()) return rc;
 
     HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(watershed_counters), ctx->stream));
@@ -354,8 +327,7 @@ extern "C" int hdem_watershed_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, in
     if (compact) {
         hipLaunchKernelGGL(watershed_tile_kernel<true>, grid, dim3(TNT), 0, ctx->stream, d8, seeds,
                            H, W, tiles_x, target, word, tile_offset, cnt);
-        hipLaunchKernelGGL(watershed_scan_kernel, dim3(1), dim3(SCAN_NT), 0, ctx->stream,
-                           tile_offset, tiles);
+        hdem_scan_exclusive_small(ctx->stream, tile_offset, tiles);
     } else {
         hipLaunchKernelGGL(watershed_tile_kernel<false>, grid, dim3(TNT), 0, ctx->stream, d8,
                            seeds, H, W, tiles_x, target, word, tile_offset, cnt);

@@ -59,17 +59,6 @@ struct zonal_counters {
 };
 static_assert(sizeof(zonal_counters) <= HEAD, "counters outgrew their block");
 
-// float -> uint32 whose unsigned order is the floats' order: -0.0 below +0.0
-__device__ __forceinline__ uint32_t key_of(float f)
-{
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : b | 0x80000000u;
-}
-__device__ __forceinline__ float float_of(uint32_t k)
-{
-    return __uint_as_float((k & 0x80000000u) ? k & 0x7FFFFFFFu : ~k);
-}
-
 __device__ __forceinline__ unsigned int wave_sum(unsigned int v)
 {
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
@@ -151,12 +140,8 @@ __global__ __launch_bounds__(NT) void zonal_popc_kernel(int64_t words, const u64
 __device__ __forceinline__ bool row_of(uint32_t z, uint32_t K, const u64 *__restrict__ bits,
                                        const uint32_t *__restrict__ before, uint32_t &r)
 {
-    const uint32_t at = z - 1u, w = at >> 6;
-    const int sh = (int)(at & 63u);
-    const u64 b = bits[w];
-    if (!((b >> sh) & 1ull)) return false;
-    r = before[w] + (uint32_t)__popcll(b & ((1ull << sh) - 1ull));
-    return r < K;
+    const uint32_t at = z - 1u;
+    return hdem_rank_of(bits, before, at >> 6, (int)(at & 63u), K, r);
 }
 
 // 2.  The columns the tile pass adds to (null: not wanted) and what a run, a cell or a slot adds.
@@ -416,28 +401,21 @@ struct zonal_call {
 
 // the arena of a call: counters | bits u64 per word | counts u32 per word | chunk sums u32 |
 // packed min, packed max u64 per row (when wanted)
-struct zonal_ws {
+struct zonal_ws : hdem_rank_table {
     int64_t words;
     zonal_counters *cnt;
-    u64 *bits;
-    uint32_t *count, *sums;
     u64 *pmin, *pmax;
 };
 
 int zonal_carve(hdem_ctx *ctx, int64_t cells, size_t packed_rows, zonal_ws *ws)
 {
     ws->words = (cells + 63) / 64;
-    const size_t bits_bytes = hdem_round16((size_t)ws->words * 8);
-    const size_t count_bytes = hdem_round16((size_t)ws->words * 4);
-    const size_t sums_bytes = hdem_round16((size_t)hdem_scan_chunks(ws->words) * 4);
+    const size_t table_bytes = hdem_rank_table_bytes(ws->words);
     const size_t packed_bytes = hdem_round16(packed_rows * 8);
-    char *at = static_cast<char *>(
-        hdem_arena(ctx, HEAD + bits_bytes + count_bytes + sums_bytes + 2 * packed_bytes));
+    char *at = static_cast<char *>(hdem_arena(ctx, HEAD + table_bytes + 2 * packed_bytes));
     if (!at) return HDEM_ERR_OOM;
     ws->cnt = reinterpret_cast<zonal_counters *>(at), at += HEAD;
-    ws->bits = reinterpret_cast<u64 *>(at), at += bits_bytes;
-    ws->count = reinterpret_cast<uint32_t *>(at), at += count_bytes;
-    ws->sums = reinterpret_cast<uint32_t *>(at), at += sums_bytes;
+    hdem_rank_table_at(at, ws->words, ws), at += table_bytes;
     ws->pmin = packed_rows ? reinterpret_cast<u64 *>(at) : nullptr, at += packed_bytes;
     ws->pmax = packed_rows ? reinterpret_cast<u64 *>(at) : nullptr;
     return HDEM_OK;
@@ -523,31 +501,7 @@ int check_args(hdem_ctx *ctx, const zonal_call &a, d8_grid *g)
     return d8_check_stats(a.stats, "hdem_zonal_stats");
 }
 
-// HIP-event times of the three steps, as d8_phase_timer takes its three
-struct step_timer {
-    hipEvent_t ev[4] = {};
-    hipStream_t stream;
-    bool on;
-    step_timer(const hdem_ctx *ctx, bool wanted) : stream(ctx->stream), on(ctx->profiling && wanted) {}
-    step_timer(const step_timer &) = delete;
-    ~step_timer()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    int start()
-    {
-        for (int k = 0; on && k < 4; ++k) HDEM_HIP_CHECK(hipEventCreate(&ev[k]));
-        return HDEM_OK;
-    }
-    void mark(int k) { if (on) (void)hipEventRecord(ev[k], stream); }
-    float ms(int from, int to) const
-    {
-        float t = 0.f;
-        if (on) (void)hipEventElapsedTime(&t, ev[from], ev[to]);
-        return t;
-    }
-};
+typedef hdem_event_timer<4> step_timer;   // marks around the three steps
 
 template <int VT>
 void launch_tile_and_final(hdem_ctx *ctx, const zonal_call &a, const d8_grid &g, const zonal_ws &ws,

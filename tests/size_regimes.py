@@ -9,11 +9,12 @@ Every other raster that the suite checks bit for bit has 130 x 257 or 200 x 333 
 every decision below takes its trivial value:
 
   decision                                             trivial until        predicate
-  chunks of a rank scan (hdem_scan.h and the private   4 096 words          scan_chunks
-    copies in hdem_streamnet.hip, hdem_depressions.hip)
+  chunks of a rank scan (hdem_scan.h, under the zonal   4 096 words          scan_chunks
+    statistics, the stream network, the depressions)
   per-thread loop of the one workgroup over the        1 024 chunks         one_kernel_loops
-    chunk sums (*_scan_one_kernel, ``chunk >= 2``)
-  per-thread loop of watershed_scan_kernel             1 024 tiles          watershed_scan_loops
+    chunk sums (hdem_scan_one_kernel, ``chunk >= 2``)
+  the same loop over the tile counts of Watersheds     1 024 tiles          watershed_scan_loops
+    (hdem_scan_exclusive_small)
   second stride of the grid-stride forest kernels      8 * CUs workgroups   past_the_cap,
     (flowacc / upstream degree kernels, the forests                           second_stride_tiles
     of Watersheds and the flow trace)
@@ -42,10 +43,9 @@ NONE = 0xFFFFFFFF
 # ---------------------------------------------------------------------------
 TS = 64                     # hdem_d8tile.h `constexpr int TS = 64` (tile edge, bits of a word)
 PER = 252                   # hdem_d8tile.h `constexpr int PER = 4 * TS - 4`
-SCAN_CHUNK = 4096           # hdem_scan.h `HDEM_SCAN_CHUNK = HDEM_SCAN_NT * HDEM_SCAN_PER` (256 * 16);
-                            # hdem_streamnet.hip, hdem_depressions.hip `SCAN_CHUNK = SCAN_NT * SCAN_PER`
-ONE_NT = 1024               # hdem_scan.h `HDEM_SCAN_ONE_NT = 1024`; `ONE_NT = 1024` in the two copies
-WATERSHED_SCAN_NT = 1024    # hdem_watershed.hip `constexpr int SCAN_NT = 1024`
+SCAN_CHUNK = 4096           # hdem_scan.h `HDEM_SCAN_CHUNK = HDEM_SCAN_NT * HDEM_SCAN_PER` (256 * 16)
+ONE_NT = 1024               # hdem_scan.h `HDEM_SCAN_ONE_NT = 1024`
+WATERSHED_SCAN_NT = 1024    # the same workgroup: hdem_watershed.hip calls hdem_scan_exclusive_small
 FOREST_NT = 256             # `constexpr int NT = 256` of hdem_flowacc.hip, hdem_upstream.hip,
                             # hdem_watershed.hip and hdem_flowtrace.hip (the forest workgroups)
 CAP_PER_CU = 8              # hdem_d8tile.h d8_forest_plan_of `(int64_t)ctx->num_cus * 8`; the same
@@ -88,7 +88,8 @@ def one_kernel_loops(words):
 
 
 def watershed_scan_loops(shape):
-    """``chunk = (tiles + SCAN_NT - 1) / SCAN_NT`` of watershed_scan_kernel."""
+    """``chunk = (n + HDEM_SCAN_ONE_NT - 1) / HDEM_SCAN_ONE_NT`` of hdem_scan_one_kernel, n the
+    tiles: what a thread of the scan over the watersheds' tile counts adds up."""
     return _ceil(tiles_of(shape), WATERSHED_SCAN_NT)
 
 

@@ -7,31 +7,43 @@ closed forms that tests/test_size_regimes.py holds to those references.  Every c
 that branch's predicate on its own input first.
 
   ZonalStatistics, zonal_count, broadcast     ids in two and three chunks of hdem_scan.h
-  StreamOrder, StreamNetwork                  tile words in two and three chunks of the private
+  StreamOrder, StreamNetwork                  tile words in two and three chunks of the same
                                               scan, both forms of the end kernel above one chunk
-  the column of 4 194 404 rows                the per-thread loop of streamnet_scan_one_kernel
-                                              and depr_scan_one_kernel (1 025 chunks)
+  the column of 4 194 404 rows                the per-thread loop of hdem_scan_one_kernel, through
+                                              the stream network and the depressions (1 025 chunks)
   strips and 65 x 67 200 (at 256 CUs)         the second stride of the grid-stride forest
-                                              kernels, the loop of watershed_scan_kernel
+                                              kernels; the same loop of hdem_scan_one_kernel
+                                              through Watersheds (hdem_scan_exclusive_small over
+                                              more than 1 024 tile counts)
 
-Not reached: the per-thread loop of hdem_scan_one_kernel on the zonal path needs more than
-1 024 chunks of 262 144 ids, a raster of more than 268 435 456 cells.
+The per-thread loop of hdem_scan_one_kernel (``chunk >= 2``) is reached three ways: by the two
+tall-column tests (4 194 404 rows, 1 025 chunk sums) through the stream network and through
+the depressions, and by the ``wide`` and strip cases through Watersheds (more than 1 024 tile
+counts).  Only the zonal path does not get there: it needs more than 1 024 chunks of 262 144
+ids, a raster of more than 268 435 456 cells.
 
-Value-only mutants of the kernels that were run against this file, once each, with the tests
-each fails (both keep every store in bounds: a rank is compared with K before it indexes a
-column, so ranks collide and rows are wrong, nothing is written elsewhere).  The files that
-used these kernels before this one -- tests/test_gpu_zonal.py, tests/test_gpu_streamnet.py,
-tests/test_gpu_streamorder.py, tests/test_gpu_terrain_attributes.py -- pass under both.
-  hdem_scan_one_kernel writing ``sums[t] = 0`` -> 13 tests:
+The value-only mutant of that kernel that was run against this file, once, with the tests it
+fails (it keeps every store in bounds: the ranks it gives stay below the true ones and a rank
+is compared with K before it indexes a column, so ranks collide and rows are wrong, nothing is
+written elsewhere).  While the scan had a copy per operator the same mutation failed 13 tests
+in the header (the zonal ones below) and 19 in the stream network's copy; the files that used
+these kernels before this one -- tests/test_gpu_zonal.py, tests/test_gpu_streamnet.py,
+tests/test_gpu_streamorder.py, tests/test_gpu_terrain_attributes.py -- passed under both.
+  hdem_scan_one_kernel writing ``sums[t] = 0`` -> 36 of the 55 tests:
       test_zonal_tables_with_ids_past_one_scan_chunk at 5 x 52 429, 1024 x 512 and 771 x 700
       with all four zone kinds (512 x 512, one chunk, passes), and
-      test_zonal_uint32_values_in_three_chunks; nothing else
-  streamnet_scan_one_kernel writing ``sums[t] = 0`` -> 19 tests:
+      test_zonal_uint32_values_in_three_chunks (13);
       test_stream_networks_past_one_scan_chunk at 1400 x 130 and 2800 x 130 with all four
       stream sets, flat and ramp (both end kernels), and at 4097 x 1 with every cell a stream
       cell (its second chunk is one word: the other stream sets leave no end there; 4096 x 1,
       one chunk, passes), and
-      test_the_tall_column_takes_the_per_thread_loop_of_the_streamnet_scan; nothing else
+      test_the_tall_column_takes_the_per_thread_loop_of_the_streamnet_scan (19);
+      test_the_tall_column_takes_the_per_thread_loop_of_the_depression_scan (1);
+      test_strips_take_the_second_stride_of_the_forest_kernels with ``segments``, row and
+      column (the compact labels of 2 792 basins in 2 181 tiles; ``one_path`` has one basin
+      and passes), and
+      test_wide_raster_watersheds_match_the_doubling_reference_and_the_numbering_rule (3);
+      nothing else
 """
 import numpy as np
 import pytest
@@ -129,7 +141,7 @@ def test_zonal_uint32_values_in_three_chunks():
 
 
 # ---------------------------------------------------------------------------
-# 2. StreamOrder and StreamNetwork: the private scan of hdem_streamnet.hip
+# 2. StreamOrder and StreamNetwork: the scan of hdem_scan.h under hdem_streamnet.hip
 # ---------------------------------------------------------------------------
 def stream_kinds(shape):
     return sr.STREAM_KINDS + (("sparse",) if shape[1] > 1 else ())
@@ -189,7 +201,7 @@ def test_the_tall_column_takes_the_per_thread_loop_of_the_streamnet_scan(tall):
 
 
 # ---------------------------------------------------------------------------
-# 3. Depressions, compact labels: the private scan of hdem_depressions.hip
+# 3. Depressions, compact labels: the scan of hdem_scan.h under hdem_depressions.hip
 # ---------------------------------------------------------------------------
 def test_the_tall_column_takes_the_per_thread_loop_of_the_depression_scan():
     words = sr.tile_words(sr.TALL)
@@ -229,7 +241,7 @@ def test_strips_take_the_second_stride_of_the_forest_kernels(cus, strip, segment
     assert compact.dtype == U32 and np.array_equal(compact, want["compact"])
     assert basins.outlets.dtype == U32 and np.array_equal(basins.outlets, want["outlets"])
     assert basins.stats["basins"] == want["outlets"].size
-    if segment:         # basins in more tiles than watershed_scan_kernel has threads
+    if segment:         # basins in more tiles than hdem_scan_one_kernel has threads
         tiles_with_outlets = np.unique(want["outlets"] // sr.TS).size
         assert tiles_with_outlets > sr.WATERSHED_SCAN_NT and want["outlets"].size > 2048
 
