@@ -27,6 +27,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      DemToStreamNetwork, ZonalStatistics, DemToBasins,
                                      TerrainAttributes, Slope, Aspect, WetnessIndex,
                                      DemToWetness,
+                                     EuclideanDistance, EuclideanAllocation, BurnStreams,
                                      ResolveFlats,
                                      Depressions, DepressionInventory,
                                      HydroConditioning, DemToHAND,

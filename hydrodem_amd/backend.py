@@ -181,6 +181,13 @@ class _TerrainStats(_SizedStats):
                 ("floored_cells", ctypes.c_int64), ("invalid_codes", ctypes.c_int64)]
 
 
+class _ProximityStats(_SizedStats):
+    """``hdem_proximity_stats`` (the binding is hydrodem_amd/proximity.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("ms_row", ctypes.c_float),
+                ("ms_column", ctypes.c_float), ("ms_final", ctypes.c_float),
+                ("sources", ctypes.c_int64), ("unreached", ctypes.c_int64)]
+
+
 DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
 # columns of the depression table, in the order of the C ABI's pointers
 DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
@@ -307,6 +314,10 @@ SIGNATURES = {
                         [_i, _c.POINTER(_TerrainStats)],
     "hdem_terrain_f32_dev": [_vp, _vp, _i, _i, _vp, _vp] + [_c.c_double] * 4 + [_vp] * 8 +
                             [_i, _c.POINTER(_TerrainStats)],
+    "hdem_proximity": [_vp, _vp, _i, _c.c_uint32, _i, _i, _vp, _c.c_double, _c.c_uint32] +
+                      [_c.c_double] * 3 + [_vp] * 6 + [_c.POINTER(_ProximityStats)],
+    "hdem_proximity_dev": [_vp, _vp, _i, _c.c_uint32, _i, _i, _vp, _c.c_double, _c.c_uint32] +
+                          [_c.c_double] * 3 + [_vp] * 6 + [_c.POINTER(_ProximityStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

@@ -63,6 +63,7 @@ from .. import streamorder as _streamorder
 from .. import streamnet as _streamnet
 from .. import zonal as _zonal
 from .. import terrain as _terrain
+from .. import proximity as _proximity
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -1079,6 +1080,142 @@ class WetnessIndex(TerrainAttributes):  # pylint: disable=too-few-public-methods
                  min_slope=1e-3, slope="horn"):
         super().__init__(want=("twi",), cellsize=cellsize, z_factor=z_factor, codes=codes,
                          accumulation=accumulation, min_slope=min_slope, slope=slope)
+
+
+class _Proximity(Filter):  # pylint: disable=too-few-public-methods
+    """What ``EuclideanDistance``, ``EuclideanAllocation`` and ``BurnStreams`` share: the
+    operands of one ``hdem_proximity`` call, checked as far as they can be before the shapes
+    are known, and the call on host arrays or device rasters.
+
+    The nearest source of a cell minimises ``(r - r')^2 + (x - x')^2``, in integers; among
+    sources at equal distance it is the one with the smallest flat index ``r' * W + x'``.
+    Exact, identical from run to run.  ``ValueError`` (before the device is touched) for
+    operands of another type, dtype or shape, a ``threshold`` that does not go with the
+    sources, more than 2^32 - 1 cells, a squared diagonal of more than 2^32 - 2 and a side of
+    more than 65535 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        sources (cells of the source set), unreached (cells out of reach) of the last call;
+        ms_row, ms_column and ms_final when profiling is on.
+    """
+
+    SOURCE_TYPES = (np.bool_, np.uint8, np.uint32)
+
+    def _set_operands(self, sources, threshold, cellsize=1.0, max_distance=None, buffer=None,
+                      smooth=0.0, sharp=0.0):
+        self.sources = _Given(sources, "sources", self.SOURCE_TYPES).value
+        self.threshold, self.cellsize, self.max_distance = threshold, cellsize, max_distance
+        self.buffer, self.smooth, self.sharp = buffer, smooth, sharp
+        self.stats = {}
+
+    def _args(self, sources, want, dem=None):
+        return _proximity.proximity_args(sources, self.threshold, want, dem, self.cellsize,
+                                         self.max_distance, self.buffer, self.smooth, self.sharp)
+
+    def _call(self, run, sources, want, dem=None):
+        outs, self.stats = run(sources, self.threshold, want, dem, self.cellsize,
+                               self.max_distance, self.buffer, self.smooth, self.sharp)
+        return outs
+
+
+class _FromSources(_Proximity):  # pylint: disable=too-few-public-methods
+    """The proximity filters whose input is the source raster itself, unless ``sources`` were
+    given at construction: then the raster they are applied to only has to have their shape."""
+
+    auto_device = False     # the input is a mask, an accumulation or labels, not a float32 DEM
+
+    def __init__(self, sources=None, *, threshold=None, cellsize=1.0, max_distance=None):
+        self._set_operands(sources, threshold, cellsize, max_distance)
+        # everything but the shapes, on a 1 x 1 stand-in
+        if self.sources is not None:
+            self._args(_Given(self.sources).stand_in(), self._first(self.sources))
+
+    def _first(self, sources):
+        raise NotImplementedError
+
+    def _given(self, raster):
+        if self.sources is None:
+            return raster
+        backend._check(raster, None, "the raster is",  # pylint: disable=protected-access
+                       like=("the sources", tuple(self.sources.shape)))
+        return self.sources
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        sources = _Given(self._given(image_to_filter)).host()     # (a bool mask as bytes)
+        want = self._first(sources)
+        self._args(sources, want)
+        return self._call(_proximity.proximity, sources, want)[want]
+
+    def apply_device(self, raster):
+        sources = self._given(raster)
+        want = self._first(sources)
+        self._args(sources, want)
+        with _Given(sources).device(raster.ctx) as on_device:
+            return self._call(_proximity.proximity_dev, on_device, want)[want]
+
+
+class EuclideanDistance(_FromSources):  # pylint: disable=too-few-public-methods
+    """Euclidean distance to the nearest source (new operator; ArcGIS *Euclidean Distance*).
+    Input: the source raster -- a bool / uint8 mask (non-zero = source), a uint32 raster with
+    ``threshold`` (source where ``>= threshold``: a ``FlowAccumulation`` result goes in as it
+    is) or a uint32 label raster without one (non-zero = source) -- or, with ``sources`` given
+    at construction, any raster of their shape.  Returns float32
+    ``sqrt(d2) * cellsize``, evaluated in float64 and rounded once, ``d2`` the exact squared
+    distance in cells; NaN beyond ``max_distance`` cells and where there is no source at all.
+    Tie rule, errors and ``stats``: ``_Proximity``."""
+
+    def _first(self, sources):
+        return "distance"
+
+
+class EuclideanAllocation(_FromSources):  # pylint: disable=too-few-public-methods
+    """The nearest source of every cell (new operator; ArcGIS *Euclidean Allocation*).  Input
+    as ``EuclideanDistance`` takes it.  Returns uint32: for a uint32 label raster (no
+    ``threshold``) the label of the nearest source, 0 out of reach; for a mask or an
+    accumulation with ``threshold`` the flat index of the nearest source, 0xFFFFFFFF out of
+    reach.  Among sources at equal distance the one with the smallest flat index wins."""
+
+    def _first(self, sources):
+        labels = np.dtype(sources.dtype) == np.uint32 and self.threshold is None
+        return "label" if labels else "nearest"
+
+
+class BurnStreams(_Proximity):  # pylint: disable=too-few-public-methods
+    """Stream burning of the AGREE kind (new operator): a float32 DEM in, the DEM lowered
+    towards a known stream raster out, to be filled afterwards.  ``streams`` (a mask, a uint32
+    raster with ``threshold``, or uint32 labels; array or ``DeviceRaster`` of the DEM's shape)
+    is given at construction.  With ``d`` the float32 Euclidean distance in cells to the
+    nearest stream cell, in float32, one rounding per operation:
+    ``burned = dem - smooth * (1 - d / buffer) - (sharp on a stream cell)`` where
+    ``d < buffer``, the DEM elsewhere (``1 / buffer`` is rounded to float32 once and
+    multiplied); NaN stays NaN.  ``buffer > 0`` in cells, ``smooth >= 0`` and ``sharp >= 0`` in
+    the DEM's units.  ``ComposedFilter`` chains ``BurnStreams``, ``SinkFill`` and
+    ``D8FlowDirection`` on the device.  Tie rule, errors and ``stats``: ``_Proximity``."""
+
+    auto_device = True      # device form == host form for a float32 raster
+
+    def __init__(self, streams, *, threshold=None, buffer, smooth=0.0, sharp=0.0):
+        if streams is None:
+            raise ValueError("BurnStreams needs the streams it burns in (a mask, a uint32 raster "
+                             "with a threshold, or labels)")
+        self._set_operands(streams, threshold, buffer=buffer, smooth=smooth, sharp=sharp)
+        self._args(_Given(self.sources).stand_in(), "burned", np.zeros((1, 1), np.float32))
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("BurnStreams", image_to_filter, np.float32, "a float32 DEM")
+        self._args(self.sources, "burned", image_to_filter)
+        return self._call(_proximity.proximity, _Given(self.sources).host(), "burned",
+                          image_to_filter)["burned"]
+
+    def apply_device(self, raster):
+        _check_raster("BurnStreams", raster, np.float32, "a float32 DEM")
+        self._args(self.sources, "burned", raster)
+        with _Given(self.sources).device(raster.ctx) as streams:
+            return self._call(_proximity.proximity_dev, streams, "burned", raster)["burned"]
 
 
 class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods

@@ -1019,6 +1019,74 @@ int hdem_terrain_f32_dev(hdem_ctx *ctx, const float *dem, int H, int W, const ui
                          float *degrees, float *aspect, float *d8_slope, float *twi, float *spi,
                          int flags, hdem_terrain_stats *stats);    /* device pointers */
 
+/* ---- A15  Proximity.apply  (new operator: Euclidean distance, allocation, stream burning) ----
+ * The exact Euclidean distance transform of a source set S in the plane of the raster, and what
+ * is built on the nearest source: where the D8 operators answer "where does the water of this
+ * cell go", this one answers "which source is this cell next to, and how far away is it".
+ * sources, source_kind, threshold: the set S, given as A7 gives its stream set, plus one kind:
+ *   HDEM_FT_STREAMS_MASK_U8      sources is uint8 H x W, non-zero = in S; threshold 0
+ *   HDEM_FT_STREAMS_ACC_U32      sources is uint32 H x W, in S where >= threshold; threshold >= 1
+ *   HDEM_PX_SOURCES_LABELS_U32   sources is uint32 H x W, non-zero = in S (and the cell's label);
+ *                                threshold 0
+ * "Every cell" (HDEM_FT_STREAMS_NONE) is not a kind here.
+ * For a cell c = (r, x), n(c) is the source (r', x') that minimises
+ *   d2 = (r - r')^2 + (x - x')^2,
+ * and AMONG SOURCES AT EQUAL d2 THE ONE WITH THE SMALLEST FLAT INDEX r' * W + x': the tie rule
+ * is part of the contract.  Integers decide n(c); no float comparison does.
+ * max_distance (cells; 0: none): a cell with d2 > max_distance^2 is out of reach, and so is
+ * every cell when S is empty.  The search is not bounded by it.
+ * Outputs, all H x W, each may be NULL, at least one must not be:
+ *   d2       uint32  the squared distance in cells, exact               0xFFFFFFFF out of reach
+ *   nearest  uint32  the flat index of n(c)                             0xFFFFFFFF
+ *   label    uint32  sources[n(c)]; HDEM_PX_SOURCES_LABELS_U32 only     0
+ *   distance float32 (float)(sqrt((double)d2) * cellsize); square cells NaN
+ *   rise     float32 dem[c] - dem[n(c)], one float32 subtraction: the   NaN
+ *                    Euclidean counterpart of HAND; needs dem
+ *   burned   float32 the dem lowered towards S inside a buffer (AGREE); dem[c]
+ *                    needs dem
+ * burned, with bf = (float)buffer, sm = (float)smooth, sh = (float)sharp and
+ * inv = (float)(1.0 / buffer), in float32, one rounding per operation, no fused multiply-add:
+ *   d = (float)sqrt((double)d2)        t = 1 - d * inv
+ *   burned = (dem - sm * t) - (d2 == 0 ? sh : 0)   where d < bf,   burned = dem elsewhere.
+ * NaN in dem passes through rise and burned by arithmetic.
+ * HDEM_ERR_BAD_ARG before any allocation or launch: H * W > 2^32 - 1; (H-1)^2 + (W-1)^2 >
+ * 2^32 - 2 (d2 would not fit beside its sentinel); H or W > 65535 (the row pass keeps a column
+ * index in 16 bits beside its sentinel, so (1, 65536), which the second bound alone would admit,
+ * is refused like (1, 65537); 32768 x 32768 passes); an unknown kind, a threshold that does not
+ * go with the kind; no output; label without label sources; rise or burned without dem;
+ * cellsize not finite and > 0 when distance is wanted; buffer not finite and > 0 or smooth or
+ * sharp not finite and >= 0 when burned is wanted; an output that overlaps an input or another
+ * output.
+ * Every output is the same bytes from run to run, whatever the schedule; a subset of the outputs
+ * holds the bytes the call for all of them writes.
+ * Workspace from the context's arena: 4 bytes per cell (the nearest source column of every
+ * cell in its row and the nearest row of every cell in its column, both uint16 and both kept
+ * column-major) plus 12 bytes per 64 cells (source bits and row carries) and 16 bytes of
+ * counters.  The _dev form synchronises the context's stream once, to read the counters.
+ * stats may be NULL; otherwise the caller sets stats->struct_size =
+ * sizeof(hdem_proximity_stats) first (32 bytes in this version; a shorter struct is filled as
+ * far as it goes).  The ms_* fields are filled only while profiling is on
+ * (hdem_profile_enable); the call has no kernel id. */
+#define HDEM_PX_SOURCES_LABELS_U32 3    /* beside HDEM_FT_STREAMS_MASK_U8 and _ACC_U32 */
+typedef struct hdem_proximity_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_proximity_stats), set by the caller         */
+    float ms_row;            /* source bits, row carries, row pass (HIP events; profiling)  */
+    float ms_column;         /* the column pass                                             */
+    float ms_final;          /* the launch that writes the outputs                          */
+    int64_t sources;         /* cells of S                                                  */
+    int64_t unreached;       /* cells out of reach                                          */
+} hdem_proximity_stats;      /* sizeof == 32 */
+int hdem_proximity(hdem_ctx *ctx, const void *sources, int source_kind, uint32_t threshold,
+                   int H, int W, const float *dem, double cellsize, uint32_t max_distance,
+                   double buffer, double smooth, double sharp, uint32_t *d2, uint32_t *nearest,
+                   uint32_t *label, float *distance, float *rise, float *burned,
+                   hdem_proximity_stats *stats);        /* host pointers, synchronous */
+int hdem_proximity_dev(hdem_ctx *ctx, const void *sources, int source_kind, uint32_t threshold,
+                       int H, int W, const float *dem, double cellsize, uint32_t max_distance,
+                       double buffer, double smooth, double sharp, uint32_t *d2,
+                       uint32_t *nearest, uint32_t *label, float *distance, float *rise,
+                       float *burned, hdem_proximity_stats *stats);    /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
