@@ -22,6 +22,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      GrovesCorrection, GrovesCorrectionsIter,
                                      PostProcessingFinal, SinkFill,
                                      D8FlowDirection, FlowAccumulation, Watersheds,
+                                     WeightedFlowAccumulation,
                                      FlowDistance, HeightAboveDrainage, UpstreamFlowLength,
                                      StreamOrder, DemToStreamOrder, StreamNetwork,
                                      DemToStreamNetwork, ZonalStatistics, DemToBasins,

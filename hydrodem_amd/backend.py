@@ -188,6 +188,15 @@ class _ProximityStats(_SizedStats):
                 ("sources", ctypes.c_int64), ("unreached", ctypes.c_int64)]
 
 
+class _FlowSumStats(_SizedStats):
+    """``hdem_flowsum_stats`` (the binding is hydrodem_amd/flowsum.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_hops", ctypes.c_int32),
+                ("exits", ctypes.c_int64), ("nan_weights", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_tile", ctypes.c_float), ("ms_forest", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
 # columns of the depression table, in the order of the C ABI's pointers
 DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
@@ -318,6 +327,10 @@ SIGNATURES = {
                       [_c.c_double] * 3 + [_vp] * 6 + [_c.POINTER(_ProximityStats)],
     "hdem_proximity_dev": [_vp, _vp, _i, _c.c_uint32, _i, _i, _vp, _c.c_double, _c.c_uint32] +
                           [_c.c_double] * 3 + [_vp] * 6 + [_c.POINTER(_ProximityStats)],
+    "hdem_flowsum_u8": [_vp, _vp, _i, _i, _vp, _i, _i, _c.c_int64, _vp, _vp, _vp,
+                        _c.POINTER(_FlowSumStats)],
+    "hdem_flowsum_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _i, _c.c_int64, _vp, _vp, _vp,
+                            _c.POINTER(_FlowSumStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

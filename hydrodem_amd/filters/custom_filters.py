@@ -24,7 +24,8 @@ construction, SURVEY section 2 #9 / 8e "not shardable"; no kernel is wanted):
 unchanged when ``filters`` resolves here.
 
 New operators (the reference has neither): ``SinkFill``,
-``D8FlowDirection``, ``ResolveFlats``, ``FlowAccumulation``, ``Watersheds``, ``FlowDistance``,
+``D8FlowDirection``, ``ResolveFlats``, ``FlowAccumulation``, ``WeightedFlowAccumulation``,
+``Watersheds``, ``FlowDistance``,
 ``HeightAboveDrainage``, ``UpstreamFlowLength``, ``StreamOrder``, ``StreamNetwork`` and the
 chains ``DemToHAND``, ``DemToStreamOrder`` and ``DemToStreamNetwork``, shaped like every other
 ``Filter``.
@@ -64,6 +65,7 @@ from .. import streamnet as _streamnet
 from .. import zonal as _zonal
 from .. import terrain as _terrain
 from .. import proximity as _proximity
+from .. import flowsum as _flowsum
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -407,6 +409,71 @@ class FlowAccumulation(Filter):  # pylint: disable=too-few-public-methods
         _check_raster("FlowAccumulation", raster, np.uint8, "uint8 D8 codes")
         out, self.stats = backend.flowacc_dev(raster)
         return out
+
+
+class WeightedFlowAccumulation(Filter):  # pylint: disable=too-few-public-methods
+    """Weighted D8 flow accumulation (new operator; ArcGIS *Flow Accumulation* with a weight
+    raster, TauDEM ``aread8 -wg``).  Input: a uint8 H x W raster of ESRI D8 codes exactly as
+    ``FlowAccumulation`` takes them.  ``weights``: an H x W NumPy array or ``DeviceRaster`` of
+    uint8, uint32 or float32 (float64 is refused, not narrowed).  Every cell's weight is
+    quantised to an integer ``q``: the weight itself for the integer types, which take
+    ``frac_bits=0``, and ``rint(float64(w) * 2^frac_bits)`` for float32, ``frac_bits`` 0 ... 30.
+    ``S[c] = q[c] + sum(S[d])`` over the neighbours ``d`` whose code points at ``c`` is summed in
+    int64: exact, identical from run to run.
+
+    ``output`` fixes what ``apply`` returns: ``"sum"`` int64 ``S``; ``"value"`` float32
+    ``float32(float64(S) * 2^-frac_bits)``; ``"mask"`` uint8, 1 where
+    ``S >= ceil(threshold * 2^frac_bits)``, with ``threshold`` in weight units -- a stream mask
+    for ``FlowDistance``, ``HeightAboveDrainage``, ``StreamOrder``, ``StreamNetwork``,
+    ``EuclideanDistance`` and ``BurnStreams``.
+
+    A NaN weight contributes 0 (``stats["nan_weights"]`` counts them).  ``ValueError`` for
+    operands of another type, dtype or shape, ``frac_bits`` out of range, a ``threshold`` that
+    does not go with the output or comes out below 1 (all before the device is touched), for a
+    negative or infinite weight, a quantised weight above 2^31 - 1 (so that no sum can
+    overflow), a byte that is not a D8 code, codes that form a cycle and more than 2^32 - 1
+    cells.
+
+    Attributes
+    ----------
+    stats : dict
+        nan_weights, exits (nodes of the exit forest), max_hops (tile crossings of the longest
+        forest walk), tile_h / tile_w of the last call; phase times when profiling is on.
+    """
+
+    auto_device = True      # device form == host form for a uint8 code raster
+    WEIGHT_TYPES = (np.uint8, np.uint32, np.float32)
+    OUTPUTS = {name: np.dtype(dtype) for name, dtype in _flowsum.FS_OUTPUTS}
+
+    def __init__(self, weights, frac_bits=16, output="value", threshold=None):
+        if weights is None:
+            raise ValueError("WeightedFlowAccumulation needs the weights it sums")
+        self.weights = _Given(weights, "weights", self.WEIGHT_TYPES).value
+        if not isinstance(output, str) or output not in self.OUTPUTS:
+            raise ValueError(f"output is one of {list(self.OUTPUTS)}, got {output!r}")
+        self.frac_bits, self.output, self.threshold = frac_bits, output, threshold
+        self.dtype = self.OUTPUTS[output]
+        self.stats = {}
+        # everything but the shapes, on 1 x 1 stand-ins
+        _flowsum.flowsum_args(np.empty((1, 1), np.uint8), _Given(self.weights).stand_in(),
+                              frac_bits, output, threshold)
+
+    def _args(self, codes):
+        _flowsum.flowsum_args(codes, self.weights, self.frac_bits, self.output, self.threshold)
+
+    def apply(self, image_to_filter):
+        super().apply(image_to_filter)
+        self._args(image_to_filter)
+        outs, self.stats = _flowsum.flowsum(image_to_filter, _Given(self.weights).host(),
+                                            self.frac_bits, self.output, self.threshold)
+        return outs[self.output]
+
+    def apply_device(self, raster):
+        self._args(raster)
+        with _Given(self.weights).device(raster.ctx) as weights:
+            outs, self.stats = _flowsum.flowsum_dev(raster, weights, self.frac_bits,
+                                                    self.output, self.threshold)
+        return outs[self.output]
 
 
 class Watersheds(Filter):  # pylint: disable=too-few-public-methods

@@ -1087,6 +1087,64 @@ int hdem_proximity_dev(hdem_ctx *ctx, const void *sources, int source_kind, uint
                        uint32_t *nearest, uint32_t *label, float *distance, float *rise,
                        float *burned, hdem_proximity_stats *stats);    /* device pointers */
 
+/* ---- A16  WeightedFlowAccumulation.apply  (new operator: weighted D8 flow accumulation) ----
+ * d8: uint8 ESRI codes exactly as hdem_flowacc_u8 takes them (0, or a code pointing outside
+ * the raster, is terminal; any byte that is not a code is invalid).
+ * A donor of c is a neighbour whose code points at c.  For every cell
+ *   S[c] = q(w[c]) + sum of S[d] over the donors d of c,
+ * the sum of the quantised weights of every cell whose D8 path passes through c, c included.
+ * weights is H x W of weight_type:
+ *   HDEM_FLOWSUM_U8, HDEM_FLOWSUM_U32   q(w) = w; frac_bits must be 0
+ *   HDEM_FLOWSUM_F32                    q(w) = (int64)rint((double)w * 2^frac_bits), frac_bits
+ *                                       0 ... 30: the exact double product rounded once, to
+ *                                       nearest even (A13's rule); -0.0 counts as 0
+ * A NaN weight contributes 0 and is counted in stats->nan_weights.  A negative or infinite
+ * weight, and any q(w) > 2^31 - 1, is refused: HDEM_ERR_BAD_ARG with their count, after the
+ * call's one synchronisation.  With q < 2^31 and H * W < 2^32 every sum is below 2^63.
+ * Outputs, all H x W, each may be NULL (not wanted), at least one must not be; all are written
+ * by the last launch from one walk:
+ *   sum     int64    S
+ *   value   float32  (float)((double)S * 2^-frac_bits), two roundings to nearest even
+ *   mask    uint8    1 where S >= threshold, else 0; threshold >= 1 (in units of q) with mask,
+ *                    0 without.  Goes as it is wherever HDEM_FT_STREAMS_MASK_U8 is taken.
+ * Integer adds only: identical from run to run, whatever the schedule, and between the host
+ * and device forms.
+ * HDEM_ERR_BAD_ARG before any allocation or launch: H * W > 2^32 - 1; an unknown weight_type;
+ * frac_bits out of range or not 0 with integer weights; no output; mask without threshold >= 1
+ * or a threshold without mask; an output that overlaps an input or another output.  After the
+ * launches, in bounded time: an invalid byte, codes that form a cycle ("N cells never drain"),
+ * weights out of range.  On error the contents of the outputs are unspecified.
+ * Workspace: 28 B per tile-perimeter slot, about 1.7 B per cell, from the context's arena.
+ * The _dev form synchronises the context's stream once to read its counters.  stats may be
+ * NULL; otherwise the caller sets stats->struct_size = sizeof(hdem_flowsum_stats) first (48
+ * bytes in this version; a shorter struct is filled as far as it goes).  The three phase times
+ * are filled only while profiling is on (hdem_profile_enable); the call has no kernel id. */
+typedef enum hdem_flowsum_weight_type {   /* numbered as the zonal value types are */
+    HDEM_FLOWSUM_F32 = 1,
+    HDEM_FLOWSUM_U32 = 2,
+    HDEM_FLOWSUM_U8 = 3
+} hdem_flowsum_weight_type;
+typedef struct hdem_flowsum_stats {
+    uint32_t struct_size;   /* in: sizeof(hdem_flowsum_stats), set by the caller            */
+    int32_t max_hops;       /* tile crossings of the longest walk over the exit forest      */
+    int64_t exits;          /* cells that drain into another tile: nodes of the exit forest */
+    int64_t nan_weights;    /* NaN weights: each contributed 0                              */
+    int32_t tile_h, tile_w;
+    float ms_tile;          /* phase A: weights quantised, in-tile walks, perimeter paths
+                               (HIP events; profiling)                                      */
+    float ms_forest;        /* phase B: the exit forest                                     */
+    float ms_final;         /* phase C: seeded in-tile walks, outputs written               */
+    int32_t reserved;       /* 0                                                            */
+} hdem_flowsum_stats;       /* sizeof == 48 */
+int hdem_flowsum_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *weights,
+                    int weight_type, int frac_bits, int64_t threshold, int64_t *sum,
+                    float *value, uint8_t *mask,
+                    hdem_flowsum_stats *stats);        /* host pointers, synchronous */
+int hdem_flowsum_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *weights,
+                        int weight_type, int frac_bits, int64_t threshold, int64_t *sum,
+                        float *value, uint8_t *mask,
+                        hdem_flowsum_stats *stats);    /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
