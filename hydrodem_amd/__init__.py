@@ -23,6 +23,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      PostProcessingFinal, SinkFill,
                                      D8FlowDirection, FlowAccumulation, Watersheds,
                                      WeightedFlowAccumulation,
+                                     UpstreamExtreme, BreachDepressions,
                                      FlowDistance, HeightAboveDrainage, UpstreamFlowLength,
                                      StreamOrder, DemToStreamOrder, StreamNetwork,
                                      DemToStreamNetwork, ZonalStatistics, DemToBasins,

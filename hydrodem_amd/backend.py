@@ -197,6 +197,21 @@ class _FlowSumStats(_SizedStats):
                 ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class _UpExtremeStats(_SizedStats):
+    """``hdem_upextreme_stats`` (the binding is hydrodem_amd/upextreme.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_hops", ctypes.c_int32),
+                ("exits", ctypes.c_int64), ("absent", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_tile", ctypes.c_float), ("ms_forest", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+class _BreachStats(_SizedStats):
+    """``hdem_breach_stats``: the extreme's fields, then the pits and the cells lowered."""
+    _fields_ = _UpExtremeStats._fields_ + [("pits", ctypes.c_int64),
+                                           ("lowered", ctypes.c_int64)]
+
+
 DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
 # columns of the depression table, in the order of the C ABI's pointers
 DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
@@ -331,6 +346,12 @@ SIGNATURES = {
                         _c.POINTER(_FlowSumStats)],
     "hdem_flowsum_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _i, _c.c_int64, _vp, _vp, _vp,
                             _c.POINTER(_FlowSumStats)],
+    "hdem_upextreme_u8": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp,
+                          _c.POINTER(_UpExtremeStats)],
+    "hdem_upextreme_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp,
+                              _c.POINTER(_UpExtremeStats)],
+    "hdem_breach_f32": [_vp, _vp, _vp, _i, _i, _vp, _vp, _c.POINTER(_BreachStats)],
+    "hdem_breach_f32_dev": [_vp, _vp, _vp, _i, _i, _vp, _vp, _c.POINTER(_BreachStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

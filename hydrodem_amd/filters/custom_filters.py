@@ -25,7 +25,7 @@ unchanged when ``filters`` resolves here.
 
 New operators (the reference has neither): ``SinkFill``,
 ``D8FlowDirection``, ``ResolveFlats``, ``FlowAccumulation``, ``WeightedFlowAccumulation``,
-``Watersheds``, ``FlowDistance``,
+``UpstreamExtreme``, ``BreachDepressions``, ``Watersheds``, ``FlowDistance``,
 ``HeightAboveDrainage``, ``UpstreamFlowLength``, ``StreamOrder``, ``StreamNetwork`` and the
 chains ``DemToHAND``, ``DemToStreamOrder`` and ``DemToStreamNetwork``, shaped like every other
 ``Filter``.
@@ -66,6 +66,7 @@ from .. import zonal as _zonal
 from .. import terrain as _terrain
 from .. import proximity as _proximity
 from .. import flowsum as _flowsum
+from .. import upextreme as _upextreme
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -473,6 +474,65 @@ class WeightedFlowAccumulation(Filter):  # pylint: disable=too-few-public-method
         with _Given(self.weights).device(raster.ctx) as weights:
             outs, self.stats = _flowsum.flowsum_dev(raster, weights, self.frac_bits,
                                                     self.output, self.threshold)
+        return outs[self.output]
+
+
+class UpstreamExtreme(Filter):  # pylint: disable=too-few-public-methods
+    """Upstream D8 minimum or maximum (new operator; TauDEM ``d8flowpathextremeup``).  Input: a
+    uint8 H x W raster of ESRI D8 codes exactly as ``FlowAccumulation`` takes them.  ``values``:
+    an H x W NumPy array or ``DeviceRaster`` of float32 or uint32 (float64 is refused, not
+    narrowed).  For every cell, over the cell and every cell whose D8 path passes through it,
+    the least (``mode="min"``) or greatest (``mode="max"``) present value.  A float32 NaN is
+    absent (``stats["absent"]`` counts them); floats are ordered
+    ``-inf < ... < -0.0 < +0.0 < ... < +inf``.
+
+    ``output`` fixes what ``apply`` returns: ``"extreme"``, of the values' dtype, the bits of
+    the cell that holds the extreme (the quiet NaN where nothing upstream is present), or
+    ``"where"``, uint32, that cell's flat index (``0xFFFFFFFF`` where nothing is present).
+    Among cells that hold the same value the smallest flat index is the holder, in both modes.
+    Min and max are reductions on a total order: identical from run to run.
+
+    ``ValueError`` for operands of another type, dtype or shape, an unknown ``mode`` or
+    ``output`` (all before the device is touched), a byte that is not a D8 code, codes that form
+    a cycle and more than 2^32 - 1 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        absent, exits (nodes of the exit forest), max_hops (tile crossings of the longest
+        forest walk), tile_h / tile_w of the last call; phase times when profiling is on.
+    """
+
+    auto_device = True      # device form == host form for a uint8 code raster
+    VALUE_TYPES = (np.float32, np.uint32)
+
+    def __init__(self, values, mode="max", output="extreme"):
+        if values is None:
+            raise ValueError("UpstreamExtreme needs the values it reduces")
+        self.values = _Given(values, "values", self.VALUE_TYPES).value
+        if not isinstance(output, str) or output not in _upextreme.UE_OUTPUTS:
+            raise ValueError(f"output is one of {list(_upextreme.UE_OUTPUTS)}, got {output!r}")
+        self.mode, self.output = mode, output
+        self.dtype = np.dtype(np.uint32) if output == "where" else np.dtype(self.values.dtype)
+        self.stats = {}
+        # everything but the shapes, on 1 x 1 stand-ins
+        _upextreme.upextreme_args(np.empty((1, 1), np.uint8), _Given(self.values).stand_in(),
+                                  mode, output)
+
+    def _args(self, codes):
+        _upextreme.upextreme_args(codes, self.values, self.mode, self.output)
+
+    def apply(self, image_to_filter):
+        super().apply(image_to_filter)
+        self._args(image_to_filter)
+        outs, self.stats = _upextreme.upextreme(image_to_filter, _Given(self.values).host(),
+                                                self.mode, self.output)
+        return outs[self.output]
+
+    def apply_device(self, raster):
+        self._args(raster)
+        with _Given(self.values).device(raster.ctx) as values:
+            outs, self.stats = _upextreme.upextreme_dev(raster, values, self.mode, self.output)
         return outs[self.output]
 
 
@@ -1631,6 +1691,61 @@ class DemToHAND(ComposedFilter):  # pylint: disable=too-few-public-methods
                 self.distance = trace.distance
                 stack.pop_all()                     # the caller's to free from here on
             return hand
+
+
+class BreachDepressions(ComposedFilter):  # pylint: disable=too-few-public-methods
+    """Depression breaching (new operator; Soille's carving, Whitebox and RichDEM
+    *BreachDepressions*): the other way to condition a DEM.  Where ``SinkFill`` raises every
+    depression to its spill level, this cuts a trench at the level of each pit down to where the
+    terrain is lower again and leaves the rest of the depression alone.  Takes a float32 DEM and
+    returns the carved DEM.
+
+    One device-resident chain, nothing downloaded in between: ``SinkFill(epsilon=0)`` and
+    ``D8FlowDirection`` with ``ResolveFlats`` (one call, as in
+    ``HydroConditioning(epsilon=0.0, flats="resolve")``) give a forest in which every cell
+    reaches an outlet, then one reduction up that forest: every cell takes the elevation of the
+    lowest pit upstream of it where that is below its own, and stays bit for bit otherwise (NaN
+    included).  A pit is a non-NaN cell off the raster's one-cell ring with no NaN neighbour and
+    no strictly lower neighbour.  An outlet on the ring that a trench reaches is lowered too.
+
+    The carved DEM has no sinks (its ``epsilon=0`` fill is itself) and carving it again changes
+    nothing.  ``HydroConditioning(epsilon=0.0, flats="resolve")`` gives its D8 codes.
+
+    ``stats`` maps ``SinkFill``, ``ResolveFlats`` and ``BreachDepressions`` (pits, lowered,
+    exits, max_hops, ...) to the stats of their stage.  With ``keep_partial_results=True`` the
+    last call leaves ``filled`` (the exact fill), ``codes`` (the forest) and ``source`` (uint32,
+    the flat index of the pit a cell was lowered to, ``0xFFFFFFFF`` where it is unchanged): host
+    arrays after ``apply``, device rasters (the caller's to free) after ``apply_device``;
+    otherwise they are ``None``."""
+
+    def __init__(self, keep_partial_results=False):
+        super().__init__()
+        self.filters = [SinkFill(epsilon=0.0), D8FlowDirection()]
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.filled = self.codes = self.source = None
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("BreachDepressions", image_to_filter, np.float32, "a float32 DEM")
+        return _through_device(self, image_to_filter,
+                               ("filled", "codes", "source")
+                               if self.keep_partial_results else ())
+
+    def apply_device(self, raster):
+        _check_raster("BreachDepressions", raster, np.float32, "a float32 DEM")
+        fill = self.filters[0]
+        self.filled = self.codes = self.source = None
+        with contextlib.ExitStack() as stack:
+            filled, codes, resolve_stats = _fill_d8(stack, raster, fill, "resolve")
+            outs, breach_stats = _upextreme.breach_dev(
+                raster, codes, ("carved", "source") if self.keep_partial_results else ("carved",))
+            self.stats = {"SinkFill": fill.stats, "ResolveFlats": resolve_stats,
+                          "BreachDepressions": breach_stats}
+            if self.keep_partial_results:
+                self.filled, self.codes, self.source = filled, codes, outs["source"]
+                stack.pop_all()                     # the caller's to free from here on
+            return outs["carved"]
 
 
 class DemToWetness(ComposedFilter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes

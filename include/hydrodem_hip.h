@@ -1145,6 +1145,108 @@ int hdem_flowsum_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const vo
                         float *value, uint8_t *mask,
                         hdem_flowsum_stats *stats);    /* device pointers */
 
+/* ---- A17  UpstreamExtreme.apply  (new operator: upstream D8 minimum / maximum) ----
+ * d8: uint8 ESRI codes exactly as hdem_flowacc_u8 takes them (0, or a code pointing outside
+ * the raster, is terminal; any byte that is not a code is invalid).
+ * U(c) is c together with every cell whose D8 path passes through c.  values is H x W of
+ * value_type HDEM_UPEXT_F32 or HDEM_UPEXT_U32.  A float32 NaN is absent: it takes no part and
+ * is counted in stats->absent.  Floats are ordered by their bits as a sign-magnitude number,
+ *   -inf < ... < -0.0 < +0.0 < ... < +inf,
+ * uint32 values as they are, and all of those are present.  For every cell
+ *   E[c] = best(v[c], E[d] over the donors d of c),
+ * the least (HDEM_UPEXT_MIN) or greatest (HDEM_UPEXT_MAX) present value over U(c).  Where
+ * several cells of U(c) hold it with the same bits, the one with the smallest flat index is the
+ * holder, in both modes.
+ * Outputs, both H x W, each may be NULL (not wanted), at least one must not be:
+ *   extreme  of the values' type   E[c], the holder's own bits; for float32 the quiet NaN
+ *                                  0x7FC00000 where nothing in U(c) is present
+ *   where    uint32                the holder's flat index, 0xFFFFFFFF where nothing is present
+ *                                  (H * W <= 2^32 - 1 keeps that value free)
+ * One reduction over a 64-bit word per cell, key << 32 | index under unsigned min or
+ * key << 32 | ~index under unsigned max: idempotent, commutative and associative on a total
+ * order, so the result is identical from run to run, whatever the schedule, and between the
+ * host and device forms.
+ * HDEM_ERR_BAD_ARG before any allocation or launch: H * W > 2^32 - 1; an unknown value_type or
+ * mode; null values; no output; an output that overlaps an input or the other output.  After
+ * the launches, in bounded time: an invalid byte, codes that form a cycle ("N cells never
+ * drain").  On error the contents of the outputs are unspecified; the context stays usable.
+ * Workspace: 28 B per tile-perimeter slot, about 1.7 B per cell, from the context's arena.
+ * The _dev form synchronises the context's stream once to read its counters.  stats may be
+ * NULL; otherwise the caller sets stats->struct_size = sizeof(hdem_upextreme_stats) first (48
+ * bytes in this version; a shorter struct is filled as far as it goes).  The three phase times
+ * are filled only while profiling is on (hdem_profile_enable); the call has no kernel id. */
+typedef enum hdem_upext_value_type {   /* numbered as the flowsum weight types are */
+    HDEM_UPEXT_F32 = 1,
+    HDEM_UPEXT_U32 = 2
+} hdem_upext_value_type;
+typedef enum hdem_upext_mode {
+    HDEM_UPEXT_MIN = 0,
+    HDEM_UPEXT_MAX = 1
+} hdem_upext_mode;
+typedef struct hdem_upextreme_stats {
+    uint32_t struct_size;   /* in: sizeof(hdem_upextreme_stats), set by the caller          */
+    int32_t max_hops;       /* tile crossings of the longest walk over the exit forest      */
+    int64_t exits;          /* cells that drain into another tile: nodes of the exit forest */
+    int64_t absent;         /* NaN values: they took no part                                */
+    int32_t tile_h, tile_w;
+    float ms_tile;          /* phase A: values read, in-tile walks, perimeter paths
+                               (HIP events; profiling)                                      */
+    float ms_forest;        /* phase B: the exit forest                                     */
+    float ms_final;         /* phase C: seeded in-tile walks, outputs written               */
+    int32_t reserved;       /* 0                                                            */
+} hdem_upextreme_stats;     /* sizeof == 48 */
+int hdem_upextreme_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *values,
+                      int value_type, int mode, void *extreme, uint32_t *where,
+                      hdem_upextreme_stats *stats);        /* host pointers, synchronous */
+int hdem_upextreme_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *values,
+                          int value_type, int mode, void *extreme, uint32_t *where,
+                          hdem_upextreme_stats *stats);    /* device pointers */
+
+/* ---- A18  BreachDepressions.apply  (new operator: depression breaching, "carving") ----
+ * dem: float32, H x W.  d8: a forest over it, any valid acyclic codes as A17 takes them.
+ * A pit is a non-NaN cell that is not on the raster's one-cell ring, has no NaN 8-neighbour
+ * and no 8-neighbour whose elevation is strictly lower (float <).  Cells on the ring and cells
+ * next to nodata are the fill's outlets and never pits.
+ *   t[c]       A17 in min mode over (pit ? dem : absent): the lowest pit upstream of c
+ *   carved[c]  t[c] where it is present and t[c] < dem[c] (float <), else dem[c] bit for bit,
+ *              NaN payloads included
+ *   source[c]  uint32, optional (NULL): the flat index of the pit whose level c was lowered
+ *              to, 0xFFFFFFFF where c is unchanged
+ * A trench is cut at the pit's level from each pit down its D8 path to where the terrain is
+ * lower again; the rest of the depression stays.  An outlet on the ring that a trench reaches
+ * is lowered like any other cell.
+ * Guarantee: when d8 are the A12 (ResolveFlats) codes of the eps = 0 fill of the same DEM,
+ * carved has no sinks (its eps = 0 fill is itself) and carving it again changes nothing.  A
+ * local minimum c of carved that is no outlet has no lower neighbour in dem either (carved <=
+ * dem), so it is a pit, t[c] <= dem[c] and carved[c] = t[c]; for its receiver r, U(r) contains
+ * U(c), so carved[r] <= t[r] <= t[c]: every cell has a non-ascending path to an outlet.  The
+ * forest of a sink-free DEM never ascends, so no upstream pit is lower than the cell.
+ * The launches are A17's after one radius-1 stencil launch that writes the seeds; the last
+ * launch writes carved and source.  Errors as A17 (dem and carved must not be NULL), and carved
+ * or source overlapping dem, d8 or each other.
+ * Workspace: A17's plus the seed raster, 4 B per cell, from the context's arena.
+ * stats as A17's with the pit count and the cells lowered; absent counts the cells that are
+ * not pits.  sizeof(hdem_breach_stats) is 64 in this version. */
+typedef struct hdem_breach_stats {
+    uint32_t struct_size;   /* in: sizeof(hdem_breach_stats), set by the caller             */
+    int32_t max_hops;
+    int64_t exits;
+    int64_t absent;         /* cells that are not pits                                      */
+    int32_t tile_h, tile_w;
+    float ms_tile;          /* phase A, the pit stencil included                            */
+    float ms_forest;
+    float ms_final;
+    int32_t reserved;       /* 0                                                            */
+    int64_t pits;           /* pits                                                         */
+    int64_t lowered;        /* cells of carved below dem                                    */
+} hdem_breach_stats;        /* sizeof == 64 */
+int hdem_breach_f32(hdem_ctx *ctx, const float *dem, const uint8_t *d8, int H, int W,
+                    float *carved, uint32_t *source,
+                    hdem_breach_stats *stats);        /* host pointers, synchronous */
+int hdem_breach_f32_dev(hdem_ctx *ctx, const float *dem, const uint8_t *d8, int H, int W,
+                        float *carved, uint32_t *source,
+                        hdem_breach_stats *stats);    /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
