@@ -280,12 +280,11 @@ __device__ __forceinline__ int float_key(float f)
 #endif
 
 // Hub start: a tile holds d (cost to its hub) until its first visit makes max(d, level of the
-// hub) of it.  lv[3 * (dy + 1) + dx + 1]: that level for the tile at (ty + dy, tx + dx) while
-// it has not had its first visit, -inf once it has (or when there is no such tile).
-struct hub_bounds {
-    float lv[9];
-    bool mine;         // this tile's own first visit: write the tile back whatever happens
-};
+// hub) of it.  The asynchronous driver holds that level for the nine tiles under a window --
+// -inf once a tile has had its first visit, or where there is none -- and hands a visit, by
+// value, what each lane needs of them: the bound of the tile above / beside / below the lane's
+// column (window visit), of the tile above / below / left / right of the lane's halo cells
+// (flat visit).  -inf everywhere is "no hub start".
 
 struct visit_result {
 #ifdef HDEM_VISIT_PROF
@@ -310,7 +309,10 @@ __device__ __forceinline__ visit_result tile_visit(const float *__restrict__ zg,
                                                    int H, int W, float eps, int ty, int tx,
                                                    float *T, uint8_t *d8 = nullptr,
                                                    float flat_level = HDEM_INF,
-                                                   const hub_bounds *hb = nullptr)
+                                                   float hub_t = -HDEM_INF,
+                                                   float hub_m = -HDEM_INF,
+                                                   float hub_b = -HDEM_INF,
+                                                   bool first_visit = false)
 {
     const int lane = threadIdx.x;
     const int y0 = ty * FT, x0 = tx * FT;              // window origin (= halo row/col)
@@ -378,13 +380,7 @@ __device__ __forceinline__ visit_result tile_visit(const float *__restrict__ zg,
     unsigned free_lo = 0, free_hi = 0;          // per lane: bit 31 - r of lo / hi <- row r / 32 + r free
     // (hub start) cells of tiles that have not had their first visit still hold d: raise them
     // to their tile's start bound -- per lane the bound of the tile above / beside / below
-    float hub_t = -HDEM_INF, hub_m = -HDEM_INF, hub_b = -HDEM_INF;
-    if (COHERENT && hb) {
-        const int k = lane == 0 ? 0 : (lane == WN - 1 ? 2 : 1);
-        hub_t = k == 0 ? hb->lv[0] : (k == 1 ? hb->lv[1] : hb->lv[2]);
-        hub_m = k == 0 ? hb->lv[3] : (k == 1 ? hb->lv[4] : hb->lv[5]);
-        hub_b = k == 0 ? hb->lv[6] : (k == 1 ? hb->lv[7] : hb->lv[8]);
-    }
+    // (hub_t / hub_m / hub_b)
     // What depends on the row is decided per lane against a row number held in a register --
     // one vector compare with the row as a literal -- not per row in scalar code: the uniform
     // form cost ten scalar instructions per row (compare, select, combine the masks), 640 per
@@ -463,7 +459,8 @@ __device__ __forceinline__ visit_result tile_visit(const float *__restrict__ zg,
     V.all |= V.first | V.last;
     bool more = V.all != 0;
     out.changed = more;
-    const bool force_store = COHERENT && hb && hb->mine;
+    // (this tile's own first visit: written back whatever happens)
+    const bool force_store = COHERENT && first_visit;
     // lanes whose cell of row 1 / row 62 / column 1 / column 62 moved during the visit
     // (columns: lane = row) -- what the wake tests below are gated on
     const unsigned long long b1 = 1ull << 1, bl = 1ull << FT;
@@ -794,15 +791,24 @@ __device__ __attribute__((noinline)) int async_pick(int b, int G, int S, int nti
 {
     const int lane = threadIdx.x;
     int *my_state = state + (size_t)b * S, *my_prio = prio + (size_t)b * S;
+    const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(
+        my_state, 0, S * (int)sizeof(int), 0x00020000);
+    const __amdgpu_buffer_rsrc_t prsrc = __builtin_amdgcn_make_buffer_rsrc(
+        my_prio, 0, S * (int)sizeof(int), 0x00020000);
     int zero_reads = 0;
     for (;;) {
         // the queued slot with the lowest key
+        // (state word and key of a slot as two agent-scope loads in flight together, by every
+        // lane: one round trip, not two)
         long long best = 0x7fffffffffffffffll;
         for (int base = 0; base < S; base += NT) {
             const int slot = base + lane;
+            const unsigned off = (unsigned)min(slot, S - 1) * (unsigned)sizeof(int);
+            const int st = __builtin_amdgcn_raw_buffer_load_b32(srsrc, off, 0, AUX_SC1);
+            const int key = __builtin_amdgcn_raw_buffer_load_b32(prsrc, off, 0, AUX_SC1);
             long long cand = 0x7fffffffffffffffll;
-            if (slot < S && slot * G + b < ntiles && ld_relaxed(&my_state[slot]) == ST_QUEUED)
-                cand = ((long long)ld_relaxed(&my_prio[slot]) << 32) | (unsigned)slot;
+            if (slot < S && slot * G + b < ntiles && st == ST_QUEUED)
+                cand = ((long long)key << 32) | (unsigned)slot;
             best = cand < best ? cand : best;
         }
 #pragma unroll
@@ -911,8 +917,8 @@ struct flat_result {
 };
 
 __device__ __attribute__((noinline)) flat_result flat_visit(float *wg, int H, int W, int ty, int tx,
-                                                            float L, float zmax,
-                                                            const hub_bounds *hb)
+                                                            float L, float zmax, float hub_t,
+                                                            float hub_b, float hub_l, float hub_r)
 {
     const int lane = threadIdx.x;
     const int y0 = ty * FT, x0 = tx * FT;
@@ -928,14 +934,11 @@ __device__ __attribute__((noinline)) flat_result flat_visit(float *wg, int H, in
     // (only tiles whose window lies inside the raster are ever flat)
     float top = ld(at(0, lane)), bottom = ld(at(WN - 1, lane));
     float left = ld(at(lane, 0)), right = ld(at(lane, WN - 1));             // lane = row
-    if (hb) {
-        // (hub start) halo cells of tiles that still hold d: raised to their start bound
-        const int k = lane == 0 ? 0 : (lane == WN - 1 ? 2 : 1);
-        top = fmaxf(top, k == 0 ? hb->lv[0] : (k == 1 ? hb->lv[1] : hb->lv[2]));
-        bottom = fmaxf(bottom, k == 0 ? hb->lv[6] : (k == 1 ? hb->lv[7] : hb->lv[8]));
-        left = fmaxf(left, k == 0 ? hb->lv[0] : (k == 1 ? hb->lv[3] : hb->lv[6]));
-        right = fmaxf(right, k == 0 ? hb->lv[2] : (k == 1 ? hb->lv[5] : hb->lv[8]));
-    }
+    // (hub start) halo cells of tiles that still hold d: raised to their start bound
+    top = fmaxf(top, hub_t);
+    bottom = fmaxf(bottom, hub_b);
+    left = fmaxf(left, hub_l);
+    right = fmaxf(right, hub_r);
     const float low = wave_min(fminf(fminf(top, bottom), fminf(left, right)));
     flat_result out = {1, false, 0u, L};
     if (low >= L) return out;                       // nothing new
@@ -1299,41 +1302,61 @@ __global__ __launch_bounds__(NT, 2) void fill_async_kernel(const float *__restri
         // (hub start) which of the nine tiles under the window have had their first visit?
         // Read BEFORE the window: a tile found visited had its cells in memory before its
         // mark; a tile found unvisited has its cells raised to its start bound, which is right
-        // for d and harmless for newer values.  Rides on the round trip of the flat level.
-        hub_bounds hb;
-        bool use_hb = false, first_visit = false;
-        const int fb_raw = HAS_EPS ? FLAT_NONE : ld_relaxed(flat + t);
-        if (!HAS_EPS && hub_lev) {
-            const int k9 = threadIdx.x < 9 ? (int)threadIdx.x : 4;
-            const int ny = ty + k9 / 3 - 1, nx = tx + k9 % 3 - 1;
-            const bool there = threadIdx.x < 9 && ny >= 0 && ny < tiles_y && nx >= 0 && nx < tiles_x;
-            float l = -HDEM_INF;
-            int seen = 1;
-            if (there) {
-                seen = ld_relaxed(applied + ny * tiles_x + nx);
-                l = hub_lev[(size_t)(2 * ny + 1) * (2 * tiles_x + 1) + 2 * nx + 1];
+        // for d and harmless for newer values.
+        // All of it is one batch of loads, issued back to back and waited for once: the tile's
+        // flat level, its highest terrain (used only if the tile is flat; the word is there
+        // either way), the nine marks and the nine hub levels.  What other workgroups write
+        // comes through agent-scope (sc1) buffer loads, which are pipelined like any load.
+        bool first_visit = false;
+        int fb_raw = FLAT_NONE, zm_raw = FLAT_NONE;
+        float l = -HDEM_INF;          // lanes 0..8: the start bound of the tile at (k / 3, k % 3)
+        if (!HAS_EPS) {
+            const int words = ntiles * (int)sizeof(int);
+            const unsigned mine = (unsigned)t * (unsigned)sizeof(int);
+            const __amdgpu_buffer_rsrc_t frsrc =
+                __builtin_amdgcn_make_buffer_rsrc(flat, 0, words, 0x00020000);
+            const __amdgpu_buffer_rsrc_t mrsrc =
+                __builtin_amdgcn_make_buffer_rsrc(zmax, 0, words, 0x00020000);
+            fb_raw = __builtin_amdgcn_raw_buffer_load_b32(frsrc, 0, mine, AUX_SC1);
+            zm_raw = __builtin_amdgcn_raw_buffer_load_b32(mrsrc, 0, mine, AUX_SC1);
+            if (hub_lev) {
+                const int k9 = threadIdx.x < 9 ? (int)threadIdx.x : 4;
+                const int ny = ty + k9 / 3 - 1, nx = tx + k9 % 3 - 1;
+                const bool there = threadIdx.x < 9 && ny >= 0 && ny < tiles_y && nx >= 0 && nx < tiles_x;
+                // (every lane loads: the lanes without a neighbour read the tile's own words)
+                const int my = there ? ny : ty, mx = there ? nx : tx;
+                const __amdgpu_buffer_rsrc_t arsrc =
+                    __builtin_amdgcn_make_buffer_rsrc(applied, 0, words, 0x00020000);
+                const int seen_raw = __builtin_amdgcn_raw_buffer_load_b32(
+                    arsrc, (unsigned)(my * tiles_x + mx) * (unsigned)sizeof(int), 0, AUX_SC1);
+                const float lev = hub_lev[(size_t)(2 * my + 1) * (2 * tiles_x + 1) + 2 * mx + 1];
+                const int seen = there ? seen_raw : 1;
+                // (a NaN level: the tile is an outlet of the hub graph, its d is its bound)
+                l = (seen || lev != lev) ? -HDEM_INF : (lev >= HUB_BIG ? HDEM_INF : lev);
+                // The marks have come back before anything below asks for W: the tile's own
+                // mark passes through this statement, and no access to memory moves across it.
+                int seen_mine = __builtin_amdgcn_readlane(seen, 4);
+                asm volatile("" : "+s"(seen_mine) : : "memory");
+                first_visit = seen_mine == 0;
             }
-            // (a NaN level: the tile is an outlet of the hub graph, its d is its bound)
-            l = (seen || l != l) ? -HDEM_INF : (l >= HUB_BIG ? HDEM_INF : l);
-            first_visit = __builtin_amdgcn_readlane(seen, 4) == 0;
-            use_hb = first_visit || __ballot(l > -HDEM_INF) != 0;
-            if (use_hb) {
-#pragma unroll
-                for (int k = 0; k < 9; ++k)
-                    hb.lv[k] = __builtin_bit_cast(
-                        float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, l), k));
-                hb.mine = first_visit;
-            }
-            asm volatile("" ::: "memory");      // (the window loads stay behind the marks)
         }
+        // the bound of tile a in lane 0, of tile c in lane 63, of tile m in the lanes between
+        // (all three read out by the whole wave, then selected)
+        auto bound = [&](int a, int m, int c) {
+            const int bits = __builtin_bit_cast(int, l);
+            const float fa = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bits, a));
+            const float fm = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bits, m));
+            const float fc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bits, c));
+            return threadIdx.x == 0 ? fa : (threadIdx.x == WN - 1 ? fc : fm);
+        };
         if (!HAS_EPS) {
             const int fb = __builtin_amdgcn_readfirstlane(fb_raw);
             if (fb != FLAT_NONE) {
                 flat_level = __builtin_bit_cast(float, fb);
-                const float zm = __builtin_bit_cast(
-                    float, __builtin_amdgcn_readfirstlane(ld_relaxed(zmax + t)));
-                const flat_result f = flat_visit(wg, H, W, ty, tx, flat_level, zm,
-                                                 use_hb ? &hb : nullptr);
+                const float zm = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(zm_raw));
+                // halo rows: lane = column; halo columns: lane = row
+                const flat_result f = flat_visit(wg, H, W, ty, tx, flat_level, zm, bound(0, 1, 2),
+                                                 bound(6, 7, 8), bound(0, 3, 6), bound(2, 5, 8));
                 if (f.handled) {
                     if (f.changed) {
                         if (threadIdx.x == 0)
@@ -1356,8 +1379,10 @@ __global__ __launch_bounds__(NT, 2) void fill_async_kernel(const float *__restri
                 }
             }
         }
-        const visit_result v = tile_visit<HAS_EPS, true>(zg, wg, H, W, eps, ty, tx, T, nullptr,
-                                                         flat_level, use_hb ? &hb : nullptr);
+        const visit_result v = tile_visit<HAS_EPS, true>(
+            zg, wg, H, W, eps, ty, tx, T, nullptr, flat_level,
+            HAS_EPS ? -HDEM_INF : bound(0, 1, 2), HAS_EPS ? -HDEM_INF : bound(3, 4, 5),
+            HAS_EPS ? -HDEM_INF : bound(6, 7, 8), first_visit);
         if (first_visit) {
             // the tile's cells are in memory before its mark, the mark before its state word
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
