@@ -25,6 +25,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      WeightedFlowAccumulation,
                                      UpstreamExtreme, BreachDepressions,
                                      FlowDistance, HeightAboveDrainage, UpstreamFlowLength,
+                                     FlowPathSum, FlowPathExtreme,
                                      StreamOrder, DemToStreamOrder, StreamNetwork,
                                      DemToStreamNetwork, ZonalStatistics, DemToBasins,
                                      TerrainAttributes, Slope, Aspect, WetnessIndex,

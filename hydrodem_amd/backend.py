@@ -206,6 +206,17 @@ class _UpExtremeStats(_SizedStats):
                 ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class _FlowPathStats(_SizedStats):
+    """``hdem_flowpath_stats`` (the binding is hydrodem_amd/flowpath.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("forest_rounds", ctypes.c_int32),
+                ("stops", ctypes.c_int64), ("unreached", ctypes.c_int64),
+                ("exits", ctypes.c_int64), ("nan_weights", ctypes.c_int64),
+                ("absent", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_tile", ctypes.c_float), ("ms_forest", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 class _BreachStats(_SizedStats):
     """``hdem_breach_stats``: the extreme's fields, then the pits and the cells lowered."""
     _fields_ = _UpExtremeStats._fields_ + [("pits", ctypes.c_int64),
@@ -352,6 +363,10 @@ SIGNATURES = {
                               _c.POINTER(_UpExtremeStats)],
     "hdem_breach_f32": [_vp, _vp, _vp, _i, _i, _vp, _vp, _c.POINTER(_BreachStats)],
     "hdem_breach_f32_dev": [_vp, _vp, _vp, _i, _i, _vp, _vp, _c.POINTER(_BreachStats)],
+    "hdem_flowpath_u8": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _i, _vp, _i, _i, _i, _vp,
+                         _vp, _vp, _vp, _vp, _vp, _i, _c.POINTER(_FlowPathStats)],
+    "hdem_flowpath_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _i, _vp, _i, _i, _i, _vp,
+                             _vp, _vp, _vp, _vp, _vp, _i, _c.POINTER(_FlowPathStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

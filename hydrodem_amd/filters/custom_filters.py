@@ -26,9 +26,9 @@ unchanged when ``filters`` resolves here.
 New operators (the reference has neither): ``SinkFill``,
 ``D8FlowDirection``, ``ResolveFlats``, ``FlowAccumulation``, ``WeightedFlowAccumulation``,
 ``UpstreamExtreme``, ``BreachDepressions``, ``Watersheds``, ``FlowDistance``,
-``HeightAboveDrainage``, ``UpstreamFlowLength``, ``StreamOrder``, ``StreamNetwork`` and the
-chains ``DemToHAND``, ``DemToStreamOrder`` and ``DemToStreamNetwork``, shaped like every other
-``Filter``.
+``FlowPathSum``, ``FlowPathExtreme``, ``HeightAboveDrainage``, ``UpstreamFlowLength``,
+``StreamOrder``, ``StreamNetwork`` and the chains ``DemToHAND``, ``DemToStreamOrder`` and
+``DemToStreamNetwork``, shaped like every other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -67,6 +67,7 @@ from .. import terrain as _terrain
 from .. import proximity as _proximity
 from .. import flowsum as _flowsum
 from .. import upextreme as _upextreme
+from .. import flowpath as _flowpath
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -764,6 +765,187 @@ class HeightAboveDrainage(_FlowTrace):  # pylint: disable=too-few-public-methods
 
     def apply_device(self, raster):
         return self._keep(self._trace_device(raster, self._want()))
+
+
+class _FlowPath(Filter):  # pylint: disable=too-few-public-methods
+    """What ``FlowPathSum`` and ``FlowPathExtreme`` share: the operands of one
+    ``hdem_flowpath_u8`` call, with the streams and the threshold handled as ``_FlowTrace``
+    handles them, checked as far as they can be before the codes are known, and the call on
+    host arrays or device rasters.  ``stop`` is what ``keep_partial_results`` leaves."""
+
+    auto_device = True      # device form == host form for a uint8 code raster
+    VALUE_TYPES = ()
+
+    def _set_operands(self, mode, values, streams, threshold, output, keep_partial_results):
+        self.mode = mode
+        self._values = _Given(values, "weights" if mode == "sum" else "values",
+                              self.VALUE_TYPES).value
+        self.streams = _Given(streams, "streams", (np.bool_, np.uint8, np.uint32)).value
+        self.threshold, self.output = threshold, output
+        self.keep_partial_results = keep_partial_results
+        self.stop = None
+        self.stats = {}
+
+    def _table(self, height):
+        """The step-length table for codes of ``height`` rows (``None``: not per length)."""
+        raise NotImplementedError
+
+    def _call_args(self, height, values, streams):
+        per, frac_bits = getattr(self, "per", "step"), getattr(self, "frac_bits", 0)
+        return dict(values=values, mode=self.mode, streams=streams, threshold=self.threshold,
+                    per=per, step_len=self._table(height), frac_bits=frac_bits, want=self._want())
+
+    def _want(self):
+        return ("stop", self.output) if self.keep_partial_results else (self.output,)
+
+    def _check(self, codes):
+        height = codes.shape[0] if len(codes.shape) == 2 else 1
+        a = self._call_args(height, self._values, self.streams)
+        _flowpath.flowpath_args(codes, a["streams"], a["threshold"], a["mode"], a["values"],
+                                a["per"], a["step_len"], a["frac_bits"], a["want"])
+
+    def _keep(self, outs):
+        self.stop = outs.get("stop")
+        return outs[self.output]
+
+    def apply(self, image_to_filter):
+        super().apply(image_to_filter)
+        self._check(image_to_filter)
+        outs, self.stats = _flowpath.flowpath(
+            image_to_filter, **self._call_args(image_to_filter.shape[0],
+                                               _Given(self._values).host(),
+                                               _Given(self.streams).host()))
+        return self._keep(outs)
+
+    def apply_device(self, raster):
+        self._check(raster)
+        with _Given(self._values).device(raster.ctx) as values, \
+                _Given(self.streams).device(raster.ctx) as streams:
+            outs, self.stats = _flowpath.flowpath_dev(
+                raster, **self._call_args(raster.shape[0], values, streams))
+        return self._keep(outs)
+
+
+class FlowPathSum(_FlowPath):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """Downstream D8 path sum (new operator; ArcGIS *Flow Length (downstream)* with a weight
+    raster, Whitebox ``DownslopeFlowpathLength --weights``, travel time, the downslope component
+    of the sediment connectivity index).  Input: a uint8 H x W raster of ESRI D8 codes exactly
+    as ``FlowDistance`` takes them, and ``streams`` / ``threshold`` mean what they mean there: a
+    path runs from the cell to its first *stop*, a terminal cell or a stream cell.  Returns the
+    sum, over the cells of the path but the stop, of the cost of the step that leaves the cell;
+    a stop reads 0.
+
+    Every cell's cost is quantised to an integer ``q`` in 0 ... 2^31 - 1 and summed in int64:
+    exact, identical from run to run.  ``per="step"``: ``q`` is the weight itself for uint8 and
+    uint32 ``weights``, which take ``frac_bits=0``, and ``rint(float64(w) * 2^frac_bits)`` for
+    float32.  ``per="length"``: ``q = rint((float64(w) * len) * 2^frac_bits)``, ``len`` the
+    length of the leaving step from ``step_lengths``, an array of ``(rows, 3)`` float64
+    ``(east-west, north-south, diagonal)`` (``hydrodem_amd.flowpath.step_lengths`` for square
+    cells, ``geographic_step_lengths`` for a latitude / longitude grid); without one the table
+    of square cells of ``cellsize`` is used.  ``weights=None`` per length counts ``w = 1``: the
+    flow length on an anisotropic grid.  ``weights``: an H x W NumPy array or ``DeviceRaster``
+    of uint8, uint32 or float32 (float64 is refused, not narrowed).
+
+    ``output`` fixes what ``apply`` returns: ``"value"`` float32
+    ``float32(float64(S) * 2^-frac_bits)``, NaN where the path ends in a terminal cell that is
+    no stream cell, or ``"sum"`` int64 ``S`` (for an unreached cell the sum to that terminal
+    cell).  With ``keep_partial_results=True`` the call also leaves ``stop`` (uint32: 1 + flat
+    index of the stop, 0 where unreached), a host array after ``apply`` and a device raster
+    after ``apply_device``.
+
+    A NaN weight costs 0 (``stats["nan_weights"]`` counts them).  ``ValueError`` for operands of
+    another type, dtype or shape, a bad ``per``, ``frac_bits``, ``cellsize`` or table (all
+    before the device is touched), for a negative or infinite weight, a quantised cost above
+    2^31 - 1, a byte that is not a D8 code, codes that form a cycle and more than 2^32 - 1
+    cells.
+
+    Attributes
+    ----------
+    stats : dict
+        nan_weights, stops, unreached, exits, forest_rounds, tile_h / tile_w of the last call;
+        phase times when profiling is on.
+    stop : numpy.ndarray, DeviceRaster or None
+    """
+
+    VALUE_TYPES = (np.uint8, np.uint32, np.float32)
+    OUTPUTS = {"value": np.dtype(np.float32), "sum": np.dtype(np.int64)}
+
+    def __init__(self, weights=None, *, per="step", step_lengths=None, cellsize=1.0,
+                 frac_bits=16, streams=None, threshold=None, output="value",
+                 keep_partial_results=False):
+        if not isinstance(output, str) or output not in self.OUTPUTS:
+            raise ValueError(f"output is one of {list(self.OUTPUTS)}, got {output!r}")
+        self._set_operands("sum", weights, streams, threshold, output, keep_partial_results)
+        self.weights = self._values
+        self.per, self.frac_bits = per, frac_bits
+        self.step_lengths = step_lengths
+        self.cellsize = backend._cellsize(cellsize)  # pylint: disable=protected-access
+        self.dtype = self.OUTPUTS[output]
+        if step_lengths is not None and per == "length":
+            self.step_lengths = _flowpath.table_of(step_lengths)
+        # everything but the shapes, on 1 x 1 stand-ins
+        _flowpath.flowpath_args(
+            np.zeros((1, 1), np.uint8), _Given(self.streams).stand_in(), threshold, "sum",
+            _Given(self._values).stand_in(), per,
+            _flowpath.step_lengths(1, self.cellsize) if per == "length" else step_lengths,
+            frac_bits, self._want())
+
+    def _table(self, height):
+        if self.per != "length" or self.step_lengths is not None:
+            return self.step_lengths
+        return _flowpath.step_lengths(height, self.cellsize)
+
+
+class FlowPathExtreme(_FlowPath):  # pylint: disable=too-few-public-methods
+    """Downstream D8 path minimum or maximum (new operator; the twin of ``UpstreamExtreme``
+    along a cell's own path).  Input: a uint8 H x W raster of ESRI D8 codes exactly as
+    ``FlowDistance`` takes them, with its ``streams`` / ``threshold``.  ``values``: an H x W
+    NumPy array or ``DeviceRaster`` of float32 or uint32.  For every cell, over the cells of
+    its D8 path down to its first stop, the cell and the stop included, the least
+    (``mode="min"``) or greatest (``mode="max"``) present value.  A float32 NaN is absent
+    (``stats["absent"]`` counts them); floats are ordered
+    ``-inf < ... < -0.0 < +0.0 < ... < +inf``.
+
+    ``output`` fixes what ``apply`` returns: ``"extreme"``, of the values' dtype, the bits of
+    the cell that holds the extreme (the quiet NaN where nothing on the path is present), or
+    ``"where"``, uint32, that cell's flat index (``0xFFFFFFFF`` where nothing is present).
+    Among cells that hold the same value the smallest flat index is the holder, in both modes.
+    Where the path ends in a terminal cell that is no stream cell the path to that cell is
+    reduced; ``keep_partial_results=True`` leaves ``stop`` (uint32, 0 there) to tell.
+
+    ``ValueError`` for operands of another type, dtype or shape, an unknown ``mode`` or
+    ``output`` (all before the device is touched), a byte that is not a D8 code, codes that form
+    a cycle and more than 2^32 - 1 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        absent, stops, unreached, exits, forest_rounds, tile_h / tile_w of the last call; phase
+        times when profiling is on.
+    stop : numpy.ndarray, DeviceRaster or None
+    """
+
+    VALUE_TYPES = (np.float32, np.uint32)
+    OUTPUTS = ("extreme", "where")
+
+    def __init__(self, values, mode="min", *, streams=None, threshold=None, output="extreme",
+                 keep_partial_results=False):
+        if values is None:
+            raise ValueError("FlowPathExtreme needs the values it reduces")
+        if not isinstance(mode, str) or mode not in ("min", "max"):
+            raise ValueError(f"mode is one of ['min', 'max'], got {mode!r}")
+        if not isinstance(output, str) or output not in self.OUTPUTS:
+            raise ValueError(f"output is one of {list(self.OUTPUTS)}, got {output!r}")
+        self._set_operands(mode, values, streams, threshold, output, keep_partial_results)
+        self.values = self._values
+        self.dtype = np.dtype(np.uint32) if output == "where" else np.dtype(self.values.dtype)
+        # everything but the shapes, on 1 x 1 stand-ins
+        _flowpath.flowpath_args(np.zeros((1, 1), np.uint8), _Given(self.streams).stand_in(),
+                                threshold, mode, _Given(self._values).stand_in(), "step", None, 0,
+                                self._want())
+
+    def _table(self, height):
+        return None
 
 
 class UpstreamFlowLength(Filter):  # pylint: disable=too-few-public-methods

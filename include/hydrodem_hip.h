@@ -1247,6 +1247,110 @@ int hdem_breach_f32_dev(hdem_ctx *ctx, const float *dem, const uint8_t *d8, int 
                         float *carved, uint32_t *source,
                         hdem_breach_stats *stats);    /* device pointers */
 
+/* ---- A19  FlowPathSum.apply / FlowPathExtreme.apply  (new operators: downstream D8 path
+ *           sums and extremes) ----
+ * d8, streams, stream_kind and threshold exactly as hdem_flowtrace_u8 (A7) takes them, and a
+ * stop, a dry terminal cell and an unreached cell are what they are there.  Write the D8 path
+ * of c as p_0 = c -> p_1 -> ... -> p_k = s(c), its first stop (for an unreached cell: the dry
+ * terminal cell it ends in).
+ * mode HDEM_FLOWPATH_SUM:  S(c) = sum over i < k of q(p_i), the quantised cost of the step that
+ *   leaves each cell of the path; a stop has S = 0.  values are the weights, H x W of
+ *   value_type; q is an integer made once per cell:
+ *     per HDEM_FLOWPATH_PER_STEP    HDEM_FLOWPATH_U8, _U32: q = w, frac_bits must be 0
+ *                                   HDEM_FLOWPATH_F32: q = (int64)rint((double)w * 2^frac_bits),
+ *                                   A16's rule.  values must not be NULL, step_len must be.
+ *     per HDEM_FLOWPATH_PER_LENGTH  q = (int64)rint(((double)w * len) * 2^frac_bits): one
+ *                                   rounding in the product, an exact scaling, one rint to
+ *                                   nearest even.  len is the length of the step leaving the
+ *                                   cell, read from step_len, 3 * H doubles: for the leaving
+ *                                   cell's row y, step_len[3 * y + 0 ... 2] = {east-west,
+ *                                   north-south, diagonal}.  Integer weights take any
+ *                                   frac_bits.  values may be NULL with HDEM_FLOWPATH_NONE:
+ *                                   w = 1, the flow length on an anisotropic grid.  A cell
+ *                                   without a direction (code 0, an invalid byte) has q = 0.
+ *   frac_bits is 0 ... 30.  -0.0 counts as 0.  A NaN weight costs 0 and is counted in
+ *   stats->nan_weights.  A negative or infinite weight and any q > 2^31 - 1, in any cell of the
+ *   raster (stops too, so that the refusal does not depend on the streams), is refused:
+ *   HDEM_ERR_BAD_ARG with their count, after the call's one synchronisation.  With q < 2^31
+ *   and H * W < 2^32 every sum is below 2^63.
+ *   step_len is a host pointer in both forms; the call copies it.  An entry that is not finite
+ *   and positive is HDEM_ERR_BAD_ARG, with their count, before any launch.
+ * mode HDEM_FLOWPATH_MIN, HDEM_FLOWPATH_MAX:  the least / greatest present value over
+ *   {p_0, ..., p_k}, c and the stop included.  values is H x W of HDEM_FLOWPATH_F32 or _U32 and
+ *   A17's contract holds: a float32 NaN is absent and counted in stats->absent, floats are
+ *   ordered by their bits as a sign-magnitude number (-0.0 below +0.0), among equal bits the
+ *   smallest flat index is the holder in both modes.  per and frac_bits must be 0, step_len
+ *   NULL.
+ * Outputs, all H x W, each may be NULL (not wanted), at least one must not be, and an output
+ * of the other mode must be NULL:
+ *   stop     uint32   1 + flat index of s(c); 0 for an unreached cell, as A7 writes it
+ *   sum      int64    SUM: S(c); for an unreached cell the sum to the dry terminal cell
+ *   value    float32  SUM: (float)((double)S * 2^-frac_bits), two roundings to nearest even;
+ *                     NaN where unreached
+ *   extreme  of the values' type   MIN / MAX: the holder's own bits; for float32 the quiet NaN
+ *                     0x7FC00000 where nothing on the path is present.  For an unreached cell
+ *                     the path to the dry terminal cell is reduced: stop = 0 says so.
+ *   where    uint32   MIN / MAX: the holder's flat index, 0xFFFFFFFF where nothing is present
+ * Integer adds and min / max on a total order only: identical from run to run and between the
+ * host and device forms.
+ * HDEM_ERR_BAD_ARG before any allocation or launch: H * W > 2^32 - 1; an unknown mode, per,
+ * value_type, stream_kind or non-zero flags; an operand that the mode misses or does not take
+ * (as above); frac_bits out of range; no output; an output that overlaps an input or another
+ * output; a bad step_len entry.  After the launches, in bounded time: an invalid byte, weights
+ * out of range, codes that form a cycle ("N cells never resolve"; a loop that holds a stream
+ * cell ends there and is legal).  On error the contents of the outputs are unspecified; the
+ * context stays usable.
+ * Three phases as A7: A per 64 x 64 tile, B the forest of perimeter slots, C one streaming
+ * launch that writes every wanted output.
+ * Workspace: 8 B per cell, 32 B per tile-perimeter slot (2.0 B per cell) and 24 B per row for
+ * the table, about 10.0 B per cell, from the context's arena.  The _dev form synchronises the
+ * context's stream once to read its counters.  stats may be NULL; otherwise the caller sets
+ * stats->struct_size = sizeof(hdem_flowpath_stats) first (72 bytes in this version; a shorter
+ * struct is filled as far as it goes).  The three phase times are filled only while profiling
+ * is on (hdem_profile_enable); the call has no kernel id. */
+typedef enum hdem_flowpath_mode {
+    HDEM_FLOWPATH_SUM = 0,
+    HDEM_FLOWPATH_MIN = 1,
+    HDEM_FLOWPATH_MAX = 2
+} hdem_flowpath_mode;
+typedef enum hdem_flowpath_per {
+    HDEM_FLOWPATH_PER_STEP = 0,
+    HDEM_FLOWPATH_PER_LENGTH = 1
+} hdem_flowpath_per;
+typedef enum hdem_flowpath_value_type {   /* numbered as the flowsum weight types are */
+    HDEM_FLOWPATH_NONE = 0,
+    HDEM_FLOWPATH_F32 = 1,
+    HDEM_FLOWPATH_U32 = 2,
+    HDEM_FLOWPATH_U8 = 3
+} hdem_flowpath_value_type;
+typedef struct hdem_flowpath_stats {
+    uint32_t struct_size;   /* in: sizeof(hdem_flowpath_stats), set by the caller           */
+    int32_t forest_rounds;  /* pointer-jumping launches of phase B that had work to do      */
+    int64_t stops;          /* stop cells: stream cells and terminal cells                  */
+    int64_t unreached;      /* cells whose path ends in a terminal cell that is no stream   */
+    int64_t exits;          /* cells that are no stop and drain into another tile           */
+    int64_t nan_weights;    /* SUM: NaN weights, each cost 0                                */
+    int64_t absent;         /* MIN / MAX: NaN values, they took no part                     */
+    int32_t tile_h, tile_w;
+    float ms_tile;          /* phase A: costs made, in-tile pointer doubling (HIP events;
+                               profiling)                                                   */
+    float ms_forest;        /* phase B: the forest of perimeter slots                       */
+    float ms_final;         /* phase C: outputs written                                     */
+    int32_t reserved;       /* 0                                                            */
+} hdem_flowpath_stats;      /* sizeof == 72 */
+int hdem_flowpath_u8(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *streams,
+                     int stream_kind, uint32_t threshold, int mode, const void *values,
+                     int value_type, int per, int frac_bits, const double *step_len,
+                     uint32_t *stop, int64_t *sum, float *value, void *extreme,
+                     uint32_t *where, int flags,
+                     hdem_flowpath_stats *stats);      /* host pointers, synchronous */
+int hdem_flowpath_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const void *streams,
+                         int stream_kind, uint32_t threshold, int mode, const void *values,
+                         int value_type, int per, int frac_bits, const double *step_len,
+                         uint32_t *stop, int64_t *sum, float *value, void *extreme,
+                         uint32_t *where, int flags,
+                         hdem_flowpath_stats *stats);  /* device pointers; step_len host */
+
 #ifdef __cplusplus
 }
 #endif
