@@ -30,6 +30,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      DemToStreamNetwork, ZonalStatistics, DemToBasins,
                                      TerrainAttributes, Slope, Aspect, WetnessIndex,
                                      DemToWetness,
+                                     DInfFlowDirection, DInfFlowAccumulation, DemToDInfArea,
                                      EuclideanDistance, EuclideanAllocation, BurnStreams,
                                      ResolveFlats,
                                      Depressions, DepressionInventory,

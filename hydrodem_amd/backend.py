@@ -223,6 +223,23 @@ class _BreachStats(_SizedStats):
                                            ("lowered", ctypes.c_int64)]
 
 
+class _DInfStats(_SizedStats):
+    """``hdem_dinf_stats`` (the binding is hydrodem_amd/dinf.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("ms_total", ctypes.c_float),
+                ("no_flow", ctypes.c_int64), ("fallback_cells", ctypes.c_int64)]
+
+
+class _DInfAccStats(_SizedStats):
+    """``hdem_dinfacc_stats`` (the binding is hydrodem_amd/dinf.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("rounds", ctypes.c_int32),
+                ("tile_visits", ctypes.c_int64), ("split_cells", ctypes.c_int64),
+                ("terminal_cells", ctypes.c_int64), ("invalid", ctypes.c_int64),
+                ("outside", ctypes.c_int64), ("unresolved", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_classify", ctypes.c_float), ("ms_relax", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
 # columns of the depression table, in the order of the C ABI's pointers
 DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
@@ -367,6 +384,12 @@ SIGNATURES = {
                          _vp, _vp, _vp, _vp, _vp, _i, _c.POINTER(_FlowPathStats)],
     "hdem_flowpath_u8_dev": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _i, _vp, _i, _i, _i, _vp,
                              _vp, _vp, _vp, _vp, _vp, _i, _c.POINTER(_FlowPathStats)],
+    "hdem_dinf_f32": [_vp, _vp, _i, _i, _vp, _c.c_double, _c.c_double, _vp, _vp, _vp, _i,
+                      _c.POINTER(_DInfStats)],
+    "hdem_dinf_f32_dev": [_vp, _vp, _i, _i, _vp, _c.c_double, _c.c_double, _vp, _vp, _vp, _i,
+                          _c.POINTER(_DInfStats)],
+    "hdem_dinfacc_u32": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _c.POINTER(_DInfAccStats)],
+    "hdem_dinfacc_u32_dev": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _c.POINTER(_DInfAccStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

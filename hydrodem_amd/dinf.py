@@ -1,0 +1,214 @@
+"""
+D-infinity flow direction and accumulation (``hdem_dinf_f32`` / ``hdem_dinfacc_u32`` and their
+``_dev`` twins): the binding, written once for host arrays and device rasters with the two
+sides of :mod:`hydrodem_amd.backend`, and the host helpers for the D-infinity word.
+
+The word, one uint32 per cell: ``q`` in bits 0-15 (0 ... 32768, the share of the diagonal
+receiver in units of 2^-15), the facet in bits 16-19 (0: no outflow; 1 ... 8 as in Tarboton 1997,
+``FACETS``).  ``include/hydrodem_hip.h`` (A20, A21) has the contract.
+"""
+# pylint: disable=protected-access,too-many-arguments
+
+import contextlib
+import ctypes
+import math
+
+import numpy as np
+
+from . import backend
+
+Q_ONE = 32768               # q of "everything to the diagonal receiver"
+# facet -> ((dy, dx) of the cardinal receiver e1, of the diagonal receiver e2, ac, af); north is
+# row - 1
+FACETS = {1: ((0, 1), (-1, 1), 0, 1), 2: ((-1, 0), (-1, 1), 1, -1),
+          3: ((-1, 0), (-1, -1), 1, 1), 4: ((0, -1), (-1, -1), 2, -1),
+          5: ((0, -1), (1, -1), 2, 1), 6: ((1, 0), (1, -1), 3, -1),
+          7: ((1, 0), (1, 1), 3, 1), 8: ((0, 1), (1, 1), 4, -1)}
+# ESRI D8 code -> (facet, q) of its canonical word, and its multiple of pi / 4
+D8_WORDS = {1: (1, 0), 64: (2, 0), 16: (4, 0), 4: (6, 0),
+            128: (1, Q_ONE), 32: (3, Q_ONE), 8: (5, Q_ONE), 2: (7, Q_ONE)}
+D8_EIGHTHS = {1: 0, 128: 1, 64: 2, 32: 3, 16: 4, 8: 5, 4: 6, 2: 7}
+OUTPUTS = (("sum", np.int64), ("value", np.float32))    # in the order of the C ABI's pointers
+EXTRAS = ("angle", "slope")                             # float32, optional, of the direction
+
+
+# ---------------------------------------------------------------------------
+# the word on the host
+# ---------------------------------------------------------------------------
+def pack(facet, q):
+    """The uint32 words of ``facet`` (0 ... 8) and ``q`` (0 ... 32768; 0 where the facet is 0)."""
+    facet, q = np.asarray(facet), np.asarray(q)
+    if np.any((facet < 0) | (facet > 8)):
+        raise ValueError("a facet is 0 ... 8")
+    if np.any((q < 0) | (q > Q_ONE)):
+        raise ValueError(f"q is 0 ... {Q_ONE}")
+    if np.any((facet == 0) & (q != 0)):
+        raise ValueError("facet 0 goes with q 0")
+    return (facet.astype(np.uint32) << np.uint32(16)) | q.astype(np.uint32)
+
+
+def unpack(words):
+    """``(facet, q)`` of uint32 words: a uint8 and a uint32 array."""
+    words = np.asarray(words)
+    if words.dtype != np.uint32:
+        raise ValueError(f"D-infinity words are uint32, got {words.dtype}")
+    return ((words >> np.uint32(16)) & np.uint32(15)).astype(np.uint8), words & np.uint32(0xFFFF)
+
+
+def words_from_d8(codes):
+    """The canonical words of uint8 ESRI D8 codes: one receiver each, 0 for code 0."""
+    codes = np.asarray(codes)
+    if codes.dtype != np.uint8:
+        raise ValueError(f"D8 codes are uint8, got {codes.dtype}")
+    table = np.full(256, 0xFFFFFFFF, np.uint32)
+    table[0] = 0
+    for code, (facet, q) in D8_WORDS.items():
+        table[code] = (facet << 16) | q
+    words = table[codes]
+    bad = int((words == 0xFFFFFFFF).sum())
+    if bad:
+        raise ValueError(f"invalid D8 code in {bad} cells: a code is 0 or one of 1, 2, 4, ..., 128")
+    return words
+
+
+def angle_of(words, dx=1.0, dy=1.0):
+    """The flow angle the words stand for, float64 radians counter-clockwise from east, -1 where
+    the facet is 0: ``af * r + ac * pi / 2`` with ``r = q / 32768 * atan2(d2, d1)``.  (The angle
+    output of the direction operator is the unquantised one.)"""
+    facet, q = unpack(words)
+    dx, dy = backend._cellsize(dx), backend._cellsize(dy)
+    out = np.full(facet.shape, -1.0)
+    for k, ((ey, _), _, ac, af) in FACETS.items():
+        theta = math.atan2(dy, dx) if ey == 0 else math.atan2(dx, dy)
+        a = af * (q / float(Q_ONE) * theta) + ac * (math.pi / 2)
+        out = np.where(facet == k, np.where(a >= 2 * math.pi, 0.0, a), out)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# argument checks (no device)
+# ---------------------------------------------------------------------------
+def cellsizes(cellsize):
+    """``cellsize`` as ``(dx, dy)``: one number for square cells, or a ``(dx, dy)`` pair."""
+    if isinstance(cellsize, (tuple, list)):
+        if len(cellsize) != 2:
+            raise ValueError(f"cellsize is a number or a (dx, dy) pair, got {cellsize!r}")
+        return backend._cellsize(cellsize[0]), backend._cellsize(cellsize[1])
+    size = backend._cellsize(cellsize)
+    return size, size
+
+
+def dinf_args(dem, cellsize=1.0, fallback=None, want=()):
+    """The checks of the direction that need no device: ``dem`` and ``fallback`` are anything
+    with ``dtype`` and ``shape``.  Returns ``(dx, dy)`` and ``want`` in the ABI's order."""
+    shape = backend._check(dem, np.float32, "D-infinity flow direction takes", "a float32 DEM",
+                           flat="D-infinity flow direction takes")
+    dx, dy = cellsizes(cellsize)
+    if fallback is not None:
+        backend._check(fallback, np.uint8, "the fallback is", "uint8 D8 codes",
+                       like=("the dem", shape))
+    if isinstance(want, str):
+        want = (want,)
+    unknown = [w for w in want if w not in EXTRAS]
+    if unknown:
+        raise ValueError(f"unknown D-infinity outputs {unknown}: choose among {list(EXTRAS)}")
+    return (dx, dy), tuple(n for n in EXTRAS if n in want)
+
+
+def check_frac_bits(frac_bits):
+    if isinstance(frac_bits, bool) or not isinstance(frac_bits, (int, np.integer)) or \
+            not 0 <= int(frac_bits) <= 16:
+        raise ValueError(f"frac_bits is an integer in 0 ... 16, got {frac_bits!r}")
+    return int(frac_bits)
+
+
+def dinfacc_args(words, frac_bits=16, want=("value",)):
+    """The checks of the accumulation that need no device.  Returns ``frac_bits`` and ``want``
+    as a tuple in the ABI's order."""
+    if words is None:
+        raise ValueError("D-infinity flow accumulation needs the words it routes along")
+    backend._check(words, np.uint32, "D-infinity flow accumulation takes",
+                   "uint32 D-infinity words", flat="D-infinity flow accumulation takes")
+    frac_bits = check_frac_bits(frac_bits)
+    if isinstance(want, str):
+        want = (want,)
+    names = [n for n, _ in OUTPUTS]
+    unknown = [w for w in want if w not in names]
+    if unknown:
+        raise ValueError(f"unknown D-infinity accumulation outputs {unknown}: choose among "
+                         f"{names}")
+    want = tuple(n for n in names if n in want)
+    if not want:
+        raise ValueError(f"no output wanted: choose among {names}")
+    return frac_bits, want
+
+
+# ---------------------------------------------------------------------------
+# the calls
+# ---------------------------------------------------------------------------
+def _dinf(side, dem, cellsize, fallback, want, out):
+    if dem is None:
+        raise ValueError("D-infinity flow direction needs the dem it is derived from")
+    dem = side.take("dem", dem, required=True)
+    fallback = side.take("fallback", fallback)
+    (dx, dy), want = dinf_args(dem, cellsize, fallback, want)
+    if out is not None:
+        backend._check(out, np.uint32, "out is", like=("the dem", tuple(dem.shape)))
+    c = side.context(dem)
+    st = backend._DInfStats()
+    with contextlib.ExitStack() as stack:
+        words = side.result(stack, out, dem.shape, np.uint32, c)
+        extras = {name: side.result(stack, None, dem.shape, np.float32, c) for name in want}
+        side.call(c, "hdem_dinf_f32", side.address(dem), *dem.shape, side.address(fallback),
+                  dx, dy, side.address(words),
+                  *[side.address(extras.get(name)) for name in EXTRAS], 0, ctypes.byref(st))
+    return words, extras, st.as_dict()
+
+
+def dinf_dev(dem, cellsize=1.0, fallback=None, want=(), out=None):
+    """D-infinity flow direction of a float32 device raster (``hdem_dinf_f32_dev``): the uint32
+    words, ``{name: DeviceRaster}`` for the float32 extras in ``want`` (``angle``, ``slope``)
+    and the stats dict (``no_flow``, ``fallback_cells``, ``ms_total``).  ``cellsize``: a number
+    or ``(dx, dy)``.  ``fallback``: uint8 D8 codes for the cells no facet drains.  ``out``: a
+    uint32 raster to write the words into.  Synchronises (the call reads its counters)."""
+    return _dinf(backend._DEVICE, dem, cellsize, fallback, want, out)
+
+
+def dinf(dem, cellsize=1.0, fallback=None, want=()):
+    """D-infinity flow direction of host arrays (``hdem_dinf_f32``; see :func:`dinf_dev`)."""
+    return _dinf(backend._HOST, dem, cellsize, fallback, want, None)
+
+
+def _dinfacc(side, words, frac_bits, want, out):
+    words = side.take("words", words, required=True)
+    frac_bits, want = dinfacc_args(words, frac_bits, want)
+    out = dict(out or {})
+    for name, dtype in OUTPUTS:
+        if name in out:
+            if name not in want:
+                raise ValueError(f"out has {name}, which is not wanted")
+            backend._check(out[name], dtype, f"out[{name!r}] is",
+                           like=("the words", tuple(words.shape)))
+    c = side.context(words)
+    st = backend._DInfAccStats()
+    with contextlib.ExitStack() as stack:
+        outs = {name: side.result(stack, out.get(name), words.shape, dtype, c)
+                for name, dtype in OUTPUTS if name in want}
+        side.call(c, "hdem_dinfacc_u32", side.address(words), *words.shape, frac_bits,
+                  *[side.address(outs.get(name)) for name, _ in OUTPUTS], 0, ctypes.byref(st))
+    return outs, st.as_dict()
+
+
+def dinfacc_dev(words, frac_bits=16, want=("value",), out=None):
+    """D-infinity flow accumulation of a uint32 word raster (``hdem_dinfacc_u32_dev``):
+    ``A[c] = 2^frac_bits`` plus the shares its donors send it, in integers.  ``want``: ``sum``
+    (int64 ``A``) and / or ``value`` (float32 ``A * 2^-frac_bits``, in cells).  ``out``:
+    ``{name: DeviceRaster}`` to write into.  Returns ``{name: DeviceRaster}`` and the stats
+    dict.  Synchronises once per round."""
+    return _dinfacc(backend._DEVICE, words, frac_bits, want, out)
+
+
+def dinfacc(words, frac_bits=16, want=("value",)):
+    """D-infinity flow accumulation of host arrays (``hdem_dinfacc_u32``; see
+    :func:`dinfacc_dev`): ``{name: ndarray}`` and the stats dict."""
+    return _dinfacc(backend._HOST, words, frac_bits, want, None)

@@ -27,8 +27,9 @@ New operators (the reference has neither): ``SinkFill``,
 ``D8FlowDirection``, ``ResolveFlats``, ``FlowAccumulation``, ``WeightedFlowAccumulation``,
 ``UpstreamExtreme``, ``BreachDepressions``, ``Watersheds``, ``FlowDistance``,
 ``FlowPathSum``, ``FlowPathExtreme``, ``HeightAboveDrainage``, ``UpstreamFlowLength``,
-``StreamOrder``, ``StreamNetwork`` and the chains ``DemToHAND``, ``DemToStreamOrder`` and
-``DemToStreamNetwork``, shaped like every other ``Filter``.
+``StreamOrder``, ``StreamNetwork``, ``DInfFlowDirection``, ``DInfFlowAccumulation`` and the
+chains ``DemToHAND``, ``DemToStreamOrder``, ``DemToStreamNetwork`` and ``DemToDInfArea``, shaped
+like every other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -68,6 +69,7 @@ from .. import proximity as _proximity
 from .. import flowsum as _flowsum
 from .. import upextreme as _upextreme
 from .. import flowpath as _flowpath
+from .. import dinf as _dinf
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -1984,6 +1986,159 @@ class DemToWetness(ComposedFilter):  # pylint: disable=too-few-public-methods,to
                 self.tangent = outs["tangent"]
                 stack.pop_all()                     # the caller's to free from here on
             return outs["twi"]
+
+
+class DInfFlowDirection(Filter):  # pylint: disable=too-few-public-methods
+    """Tarboton's D-infinity flow direction (new operator; TauDEM ``dinfflowdir``).  Input: a
+    float32 H x W DEM, NaN where there is no data.  Returns one uint32 word per cell
+    (``hydrodem_amd.dinf``): ``q`` in bits 0-15, the share of the outflow that goes to the
+    diagonal receiver in units of 2^-15, and the facet 0 ... 8 in bits 16-19.  The steepest of the
+    eight triangular facets wins, the first one on a tie; the slopes are float64 on the float32
+    elevations.  Cells of the raster ring, NaN cells and cells without a downward facet get 0:
+    no outflow.
+
+    ``cellsize``: a number or ``(dx, dy)``.  ``fallback``: uint8 ESRI D8 codes of the DEM's shape
+    (array or ``DeviceRaster``); a cell that would get 0 takes its code's direction, so that the
+    flats of an exact fill routed by ``ResolveFlats`` keep draining.  With
+    ``keep_partial_results=True`` the launch also writes ``angle`` (float32 radians
+    counter-clockwise from east, -1 without outflow) and ``slope`` (the winner's, 0 where none
+    won, NaN at NaN) and leaves them in the attributes of those names: host arrays after
+    ``apply``, device rasters (the caller's to free) after ``apply_device``.
+
+    ``ValueError`` for a dtype other than float32, a raster that is not 2-D, a ``cellsize`` that
+    is not finite and positive, a ``fallback`` of another type, dtype or shape (all before the
+    device is touched) and a fallback byte that is no D8 code.
+
+    Attributes
+    ----------
+    stats : dict
+        no_flow (cells with word 0), fallback_cells of the last call; ms_total when profiling.
+    """
+
+    auto_device = False     # words are uint32: no float32 chain goes on from them
+
+    def __init__(self, cellsize=1.0, fallback=None, keep_partial_results=False):
+        self.cellsize = cellsize
+        self.fallback = _Given(fallback, "fallback", (np.uint8,)).value
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.angle = self.slope = None
+        _dinf.dinf_args(np.zeros((1, 1), np.float32), cellsize, _Given(self.fallback).stand_in())
+
+    def _want(self):
+        return _dinf.EXTRAS if self.keep_partial_results else ()
+
+    def _keep(self, words, extras, stats):
+        self.stats = stats
+        self.angle, self.slope = extras.get("angle"), extras.get("slope")
+        return words
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _dinf.dinf_args(image_to_filter, self.cellsize, self.fallback)
+        return self._keep(*_dinf.dinf(image_to_filter, self.cellsize,
+                                      _Given(self.fallback).host(), self._want()))
+
+    def apply_device(self, raster):
+        _dinf.dinf_args(raster, self.cellsize, self.fallback)
+        with _Given(self.fallback).device(raster.ctx) as fallback:
+            return self._keep(*_dinf.dinf_dev(raster, self.cellsize, fallback, self._want()))
+
+
+class DInfFlowAccumulation(Filter):  # pylint: disable=too-few-public-methods
+    """D-infinity flow accumulation (new operator; TauDEM ``areadinf``).  Input: a uint32 H x W
+    raster of D-infinity words as ``DInfFlowDirection`` returns them.  With ``U = 2^frac_bits``,
+    ``A[c] = U + sum(share(d -> c))`` over the 8-neighbours ``d`` whose word names ``c``: a donor
+    sends ``(A[d] * q[d]) >> 15`` to its diagonal receiver and the rest to its cardinal one.
+    Integers throughout: every cell's outflow is conserved to the unit, ``A`` summed over the
+    cells without outflow is ``H * W * U`` exactly, and the result is identical from run to run.
+
+    ``output``: ``"value"`` float32 ``float32(float64(A) * 2^-frac_bits)``, the catchment area
+    in cells; ``"sum"`` int64 ``A``.  ``frac_bits`` is 0 ... 16.
+
+    ``ValueError`` for a dtype other than uint32, a raster that is not 2-D, ``frac_bits`` out of
+    range, an unknown ``output`` (all before the device is touched), an invalid word, a
+    receiver outside the raster, words that form a cycle (only user-supplied words can) and
+    more than 2^32 - 1 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        split_cells, terminal_cells, invalid, outside, unresolved, rounds and tile_visits
+        (these two depend on the schedule), tile_h / tile_w of the last call; phase times when
+        profiling is on.
+    """
+
+    auto_device = False     # the input is uint32 words, not a float32 raster
+    OUTPUTS = {name: np.dtype(dtype) for name, dtype in _dinf.OUTPUTS}
+
+    def __init__(self, frac_bits=16, output="value"):
+        if not isinstance(output, str) or output not in self.OUTPUTS:
+            raise ValueError(f"output is one of {list(self.OUTPUTS)}, got {output!r}")
+        self.frac_bits, self.output = _dinf.check_frac_bits(frac_bits), output
+        self.dtype = self.OUTPUTS[output]
+        self.stats = {}
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _dinf.dinfacc_args(image_to_filter, self.frac_bits, self.output)
+        outs, self.stats = _dinf.dinfacc(image_to_filter, self.frac_bits, self.output)
+        return outs[self.output]
+
+    def apply_device(self, raster):
+        _dinf.dinfacc_args(raster, self.frac_bits, self.output)
+        outs, self.stats = _dinf.dinfacc_dev(raster, self.frac_bits, self.output)
+        return outs[self.output]
+
+
+class DemToDInfArea(ComposedFilter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """A float32 DEM to its D-infinity catchment area in one device-resident chain:
+    ``SinkFill(epsilon)`` and ``D8FlowDirection`` (one call, as in ``HydroConditioning``),
+    ``DInfFlowDirection`` on the **filled** DEM with the chain's D8 codes as fallback, then
+    ``DInfFlowAccumulation``.  Nothing is downloaded in between.  ``flats`` as in ``DemToHAND``:
+    with ``"resolve"`` the fallback codes cross the flats, so an exact fill (``epsilon=0``)
+    drains; ``cellsize``, ``frac_bits`` and ``output`` as in the two operators.
+
+    ``stats`` maps ``SinkFill``, ``DInfFlowDirection`` and ``DInfFlowAccumulation`` (and
+    ``ResolveFlats``) to the stats of their stage.  With ``keep_partial_results=True`` the last
+    call leaves ``filled``, ``codes`` and ``words``: host arrays after ``apply``, device rasters
+    (the caller's to free) after ``apply_device``; otherwise they are ``None``."""
+
+    def __init__(self, *, epsilon=1e-3, flats="keep", cellsize=1.0, frac_bits=16,
+                 output="value", keep_partial_results=False):
+        super().__init__()
+        self.flats = _check_flats(flats)
+        self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection(),
+                        DInfFlowDirection(cellsize=cellsize),
+                        DInfFlowAccumulation(frac_bits=frac_bits, output=output)]
+        self.cellsize, self.frac_bits, self.output = cellsize, frac_bits, output
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.filled = self.codes = self.words = None
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("DemToDInfArea", image_to_filter, np.float32, "a float32 DEM")
+        return _through_device(self, image_to_filter,
+                               ("filled", "codes", "words") if self.keep_partial_results else ())
+
+    def apply_device(self, raster):
+        _check_raster("DemToDInfArea", raster, np.float32, "a float32 DEM")
+        fill, _, direct, accumulate = self.filters
+        self.filled = self.codes = self.words = None
+        with contextlib.ExitStack() as stack:
+            filled, codes, resolve_stats = _fill_d8(stack, raster, fill, self.flats)
+            words, _, direct.stats = _dinf.dinf_dev(filled, self.cellsize, codes)
+            stack.enter_context(words)
+            outs, accumulate.stats = _dinf.dinfacc_dev(words, self.frac_bits, self.output)
+            self.stats = {"SinkFill": fill.stats, "DInfFlowDirection": direct.stats,
+                          "DInfFlowAccumulation": accumulate.stats}
+            if resolve_stats is not None:
+                self.stats["ResolveFlats"] = resolve_stats
+            if self.keep_partial_results:
+                self.filled, self.codes, self.words = filled, codes, words
+                stack.pop_all()                     # the caller's to free from here on
+            return outs[self.output]
 
 
 class DemToStreamOrder(ComposedFilter):  # pylint: disable=too-few-public-methods

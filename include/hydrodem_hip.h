@@ -1351,6 +1351,107 @@ int hdem_flowpath_u8_dev(hdem_ctx *ctx, const uint8_t *d8, int H, int W, const v
                          uint32_t *where, int flags,
                          hdem_flowpath_stats *stats);  /* device pointers; step_len host */
 
+/* ---- A20  DInfFlowDirection.apply  (new operator: Tarboton's D-infinity flow direction) ----
+ * The D-infinity word, one uint32 per cell, is what A20 writes and A21 reads:
+ *   bits 0-15   q, 0 ... 32768: the share of the cell's outflow that goes to the DIAGONAL
+ *               receiver, in units of 2^-15
+ *   bits 16-19  facet, 0 ... 8; every other bit is 0
+ * facet 0: no outflow, and then q = 0.  Facets 1 ... 8 (Tarboton 1997) as (cardinal neighbour e1,
+ * diagonal neighbour e2, ac, af), north = row - 1:
+ *   1 (E, NE, 0, +1)   2 (N, NE, 1, -1)   3 (N, NW, 1, +1)   4 (W, NW, 2, -1)
+ *   5 (W, SW, 2, +1)   6 (S, SW, 3, -1)   7 (S, SE, 3, +1)   8 (E, SE, 4, -1)
+ * q = 0 sends everything to e1, q = 32768 everything to e2, anything else to both; a receiver
+ * whose share is 0 is no receiver.
+ *
+ * dem: float32 H x W, NaN is nodata.  All arithmetic is float64 on the float32 elevations, one
+ * rounding per operation, no fused multiply-add.  For an interior cell with a non-NaN centre e0,
+ * each facet k = 1 ... 8 in order whose e1 and e2 are both non-NaN gives, with d1 the spacing
+ * towards e1 (dx for E / W, dy for N / S) and d2 the other one:
+ *   s1 = (e0 - e1) / d1                    s2 = (e1 - e2) / d2
+ *   s2 <= 0:              s = s1,                             q = 0
+ *   s2 * d1 >= s1 * d2:   s = (e0 - e2) / sqrt(d1^2 + d2^2),  q = 32768
+ *   otherwise:            s = sqrt(s1^2 + s2^2), r = atan2(s2, s1),
+ *                         q = rint(r / atan2(d2, d1) * 32768)
+ * The first facet with the strictly greatest s > 0 wins; atan2(s2, s1) is evaluated once, for the
+ * winner (atan2(d2, d1) is worked out by the host).  Cells on the raster ring, NaN centres and
+ * cells where no facet has a positive slope get word 0.
+ * fallback (optional, uint8 ESRI D8 codes, H x W): a cell that would get word 0 and whose code is
+ * not 0 takes that direction as a canonical word: E -> facet 1, N -> 2, W -> 4, S -> 6 with q = 0;
+ * NE -> facet 1, NW -> 3, SW -> 5, SE -> 7 with q = 32768.  With the A8 (ResolveFlats) codes of an
+ * eps = 0 fill the flats keep draining and the combined graph stays acyclic: elevation, then flat
+ * distance, decreases along every edge.
+ * Optional float32 outputs (NULL: no store):
+ *   angle   af * r + ac * pi / 2, radians counter-clockwise from east, with r = 0 and
+ *           r = atan2(d2, d1) in the first two cases; a result >= 2 pi reads 0; -1 where the word
+ *           is 0; the D8 direction's multiple of pi / 4 in a fallback cell
+ *   slope   (float)s of the winner; 0 where none won, NaN at a NaN centre
+ * One radius-1 stencil launch on the tile staging of A14.  words and slope are the same bits
+ * from run to run and equal to the formulas above in IEEE float64 up to the device library's
+ * atan2, which reaches q only through a quotient rounded to 15 bits.
+ * HDEM_ERR_BAD_ARG before the launch: a null dem or words, dx or dy not finite and > 0, unknown
+ * flags; after it: a fallback byte that is no D8 code.  No workspace but 32 bytes of counters.
+ * The _dev form synchronises the context's stream once to read them.  stats may be NULL;
+ * otherwise the caller sets stats->struct_size first; ms_total is filled while profiling is on. */
+typedef struct hdem_dinf_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_dinf_stats), set by the caller               */
+    float ms_total;          /* the launch (HIP events; profiling)                           */
+    int64_t no_flow;         /* cells whose word is 0                                        */
+    int64_t fallback_cells;  /* cells that took their direction from fallback                */
+} hdem_dinf_stats;           /* sizeof == 24 */
+int hdem_dinf_f32(hdem_ctx *ctx, const float *dem, int H, int W, const uint8_t *fallback,
+                  double dx, double dy, uint32_t *words, float *angle, float *slope, int flags,
+                  hdem_dinf_stats *stats);             /* host pointers, synchronous */
+int hdem_dinf_f32_dev(hdem_ctx *ctx, const float *dem, int H, int W, const uint8_t *fallback,
+                      double dx, double dy, uint32_t *words, float *angle, float *slope,
+                      int flags, hdem_dinf_stats *stats);         /* device pointers */
+
+/* ---- A21  DInfFlowAccumulation.apply  (new operator: D-infinity flow accumulation) ----
+ * words: uint32 H x W, the D-infinity words of A20.  A donor of a cell c is an 8-neighbour whose
+ * word names c with a non-zero share.  With U = 2^frac_bits, frac_bits 0 ... 16:
+ *   A[c] = U + sum over the donors d of c of share(d -> c)
+ *   to_diag(d) = (A[d] * q[d]) >> 15   (uint64)        to_card(d) = A[d] - to_diag(d)
+ * Integer adds only: every cell's outflow is conserved to the last unit, the sum of A over the
+ * cells with facet 0 is H * W * U exactly, and the result is the same from run to run and in
+ * whichever order the cells are taken.  H * W <= 2^32 - 1 keeps A < 2^48 and the product
+ * below 2^63.
+ *   sum     int64, A
+ *   value   float32, (float)((double)A * 2^-frac_bits): the area in cells
+ * At least one of the two is wanted.
+ * Accumulation over a DAG, in the structure of A8: classify (words validated, the working raster
+ * initialised, every tile listed), then rounds of tile visits -- a 64 x 64 tile and its one-cell
+ * halo in LDS, a cell whose donors are all final becomes final with its sum, until the tile
+ * stops changing; a tile runs again when one of its eight neighbours finalised a frame cell in
+ * the round before -- and a streaming pass that writes the outputs.  The host reads one word per
+ * round.  The working raster is one uint64 per cell (bit 63: final): the caller's sum, or 8 B per
+ * cell of the context's arena, beside 16 B per tile.
+ * HDEM_ERR_BAD_ARG before any launch: a null words, neither output, frac_bits outside 0 ... 16,
+ * unknown flags, more than 2^32 - 1 cells; after classify, with the count in the text: an
+ * invalid word (facet > 8, q > 32768, facet 0 with q != 0, stray bits), a receiver outside the
+ * raster; after the last round: words that form a cycle ("N cells never resolve"; only
+ * user-supplied words can).  The outputs are unspecified then.
+ * rounds and tile_visits depend on the schedule; every other count does not. */
+typedef struct hdem_dinfacc_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_dinfacc_stats), set by the caller            */
+    int32_t rounds;          /* rounds of tile visits that had work                          */
+    int64_t tile_visits;     /* workgroups launched over all rounds                          */
+    int64_t split_cells;     /* cells with two receivers (0 < q < 32768)                     */
+    int64_t terminal_cells;  /* cells with facet 0                                           */
+    int64_t invalid;         /* invalid words: refused                                       */
+    int64_t outside;         /* cells with a receiver outside the raster: refused            */
+    int64_t unresolved;      /* cells that never became final (a cycle): refused             */
+    int32_t tile_h, tile_w;
+    float ms_classify;       /* (HIP events; profiling)                                      */
+    float ms_relax;          /* all rounds, the host reads included                          */
+    float ms_final;
+    int32_t reserved;        /* 0                                                            */
+} hdem_dinfacc_stats;        /* sizeof == 80 */
+int hdem_dinfacc_u32(hdem_ctx *ctx, const uint32_t *words, int H, int W, int frac_bits,
+                     int64_t *sum, float *value, int flags,
+                     hdem_dinfacc_stats *stats);       /* host pointers, synchronous */
+int hdem_dinfacc_u32_dev(hdem_ctx *ctx, const uint32_t *words, int H, int W, int frac_bits,
+                         int64_t *sum, float *value, int flags,
+                         hdem_dinfacc_stats *stats);   /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
