@@ -1,6 +1,7 @@
 """
 Size regimes of the tiled operators: inputs for tests/test_size_regimes.py (the predicates and
-the closed forms, on the CPU) and tests/test_gpu_size_regimes.py (the HIP operators on them).
+the closed forms, on the CPU), tests/test_gpu_size_regimes.py and
+tests/test_gpu_size_regimes_newer.py (the HIP operators on them).
 A plain helper module: mirrored constants, one predicate per host-side decision that depends
 on the size of the raster, builders of the rasters that reach the far side of each decision,
 and the answers of the constructed ones in closed form.
@@ -19,6 +20,17 @@ every decision below takes its trivial value:
     (flowacc / upstream degree kernels, the forests                           second_stride_tiles
     of Watersheds and the flow trace)
   streamnet_end_kernel or streamnet_end_sparse_kernel  K >= 2 * words       dense_ends
+  second stride of flowsum_forest_degree_kernel,       8 * CUs workgroups   past_the_cap,
+    upext_forest_degree_kernel and                                            late_tiles,
+    flowpath_forest_kernel (private copies of the                             full_late_tiles
+    same grid: weighted accumulation, upstream
+    extremes and the breach, path sums and extremes)
+  second workgroup of dinfacc_schedule_kernel (one     256 tiles            schedule_blocks
+    thread per tile: D-infinity accumulation)
+
+The last two rows are run by tests/test_gpu_size_regimes_newer.py, which also takes the four
+older forest operators to ``tall_codes_2d``: the ``wide`` raster has no full tile past the first
+stride (its late tiles are one cell high), the same extent upright has nine at 256 CUs.
 
 The words of a scan are ``zonal_words`` (one bit per id 1 ... H * W) for the zonal statistics
 and ``tile_words`` (one 64-bit word per tile row: H * ceil(W / 64)) for the stream network and
@@ -29,8 +41,10 @@ import functools
 
 import numpy as np
 
+from hydrodem_amd import dinf
 from test_flowacc import acc_kahn, random_acyclic_codes, receivers
 from test_streamorder import link_stops
+from test_upextreme import IDENTITY, carve_ref, split_words, words_of
 from test_watersheds import labels_doubling
 from test_zonal import blobs, extremes, own_zones
 
@@ -50,6 +64,16 @@ FOREST_NT = 256             # `constexpr int NT = 256` of hdem_flowacc.hip, hdem
                             # hdem_watershed.hip and hdem_flowtrace.hip (the forest workgroups)
 CAP_PER_CU = 8              # hdem_d8tile.h d8_forest_plan_of `(int64_t)ctx->num_cus * 8`; the same
                             # in `degree_blocks` of hdem_flowacc.hip and hdem_upstream.hip
+# The operators merged since keep the same two figures in copies of their own:
+#   hdem_flowsum.hip    `constexpr int NT = 256`, `forest_blocks = (nslots + NT - 1) / NT` and
+#                       `degree_blocks = min(forest_blocks, (int64_t)ctx->num_cus * 8)`
+#   hdem_upextreme.hip  `constexpr int NT = 256`, `forest_blocks = (g.nslots + NT - 1) / NT` and
+#                       the same `degree_blocks`
+#   hdem_flowpath.hip   `constexpr int NT = 256` and `d8_forest_plan_of(ctx, nslots, NT)`, whose
+#                       grid is `min((nslots + nt - 1) / nt, (int64_t)ctx->num_cus * 8)`
+# ... the same figures as FOREST_NT and CAP_PER_CU, so forest_blocks and past_the_cap serve them
+SCHEDULE_NT = 256           # hdem_stencil_tile.h `constexpr int NT = 256`, the workgroup of
+                            # dinfacc_schedule_kernel (hdem_dinf.hip): one thread per tile
 CUS = (64, 256, 304)        # compute-unit counts the inputs are checked at; the MI355X has 256
 
 
@@ -355,3 +379,211 @@ def compact_by_rule(codes):
 def wide_codes(cus):
     shape = wide_shape(cus)
     return _frozen(random_acyclic_codes(*shape, seed=shape[1], ramp=True))
+
+
+# ---------------------------------------------------------------------------
+# 5. the same extent stood upright: full tiles in the second stride
+# ---------------------------------------------------------------------------
+def tall_shape(cus):
+    """``wide_shape`` transposed: two tile columns, the second one cell wide, so that the tiles
+    past the first stride alternate between full 64 x 64 tiles and one-column tiles.
+    67 200 x 65 at 256 CUs."""
+    return wide_shape(cus)[1], 65
+
+
+@functools.lru_cache(maxsize=None)
+def tall_codes_2d(cus):
+    """``random_acyclic_codes`` with the ramp, as ``wide_codes``, and the west column made a
+    trunk: all S down to a terminal cell in the last row.  The ramp sends every path north-west
+    and the raster is 65 cells wide, so on its own no path collects more than about 1 900 cells
+    (1 915 at 256 CUs) and hardly a step enters the last tiles from the tiles above them (2 at
+    256 CUs, none at 64 and 304).  The trunk collects what reaches the west edge and carries it
+    south into the tiles past the first stride.  Every other cell still steps to a strictly
+    lower one and the trunk never leaves its column, so the codes stay acyclic."""
+    shape = tall_shape(cus)
+    codes = random_acyclic_codes(*shape, seed=shape[0], ramp=True)
+    codes[:, 0] = S
+    codes[-1, 0] = 0
+    return _frozen(codes)
+
+
+def late_tiles(shape, cus):
+    """The indices (row-major, ``ty * tiles_x + tx``; a tile's slots are ``tile * PER ...``) of
+    the tiles all of whose perimeter slots lie past the first stride: the last
+    ``second_stride_tiles`` of them."""
+    tiles = tiles_of(shape)
+    return np.arange(tiles - second_stride_tiles(shape, cus), tiles)
+
+
+def tile_of_cells(shape):
+    """The tile index of every cell, int64."""
+    y, x = np.indices(shape, dtype=np.int64)
+    return y // TS * _ceil(shape[1], TS) + x // TS
+
+
+def late_mask(shape, cus):
+    """The cells of ``late_tiles``."""
+    late = late_tiles(shape, cus)
+    return tile_of_cells(shape) >= late[0] if late.size else np.zeros(shape, bool)
+
+
+def full_late_tiles(shape, cus):
+    """The number of ``late_tiles`` that are whole 64 x 64 tiles."""
+    tiles_x = _ceil(shape[1], TS)
+    ty, tx = np.divmod(late_tiles(shape, cus), tiles_x)
+    return int((((ty + 1) * TS <= shape[0]) & ((tx + 1) * TS <= shape[1])).sum())
+
+
+def late_crossings(codes, cus):
+    """The D8 steps that change tile with a late tile on either side: ``into`` one (from any
+    other tile), ``out`` of one (to any other tile), and of these the steps between a late tile
+    and a tile of the first stride, ``from_first`` and ``to_first``."""
+    rec = receivers(codes)
+    tile = tile_of_cells(codes.shape).ravel()
+    first_late = late_tiles(codes.shape, cus)[0]
+    src = np.flatnonzero(rec >= 0)
+    dst = rec[src]
+    src, dst = tile[src], tile[dst]
+    cross = src != dst
+    return {"into": int((cross & (dst >= first_late)).sum()),
+            "out": int((cross & (src >= first_late)).sum()),
+            "from_first": int(((src < first_late) & (dst >= first_late)).sum()),
+            "to_first": int(((src >= first_late) & (dst < first_late)).sum())}
+
+
+BREACH_SEED = 3              # the DEM of the breach test: default_rng(3).random(shape) * 100
+
+
+def tall_dem_2d(cus):
+    shape = tall_shape(cus)
+    return (np.random.default_rng(BREACH_SEED).random(shape) * 100).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def tall_carved(cus):
+    """``carve_ref`` of ``tall_dem_2d`` along ``tall_codes_2d``: (carved, source, pits, lowered)."""
+    carved, source, pits, lowered = carve_ref(tall_dem_2d(cus), tall_codes_2d(cus))
+    return _frozen(carved, source) + (pits, lowered)
+
+
+@functools.lru_cache(maxsize=None)
+def acc_of(kind, cus):
+    """``acc_kahn`` of the wide or the tall codes, int64, made once."""
+    return _frozen(acc_kahn(wide_codes(cus) if kind == "wide" else tall_codes_2d(cus)))
+
+
+# ---------------------------------------------------------------------------
+# 6. the schedule of the D-infinity accumulation: one thread per tile
+# ---------------------------------------------------------------------------
+def schedule_blocks(shape):
+    """hdem_dinf.hip ``dim3((unsigned)((tiles + NT - 1) / NT))`` of dinfacc_schedule_kernel."""
+    return _ceil(tiles_of(shape), SCHEDULE_NT)
+
+
+# 258 tiles in a row, the last one partial: the smallest strip with a tile in the second
+# workgroup; the same three rows high; 18 x 17 tiles: tiles_x = 17 does not divide 256, tile 256
+# is (15, 1) and its eight neighbours lie on both sides of the workgroup boundary
+DINF_SHAPES = ((1, 257 * TS + PARTIAL), (3, 257 * TS + PARTIAL), (1093, 1029))
+DINF_SEED = 4               # of test_gpu_dinf.random_acyclic_words on the last two
+
+
+def strip_words(shape, segment=None):
+    """The canonical D-infinity words of ``strip_codes``; a word may not point outside the
+    raster as a D8 code may, so the last cell is terminal."""
+    codes = strip_codes(shape, segment)
+    codes.reshape(-1)[-1] = 0
+    return dinf.words_from_d8(codes)
+
+
+# ---------------------------------------------------------------------------
+# 7. the newer operators on strips, in closed form
+# ---------------------------------------------------------------------------
+def _heads_and_ends(n, segment):
+    at = np.arange(n, dtype=np.int64)
+    head = at // segment * segment if segment else np.zeros(n, np.int64)
+    end = np.minimum(head + segment - 1, n - 1) if segment else np.full(n, n - 1, np.int64)
+    return at, head, end
+
+
+def strip_flowsum(shape, q, segment=None):
+    """WeightedFlowAccumulation on ``strip_codes``: the prefix sum of ``q`` restarted at every
+    segment head, int64."""
+    n = shape[0] * shape[1]
+    at, head, _ = _heads_and_ends(n, segment)
+    prefix = np.concatenate([[0], np.cumsum(np.asarray(q, np.int64).ravel())])
+    return (prefix[at + 1] - prefix[head]).reshape(shape)
+
+
+def strip_pathsum(shape, q, segment=None):
+    """FlowPathSum on ``strip_codes`` without streams: the sum of ``q`` from the cell to the
+    cell before its segment end (the stop costs nothing), int64; the stop raster is
+    ``strip_answer["stop"]``."""
+    n = shape[0] * shape[1]
+    at, _, end = _heads_and_ends(n, segment)
+    prefix = np.concatenate([[0], np.cumsum(np.asarray(q, np.int64).ravel())])
+    return (prefix[end] - prefix[at]).reshape(shape)
+
+
+def _running(words, mode, segment, backwards):
+    """The running unsigned minimum / maximum of flat uint64 words inside every segment, from
+    the head forwards or from the end backwards."""
+    n = words.size
+    width = segment or n
+    rows = _ceil(n, width)
+    padded = np.full(rows * width, IDENTITY[mode], np.uint64)
+    padded[:n] = words
+    padded = padded.reshape(rows, width)
+    best = np.minimum if mode == "min" else np.maximum
+    if backwards:
+        padded = padded[:, ::-1]
+    run = best.accumulate(padded, axis=1)
+    if backwards:
+        run = run[:, ::-1]
+    return np.ascontiguousarray(run).ravel()[:n]
+
+
+def strip_upextreme(shape, values, mode, segment=None):
+    """UpstreamExtreme on ``strip_codes``, (extreme, where): the running extreme from the
+    segment head to the cell, with its holder, in the word order of test_upextreme.words_of
+    (a NaN is absent, equal values keep the smallest index)."""
+    values = np.ascontiguousarray(values)
+    run = _running(words_of(values, mode), mode, segment, backwards=False)
+    return split_words(run, mode, values.dtype, shape)
+
+
+def strip_pathextreme(shape, values, mode, segment=None):
+    """FlowPathExtreme on ``strip_codes`` without streams, (extreme, where): the running
+    extreme from the cell to its segment end, both included."""
+    values = np.ascontiguousarray(values)
+    run = _running(words_of(values, mode), mode, segment, backwards=True)
+    return split_words(run, mode, values.dtype, shape)
+
+
+def strip_dinf(shape, frac_bits, segment=None):
+    """DInfFlowAccumulation on ``strip_words``: the D8 accumulation in units of 2^-frac_bits."""
+    return strip_answer(shape, segment)["acc"] << frac_bits
+
+
+def strip_weights(shape, seed=0):
+    """uint32 weights below 2^31 with the bound itself at cell 0."""
+    w = np.random.default_rng(seed).integers(0, 2 ** 31, shape, dtype=np.int64).astype(U32)
+    w.reshape(-1)[0] = 2 ** 31 - 1
+    return w
+
+
+def strip_values(shape, trend, dtype=np.float32, seed=0):
+    """Values along a strip that drift by ``trend`` per eight cells under noise of 30, floored
+    to whole numbers (ties), 5 % NaN and some -0.0 for float32: with ``trend`` -1 the running
+    minimum from the head keeps changing all the way (and the running maximum from the end),
+    with +1 the other two: a new holder in about three tiles of four, held for 80 cells on
+    average and 500 at the most, so that a tile's answer comes from up to eight tiles away.
+    Against the drift the extreme is found near the far end and carried the whole way."""
+    rng = np.random.default_rng(seed)
+    n = shape[0] * shape[1]
+    v = np.floor(rng.normal(0.0, 30.0, n) + trend * np.arange(n) / 8)
+    if np.dtype(dtype) == U32:
+        return (v - v.min()).astype(U32).reshape(shape)
+    v = v.astype(np.float32)
+    v[v == 0] = np.where(rng.random(int((v == 0).sum())) < 0.5, -0.0, 0.0)
+    v[rng.random(n) < 0.05] = np.nan
+    return v.reshape(shape)

@@ -1,19 +1,27 @@
 """
-tests/size_regimes.py without a device: every input that tests/test_gpu_size_regimes.py runs
-satisfies the predicate it exists for, at 64, 256 and 304 compute units; every closed form
-agrees with the suite's existing reference of the same operator on a small copy of the same
-construction (a strip of 700 cells, a column of 9 000 rows); and the zonal inputs put ids into
-every scan chunk, so that no chunk offset can be wrong unseen.
+tests/size_regimes.py without a device: every input that tests/test_gpu_size_regimes.py and
+tests/test_gpu_size_regimes_newer.py run satisfies the predicate it exists for, at 64, 256 and
+304 compute units; every closed form agrees with the suite's existing reference of the same
+operator on a small copy of the same construction (a strip of 700 cells, a column of 9 000
+rows); the zonal inputs put ids into every scan chunk, so that no chunk offset can be wrong
+unseen; and the tall raster sends flow, carved cells and streams through the tiles past the
+first grid stride, so that the path operators, which no stride-skipping mutant may be run
+against, cannot be right there by accident.
 """
 import numpy as np
 import pytest
 
 import size_regimes as sr
 from test_depressions import reference as depressions_reference
+from test_dinf import accumulate_ref, counts_of
 from test_flowacc import acc_kahn, terminal_mask
+from test_flowpath import extreme_doubling, sum_doubling
+from test_flowsum import wsum_kahn
 from test_flowtrace import trace_doubling
+from test_gpu_dinf import random_acyclic_words
 from test_streamnet import COUNTERS, same_table, table_np
 from test_streamorder import link_ends, order_kahn, stream_of
+from test_upextreme import same_bytes, upext_kahn
 from test_upstream import upstream_kahn
 from test_watersheds import labels_doubling
 
@@ -183,6 +191,139 @@ def test_strip_closed_forms_are_the_references_on_700_cells(shape, segment):
     assert outlets.size == int(terminal_mask(codes).sum()) == (14 if segment else 1)
     # segments do not line up with tiles
     assert segment is None or sr.TS % segment != 0
+
+
+# ---------------------------------------------------------------------------
+# 5. - 7. the newer operators: flowsum, upstream extremes, path sums, D-infinity
+# ---------------------------------------------------------------------------
+def test_the_newer_predicates_on_the_thresholds_themselves():
+    assert sr.SCHEDULE_NT == 256
+    assert [sr.schedule_blocks((1, n * 64)) for n in (1, 256, 257)] == [1, 1, 2]
+    assert sr.schedule_blocks((1024, 1024)) == 1 and sr.schedule_blocks((1025, 1024)) == 2
+    # 256 CUs: 524 288 slots in the first stride, tile 2 080 straddles its end
+    assert sr.late_tiles((1, 2081 * 64), 256).size == 0
+    assert sr.late_tiles((1, 2083 * 64), 256).tolist() == [2081, 2082]
+    assert 2080 * sr.PER < sr.CAP_PER_CU * 256 * sr.FOREST_NT <= 2081 * sr.PER
+    assert sr.tile_of_cells((65, 130)).ravel()[[0, 63, 64, 129, 64 * 130, 64 * 130 + 129]] \
+        .tolist() == [0, 0, 1, 2, 3, 5]
+    assert sr.late_mask((1, 2083 * 64), 256).sum() == 2 * 64
+    assert sr.full_late_tiles((64, 2083 * 64), 256) == 2
+    assert sr.full_late_tiles((63, 2083 * 64), 256) == 0
+
+
+@pytest.mark.parametrize("cus", sr.CUS)
+def test_the_newer_inputs_satisfy_their_predicates_at_any_compute_unit_count(cus):
+    tall, wide = sr.tall_shape(cus), sr.wide_shape(cus)
+    assert tall == (wide[1], 65) and sr.tiles_of(tall) == sr.tiles_of(wide)
+    assert sr.past_the_cap(tall, cus)
+    late = sr.late_tiles(tall, cus)
+    assert late.size == sr.second_stride_tiles(tall, cus) > 0
+    assert late[-1] == sr.tiles_of(tall) - 1
+    assert late[0] * sr.PER >= sr.CAP_PER_CU * cus * sr.FOREST_NT > (late[0] - 1) * sr.PER
+    assert sr.full_late_tiles(tall, cus) >= 8
+    assert sr.full_late_tiles(wide, cus) == 0           # what the wide raster does not supply
+    assert sr.late_mask(tall, cus).sum() == sr.full_late_tiles(tall, cus) * 64 * 64 \
+        + (late.size - sr.full_late_tiles(tall, cus)) * 64
+    if cus == 256:
+        assert tall == (67200, 65) and late.tolist() == list(range(2081, 2100))
+        assert sr.full_late_tiles(tall, cus) == 9 and sr.late_mask(tall, cus).sum() == 37504
+    # the schedule of the D-infinity accumulation does not depend on the compute units
+    assert [sr.tiles_of(s) for s in sr.DINF_SHAPES] == [258, 258, 18 * 17]
+    assert all(sr.schedule_blocks(s) >= 2 for s in sr.DINF_SHAPES)
+    assert sr.schedule_blocks(sr.DINF_SHAPES[0]) == 2
+    assert sr.DINF_SHAPES[0][1] % sr.TS == sr.PARTIAL       # a whole tile and a partial one there
+    assert divmod(256, 17) == (15, 1)                   # tile 256 of 18 x 17 is (15, 1)
+    for shape in sr.strip_shapes(cus).values():
+        assert sr.schedule_blocks(shape) >= 3
+    assert sr.schedule_blocks(tall) >= 3
+    if cus == 256:
+        assert sr.schedule_blocks(sr.strip_shapes(cus)["row"]) == 9
+
+
+@pytest.mark.parametrize("cus", sr.CUS)
+def test_the_tall_raster_exercises_its_late_tiles(cus):
+    """Conditions on the input, so that a kernel that goes wrong past its first stride cannot
+    give the right answer: flow crosses the late tiles' edges both ways, more of it arrives in
+    a late tile than a tile holds, the carving lowers cells inside and outside, and the stream
+    set divides them."""
+    shape = sr.tall_shape(cus)
+    codes = sr.tall_codes_2d(cus)
+    assert codes.shape == shape and codes.dtype == np.uint8
+    late = sr.late_mask(shape, cus)
+    steps = sr.late_crossings(codes, cus)
+    print(cus, "CUs:", steps)
+    assert steps["into"] > 100 and steps["out"] > 100
+    assert steps["from_first"] > 0 and steps["to_first"] > 0
+    acc = sr.acc_of("tall", cus)
+    assert acc[late].max() > 64 * 64                    # the flow entered from outside
+    assert acc.max() < 2 ** 32
+    stream = acc >= sr.SPARSE_THRESHOLD
+    assert stream[late].any() and not stream[late].all()
+    _, source, pits, lowered = sr.tall_carved(cus)
+    low = source != sr.NONE
+    assert pits > 0 and lowered == int(low.sum())
+    assert low[late].any() and low[~late].any() and not low[late].all()
+    if cus == 256:
+        assert steps == {"into": 605, "out": 670, "from_first": 3, "to_first": 68}
+        assert int(low[late].sum()) == 13692 and lowered == 1610380
+
+
+def newer_strips():
+    return [(shape, segment) for shape in ((1, 700), (700, 1)) for segment in (None, sr.SEGMENT)]
+
+
+STRIP_IDS = [f"{by_shape(shape)}-{'segments' if segment else 'one_path'}"
+             for shape, segment in newer_strips()]
+
+
+@pytest.mark.parametrize("shape, segment", newer_strips(), ids=STRIP_IDS)
+def test_the_newer_closed_forms_are_the_references_on_700_cells(shape, segment):
+    codes = sr.strip_codes(shape, segment)
+    stop = sr.strip_answer(shape, segment)["stop"]
+    q = sr.strip_weights(shape, seed=7).astype(np.int64)
+    assert q.ravel()[0] == 2 ** 31 - 1 and q.max() < 2 ** 31
+    assert np.array_equal(sr.strip_flowsum(shape, q, segment), wsum_kahn(codes, q))
+    got_stop, total = sum_doubling(codes, q)
+    assert np.array_equal(stop, got_stop)
+    assert np.array_equal(sr.strip_pathsum(shape, q, segment), total)
+    for mode in ("min", "max"):
+        for trend in (-1, 1):
+            for dtype in (np.float32, np.uint32):
+                v = sr.strip_values(shape, trend, dtype, seed=5)
+                assert v.dtype == dtype and v.shape == shape
+                if dtype == np.float32:         # ties, absent values and both zeros
+                    assert np.isnan(v).any() and np.unique(v[~np.isnan(v)]).size < 0.5 * v.size
+                for got, want in ((sr.strip_upextreme(shape, v, mode, segment),
+                                   upext_kahn(codes, v, mode)),
+                                  (sr.strip_pathextreme(shape, v, mode, segment),
+                                   extreme_doubling(codes, v, mode)[1:])):
+                    assert same_bytes(got[0], want[0]) and same_bytes(got[1], want[1])
+    # the running extreme changes all along the path when the values drift its way
+    v = sr.strip_values((1, 7000), -1, seed=5)
+    assert np.unique(sr.strip_upextreme((1, 7000), v, "min")[1]).size > 7000 // sr.TS // 2
+    assert np.unique(sr.strip_pathextreme((1, 7000), v, "max")[1]).size > 7000 // sr.TS // 2
+    words = sr.strip_words(shape, segment)
+    assert words.ravel()[-1] == 0 and (words.ravel()[:-1] != 0).sum() >= 700 - 14
+    for frac_bits in (0, 16):
+        assert np.array_equal(sr.strip_dinf(shape, frac_bits, segment),
+                              accumulate_ref(words, frac_bits))
+
+
+def test_strip_words_on_the_length_the_schedule_tests_use():
+    shape = (1, 16485)
+    assert shape == sr.DINF_SHAPES[0]
+    for segment in (None, sr.SEGMENT):
+        assert np.array_equal(accumulate_ref(sr.strip_words(shape, segment)),
+                              sr.strip_answer(shape, segment)["acc"] << 16)
+
+
+@pytest.mark.parametrize("shape", sr.DINF_SHAPES[1:], ids=by_shape)
+def test_random_words_split_on_the_schedule_shapes(shape):
+    words = random_acyclic_words(shape, seed=sr.DINF_SEED)
+    share = counts_of(words)["split_cells"] / words.size
+    print(by_shape(shape), "split share", share)
+    assert share >= 0.05
+    assert (0.075 < share < 0.076) if shape[0] == 3 else (0.111 < share < 0.112)
 
 
 def test_the_numbering_rule_on_a_raster_of_several_tiles():
