@@ -31,6 +31,8 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      TerrainAttributes, Slope, Aspect, WetnessIndex,
                                      DemToWetness,
                                      DInfFlowDirection, DInfFlowAccumulation, DemToDInfArea,
+                                     WeightedDInfFlowAccumulation, AreaWetnessIndex,
+                                     DemToDInfWetness,
                                      EuclideanDistance, EuclideanAllocation, BurnStreams,
                                      ResolveFlats,
                                      Depressions, DepressionInventory,

@@ -240,6 +240,18 @@ class _DInfAccStats(_SizedStats):
                 ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class _DInfSumStats(_SizedStats):
+    """``hdem_dinfsum_stats``: the accumulation's fields, then what the weights came to."""
+    _fields_ = _DInfAccStats._fields_ + [("nan_weights", ctypes.c_int64),
+                                         ("bad_weights", ctypes.c_int64),
+                                         ("total", ctypes.c_uint64)]
+
+
+class _TerrainAreaStats(_SizedStats):
+    """``hdem_terrain_area_stats``: the terrain fields, then the cells whose area is <= 0."""
+    _fields_ = _TerrainStats._fields_ + [("nonpositive_area", ctypes.c_int64)]
+
+
 DEPR_COMPACT = 1    # HDEM_DEPR_COMPACT
 # columns of the depression table, in the order of the C ABI's pointers
 DEPR_COLUMNS = (("first", np.uint32), ("area", np.uint32), ("level", np.float32),
@@ -390,6 +402,14 @@ SIGNATURES = {
                           _c.POINTER(_DInfStats)],
     "hdem_dinfacc_u32": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _c.POINTER(_DInfAccStats)],
     "hdem_dinfacc_u32_dev": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _c.POINTER(_DInfAccStats)],
+    "hdem_dinfsum_u32": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i,
+                         _c.POINTER(_DInfSumStats)],
+    "hdem_dinfsum_u32_dev": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i,
+                             _c.POINTER(_DInfSumStats)],
+    "hdem_terrain_area_f32": [_vp, _vp, _i, _i, _vp, _vp, _vp] + [_c.c_double] * 4 +
+                             [_vp] * 8 + [_i, _c.POINTER(_TerrainAreaStats)],
+    "hdem_terrain_area_f32_dev": [_vp, _vp, _i, _i, _vp, _vp, _vp] + [_c.c_double] * 4 +
+                                 [_vp] * 8 + [_i, _c.POINTER(_TerrainAreaStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

@@ -1,5 +1,5 @@
-// A20 / A21  D-infinity flow direction and accumulation (Tarboton 1997; new operators;
-// include/hydrodem_hip.h has the contract, DESIGN 3.24 the argument).
+// A20 / A21 / A22  D-infinity flow direction, accumulation and weighted accumulation (Tarboton
+// 1997; new operators; include/hydrodem_hip.h has the contract, DESIGN 3.24 and 3.25 the argument).
 //
 // The word of a cell: q in bits 0-15 (the share of the diagonal receiver in units of 2^-15),
 // the facet in bits 16-19.  Directions are numbered counter-clockwise from east, 0 = E,
@@ -13,11 +13,15 @@
 // Accumulation is a pull over donors on a DAG, in the structure of hdem_flats.hip:
 //   classify  (dinfacc_classify_kernel)  per tile: words validated and counted, the working
 //             raster (uint64 per cell, bit 63 = final, the low bits A) set to "not final",
-//             every tile listed for round 0.  It writes every word that is read later.
+//             every tile listed for round 0.  It writes every word that is read later.  The
+//             weighted form (A22) quantises the cell's weight here and leaves q(w) in the low
+//             bits of the "not final" word: the cell's own term, at no extra raster.
 //   visit     (dinfacc_visit_kernel)  one workgroup per listed tile: words and values of the
 //             tile and its one-cell halo in LDS; the donors of every cell as a bit mask beside
 //             its word; then a cell that is not final and whose donors are all final becomes
-//             final with U + the sum of their shares, until the tile stops changing.  One
+//             final with U (weighted: the q(w) its own not-yet-final word holds; a donor's word
+//             is only read once its FINAL bit has been seen, so the two uses never meet) + the
+//             sum of their shares, until the tile stops changing.  One
 //             iteration is four directional sweeps, one wave each (down the rows, up, along the
 //             columns to the right, to the left), so that a straight reach resolves in one
 //             iteration.  The waves do not wait for each other inside an iteration: a cell only
@@ -224,7 +228,39 @@ struct dinfacc_counters {
     unsigned long long unresolved;    // cells that never became final
     unsigned int listed;              // length of the list for the next round
     unsigned int pad;
+    // the weighted form (A22) alone, behind what the unweighted one reads
+    unsigned long long nan;           // NaN weights (they contribute 0)
+    unsigned long long negative;      // weights below 0 (-inf among them)
+    unsigned long long infinite;      // +inf
+    unsigned long long over;          // q(w) > 2^31 - 1
+    unsigned long long total;         // the sum of q(w) over the raster
 };
+constexpr size_t COUNTERS_UNWEIGHTED = offsetof(dinfacc_counters, nan);
+constexpr double Q_MAX = 2147483647.0;
+constexpr unsigned long long TOTAL_LIMIT = 1ull << 48;
+
+// q(w) of cell g (hdem_flowsum.hip's rule; integer weights shifted by frac_bits); a weight that
+// is refused counts 0.  n[]: what the weight is counted as (nan, negative, infinite, over).
+template <int WT>
+__device__ __forceinline__ uint64_t dinf_weight_of(const void *__restrict__ weights, size_t g,
+                                                   double scale, int frac_bits,
+                                                   unsigned int (&n)[4])
+{
+    if (WT == HDEM_FLOWSUM_F32) {
+        const float f = static_cast<const float *>(weights)[g];
+        if (f != f) { ++n[0]; return 0; }
+        if (f < 0.0f) { ++n[1]; return 0; }                    // -0.0 is not: it counts as 0
+        if (f == __builtin_inff()) { ++n[2]; return 0; }
+        const double d = rint((double)f * scale);   // exact product, one rounding to nearest even
+        if (d > Q_MAX) { ++n[3]; return 0; }
+        return (uint64_t)(long long)d;
+    }
+    const uint64_t v = (uint64_t)(WT == HDEM_FLOWSUM_U32 ? static_cast<const uint32_t *>(weights)[g]
+                                                          : static_cast<const uint8_t *>(weights)[g])
+                       << frac_bits;
+    if (v > 0x7FFFFFFFull) { ++n[3]; return 0; }
+    return v;
+}
 
 __device__ __forceinline__ uint64_t work_load(const uint64_t *p)
 {
@@ -243,18 +279,29 @@ __device__ __forceinline__ void lds_store(uint64_t *p, uint64_t v)
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// WT: 0 for the unweighted form, else the HDEM_FLOWSUM_* type of the weights
+template <int WT>
 __global__ __launch_bounds__(NT) void dinfacc_classify_kernel(
     const uint32_t *__restrict__ words, int H, int W, int tiles_x, uint64_t *__restrict__ work,
     uint32_t *__restrict__ left, uint32_t *__restrict__ stamp, uint32_t *__restrict__ list,
-    dinfacc_counters *__restrict__ cnt)
+    dinfacc_counters *__restrict__ cnt, const void *__restrict__ weights, double scale,
+    int frac_bits)
 {
     __shared__ unsigned int s_cnt[4];            // split, terminal, bad, outside
+    __shared__ unsigned int s_wcnt[4];           // weights: nan, negative, infinite, over
+    __shared__ unsigned long long s_total;
     const int tid = threadIdx.x;
     const d8_tile tile = d8_tile_of_block(tiles_x, H, W);
     if (tid < 4) s_cnt[tid] = 0;
+    if (WT) {
+        if (tid < 4) s_wcnt[tid] = 0;
+        if (tid == 0) s_total = 0;
+    }
     __syncthreads();
 
     unsigned int n[4] = {0, 0, 0, 0};
+    unsigned int nw[4] = {0, 0, 0, 0};
+    unsigned long long total = 0;
     for (int i = tid; i < TC; i += NT) {
         const int ly = i / TS, lx = i % TS;
         if (!tile.inside(ly, lx)) continue;
@@ -278,11 +325,23 @@ __global__ __launch_bounds__(NT) void dinfacc_classify_kernel(
             }
             n[3] += out;
         }
-        work[g] = 0;                             // not final
+        if (WT) {                                // not final, the own term in the low bits
+            const uint64_t q = dinf_weight_of<WT>(weights, g, scale, frac_bits, nw);
+            total += q;
+            work[g] = q;
+        } else {
+            work[g] = 0;                         // not final
+        }
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         if (n[j]) atomicAdd(&s_cnt[j], n[j]);
+    if (WT) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (nw[j]) atomicAdd(&s_wcnt[j], nw[j]);
+        if (total) atomicAdd(&s_total, total);
+    }
     __syncthreads();
     if (tid == 0) {
         left[blockIdx.x] = (uint32_t)(tile.th * tile.tw);
@@ -292,6 +351,13 @@ __global__ __launch_bounds__(NT) void dinfacc_classify_kernel(
         if (s_cnt[1]) atomicAdd(&cnt->terminal, (unsigned long long)s_cnt[1]);
         if (s_cnt[2]) atomicAdd(&cnt->bad, (unsigned long long)s_cnt[2]);
         if (s_cnt[3]) atomicAdd(&cnt->outside, (unsigned long long)s_cnt[3]);
+        if (WT) {
+            if (s_wcnt[0]) atomicAdd(&cnt->nan, (unsigned long long)s_wcnt[0]);
+            if (s_wcnt[1]) atomicAdd(&cnt->negative, (unsigned long long)s_wcnt[1]);
+            if (s_wcnt[2]) atomicAdd(&cnt->infinite, (unsigned long long)s_wcnt[2]);
+            if (s_wcnt[3]) atomicAdd(&cnt->over, (unsigned long long)s_wcnt[3]);
+            if (s_total) atomicAdd(&cnt->total, s_total);
+        }
     }
 }
 
@@ -315,6 +381,8 @@ __global__ __launch_bounds__(NT) void dinfacc_schedule_kernel(
     if (run) list[atomicAdd(&cnt->listed, 1u)] = (uint32_t)t;
 }
 
+// WEIGHTED: a cell's sum starts from the q(w) in its own not-yet-final word, not from `unit`
+template <bool WEIGHTED>
 __global__ __launch_bounds__(NT) void dinfacc_visit_kernel(
     const uint32_t *__restrict__ words, uint64_t *work, int H, int W, int tiles_x,
     const uint32_t *__restrict__ list, uint32_t round, uint64_t unit, uint32_t *__restrict__ stamp,
@@ -349,7 +417,8 @@ __global__ __launch_bounds__(NT) void dinfacc_visit_kernel(
     for (int k = 0; k < TC / NT; ++k) {
         const int i = tid + k * NT;
         const int c = (i / TS + 1) * LW + i % TS + 1;
-        if (lds_load(&v[c]) & FINAL) continue;
+        const uint64_t own = lds_load(&v[c]);
+        if (own & FINAL) continue;
         pending |= 1u << k;
         uint32_t donors = 0;
 #pragma unroll
@@ -357,7 +426,7 @@ __global__ __launch_bounds__(NT) void dinfacc_visit_kernel(
             if (word_gives(w[c + dir_dy(d) * LW + dir_dx(d)], (d + 4) & 7)) donors |= 1u << d;
         w[c] = (w[c] & 0xFFFFFFu) | (donors << 24);
         if (!donors) {
-            lds_store(&v[c], FINAL | unit);
+            lds_store(&v[c], FINAL | (WEIGHTED ? own : unit));
             changed = 1;
         }
     }
@@ -374,9 +443,10 @@ __global__ __launch_bounds__(NT) void dinfacc_visit_kernel(
     for (int iter = 0; iter < TC; ++iter) {
         changed = 0;
         for (int s = 0, c = c0; s < TS; ++s, c += step) {
-            if (lds_load(&v[c]) & FINAL) continue;
+            const uint64_t own = lds_load(&v[c]);
+            if (own & FINAL) continue;
             uint32_t donors = w[c] >> 24;
-            uint64_t sum = unit;
+            uint64_t sum = WEIGHTED ? own : unit;
             bool ready = true;
             while (donors) {
                 const int d = __builtin_ctz(donors);
@@ -449,6 +519,23 @@ __global__ __launch_bounds__(NT) void dinfacc_final_kernel(
         atomicAdd(&cnt->unresolved, (unsigned long long)s_unresolved);
 }
 
+// What a call of the accumulation is given: A21 (weights null) or A22.
+struct dinfacc_call {
+    const uint32_t *words;
+    int H, W;
+    const void *weights;              // null: every cell counts 2^frac_bits
+    int weight_type, frac_bits;
+    int64_t *sum;
+    float *value;
+};
+
+struct span {
+    const char *name;
+    uintptr_t lo, hi;
+};
+
+inline size_t weight_bytes(int weight_type) { return weight_type == HDEM_FLOWSUM_U8 ? 1 : 4; }
+
 // also the tile grid: nothing is allocated for a raster that is refused
 int dinfacc_check(const hdem_ctx *ctx, const uint32_t *words, int H, int W, int frac_bits,
                   const int64_t *sum, const float *value, int flags,
@@ -465,6 +552,174 @@ int dinfacc_check(const hdem_ctx *ctx, const uint32_t *words, int H, int W, int 
     HDEM_REQUIRE(!flags, HDEM_ERR_BAD_ARG, "D-infinity flow accumulation: unknown flags 0x%x",
                  flags);
     return d8_grid_of("D-infinity flow accumulation", H, W, g);
+}
+
+int dinfsum_check(const hdem_ctx *ctx, const dinfacc_call &a, int flags,
+                  const hdem_dinfsum_stats *stats, d8_grid *g)
+{
+    HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
+    HDEM_REQUIRE(a.words, HDEM_ERR_BAD_ARG, "null raster pointer");
+    HDEM_REQUIRE(a.H > 0 && a.W > 0, HDEM_ERR_BAD_ARG,
+                 "raster dimensions must be positive, got %d x %d", a.H, a.W);
+    if (int rc = d8_check_stats(stats, "hdem_dinfsum_stats")) return rc;
+    HDEM_REQUIRE(a.sum || a.value, HDEM_ERR_BAD_ARG,
+                 "weighted D-infinity flow accumulation: no output wanted");
+    HDEM_REQUIRE(a.weights, HDEM_ERR_BAD_ARG, "the weight raster is null");
+    HDEM_REQUIRE(a.weight_type >= HDEM_FLOWSUM_F32 && a.weight_type <= HDEM_FLOWSUM_U8,
+                 HDEM_ERR_BAD_ARG, "unknown weight type %d", a.weight_type);
+    if (a.weight_type == HDEM_FLOWSUM_F32)
+        HDEM_REQUIRE(a.frac_bits >= 0 && a.frac_bits <= 30, HDEM_ERR_BAD_ARG,
+                     "frac_bits is 0 ... 30, got %d", a.frac_bits);
+    else
+        HDEM_REQUIRE(a.frac_bits >= 0 && a.frac_bits <= 16, HDEM_ERR_BAD_ARG,
+                     "integer weights take frac_bits 0 ... 16, got %d", a.frac_bits);
+    HDEM_REQUIRE(!flags, HDEM_ERR_BAD_ARG,
+                 "weighted D-infinity flow accumulation: unknown flags 0x%x", flags);
+    if (int rc = d8_grid_of("weighted D-infinity flow accumulation", a.H, a.W, g)) return rc;
+    const size_t n = (size_t)a.H * a.W;
+    span s[4];
+    int ns = 0;
+    s[ns++] = {"words", (uintptr_t)a.words, (uintptr_t)a.words + 4 * n};
+    s[ns++] = {"weights", (uintptr_t)a.weights,
+               (uintptr_t)a.weights + n * weight_bytes(a.weight_type)};
+    const span outs[2] = {{"sum", (uintptr_t)a.sum, (uintptr_t)a.sum + 8 * n},
+                          {"value", (uintptr_t)a.value, (uintptr_t)a.value + 4 * n}};
+    for (const span &o : outs) {
+        if (!o.lo) continue;
+        for (int j = 0; j < ns; ++j)
+            HDEM_REQUIRE(o.hi <= s[j].lo || s[j].hi <= o.lo, HDEM_ERR_BAD_ARG,
+                         "weighted D-infinity flow accumulation: %s overlaps %s", o.name,
+                         s[j].name);
+        s[ns++] = o;
+    }
+    return HDEM_OK;
+}
+
+void launch_classify(hdem_ctx *ctx, const dinfacc_call &a, const d8_grid &g, uint64_t *work,
+                     uint32_t *left, uint32_t *stamp, uint32_t *list, dinfacc_counters *cnt)
+{
+    const dim3 grid((unsigned)g.tiles), block(NT);
+    const double scale = (double)(1ll << a.frac_bits);
+#define HDEM_DINF_CLASSIFY(WT)                                                                    \
+    hipLaunchKernelGGL((dinfacc_classify_kernel<WT>), grid, block, 0, ctx->stream, a.words, a.H,  \
+                       a.W, g.tiles_x, work, left, stamp, list, cnt, a.weights, scale, a.frac_bits)
+    if (!a.weights) HDEM_DINF_CLASSIFY(0);
+    else if (a.weight_type == HDEM_FLOWSUM_F32) HDEM_DINF_CLASSIFY(HDEM_FLOWSUM_F32);
+    else if (a.weight_type == HDEM_FLOWSUM_U32) HDEM_DINF_CLASSIFY(HDEM_FLOWSUM_U32);
+    else HDEM_DINF_CLASSIFY(HDEM_FLOWSUM_U8);
+#undef HDEM_DINF_CLASSIFY
+}
+
+// The accumulation of both forms on device pointers.  *st is filled when the launches ran, whatever
+// is returned; the caller publishes it.
+int dinfacc_dev(hdem_ctx *ctx, const dinfacc_call &a, const d8_grid &g, bool want_stats,
+                hdem_dinfsum_stats *st)
+{
+    const bool weighted = a.weights != nullptr;
+    const int H = a.H, W = a.W, tiles_x = g.tiles_x;
+    const int64_t tiles = g.tiles, cells = (int64_t)H * W;
+
+    // arena: counters | left, stamp, list: u32 per tile each | the working raster, u64 per
+    // cell, unless the caller's sum serves
+    const size_t head = 512;
+    static_assert(sizeof(dinfacc_counters) <= head, "counters outgrew their block");
+    const size_t per_tile = hdem_round16((size_t)tiles * 12);
+    const size_t bytes = head + per_tile + (a.sum ? 0 : (size_t)cells * 8);
+    char *ws = static_cast<char *>(hdem_arena(ctx, bytes));
+    if (!ws) return HDEM_ERR_OOM;
+    dinfacc_counters *cnt = reinterpret_cast<dinfacc_counters *>(ws);
+    uint32_t *left = reinterpret_cast<uint32_t *>(ws + head);
+    uint32_t *stamp = left + tiles, *list = stamp + tiles;
+    uint64_t *work = a.sum ? reinterpret_cast<uint64_t *>(a.sum)
+                           : reinterpret_cast<uint64_t *>(ws + head + per_tile);
+    const uint64_t unit = 1ull << (weighted ? 0 : a.frac_bits);
+    // the unweighted form neither zeroes nor reads the counters of the weights
+    const size_t cnt_bytes = weighted ? sizeof(dinfacc_counters) : COUNTERS_UNWEIGHTED;
+
+    hdem_event_timer<4> phases(ctx, want_stats);
+    if (int rc = phases.start()) return rc;
+    HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, cnt_bytes, ctx->stream));
+    const dim3 grid((unsigned)tiles);
+
+    phases.mark(0);
+    launch_classify(ctx, a, g, work, left, stamp, list, cnt);
+    phases.mark(1);
+    // one host read per round: the length of the round's list, which is its grid
+    dinfacc_counters host = {};
+    int64_t rounds = 0, visits = 0;
+    bool refused = false;
+    for (;; ++rounds) {
+        HDEM_HIP_CHECK(hipGetLastError());
+        HDEM_HIP_CHECK(hipMemcpyAsync(&host, cnt, cnt_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        refused = host.bad || host.outside || host.negative || host.infinite || host.over ||
+                  host.total >= TOTAL_LIMIT;
+        if (refused || !host.listed || rounds > cells) break;
+        visits += host.listed;
+        if (weighted)
+            hipLaunchKernelGGL(dinfacc_visit_kernel<true>, dim3(host.listed), dim3(NT), 0,
+                               ctx->stream, a.words, work, H, W, tiles_x, list, (uint32_t)rounds,
+                               unit, stamp, left);
+        else
+            hipLaunchKernelGGL(dinfacc_visit_kernel<false>, dim3(host.listed), dim3(NT), 0,
+                               ctx->stream, a.words, work, H, W, tiles_x, list, (uint32_t)rounds,
+                               unit, stamp, left);
+        HDEM_HIP_CHECK(hipMemsetAsync(&cnt->listed, 0, sizeof(cnt->listed), ctx->stream));
+        hipLaunchKernelGGL(dinfacc_schedule_kernel, dim3((unsigned)((tiles + NT - 1) / NT)),
+                           dim3(NT), 0, ctx->stream, g.tiles_y, tiles_x, (uint32_t)rounds + 1,
+                           left, stamp, list, cnt);
+    }
+    phases.mark(2);
+    if (!refused) {
+        hipLaunchKernelGGL(dinfacc_final_kernel, grid, dim3(NT), 0, ctx->stream, work, H, W,
+                           tiles_x, std::ldexp(1.0, -a.frac_bits), a.sum, a.value, cnt);
+        HDEM_HIP_CHECK(hipGetLastError());
+        HDEM_HIP_CHECK(hipMemcpyAsync(&host, cnt, cnt_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    phases.mark(3);
+    HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+
+    st->rounds = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
+    st->tile_visits = visits;
+    st->split_cells = (int64_t)host.split;
+    st->terminal_cells = (int64_t)host.terminal;
+    st->invalid = (int64_t)host.bad;
+    st->outside = (int64_t)host.outside;
+    st->unresolved = (int64_t)host.unresolved;
+    st->tile_h = TS;
+    st->tile_w = TS;
+    phases.read(&st->ms_classify, &st->ms_relax, &st->ms_final);
+    st->nan_weights = (int64_t)host.nan;
+    st->bad_weights = (int64_t)(host.negative + host.infinite + host.over);
+    st->total = host.total;
+    HDEM_REQUIRE(!host.bad, HDEM_ERR_BAD_ARG,
+                 "invalid D-infinity word in %llu cells: the facet is 0 ... 8 in bits 16-19, q is "
+                 "0 ... 32768 in bits 0-15 (0 with facet 0), every other bit is 0",
+                 host.bad);
+    HDEM_REQUIRE(!host.outside, HDEM_ERR_BAD_ARG,
+                 "D-infinity words send flow outside the raster in %llu cells", host.outside);
+    HDEM_REQUIRE(!host.negative && !host.infinite && !host.over, HDEM_ERR_BAD_ARG,
+                 "weights out of range in %llu cells: %llu negative, %llu infinite, %llu above "
+                 "2^31 - 1 once quantised (frac_bits %d)",
+                 host.negative + host.infinite + host.over, host.negative, host.infinite,
+                 host.over, a.frac_bits);
+    HDEM_REQUIRE(host.total < TOTAL_LIMIT, HDEM_ERR_BAD_ARG,
+                 "the quantised weights sum to %llu: the total must stay below 2^48 (frac_bits %d)",
+                 host.total, a.frac_bits);
+    HDEM_REQUIRE(!host.unresolved, HDEM_ERR_BAD_ARG,
+                 "D-infinity words form a cycle: %llu cells never resolve", host.unresolved);
+    return HDEM_OK;
+}
+
+// hdem_dinfsum_stats opens with the fields of hdem_dinfacc_stats
+static_assert(offsetof(hdem_dinfsum_stats, reserved) == offsetof(hdem_dinfacc_stats, reserved) &&
+                  offsetof(hdem_dinfsum_stats, nan_weights) == sizeof(hdem_dinfacc_stats),
+              "the weighted stats no longer open with the unweighted ones");
+inline hdem_dinfacc_stats unweighted_stats(const hdem_dinfsum_stats &st)
+{
+    hdem_dinfacc_stats out;
+    memcpy(&out, &st, sizeof(out));
+    return out;
 }
 
 }  // namespace
@@ -547,85 +802,13 @@ extern "C" int hdem_dinfacc_u32_dev(hdem_ctx *ctx, const uint32_t *words, int H,
     d8_grid g;
     if (int rc = dinfacc_check(ctx, words, H, W, frac_bits, sum, value, flags, stats, &g))
         return rc;
-    const int tiles_x = g.tiles_x;
-    const int64_t tiles = g.tiles, cells = (int64_t)H * W;
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
-    hdem_dinfacc_stats st = {};
-    d8_publish(stats, st);
-
-    // arena: counters | left, stamp, list: u32 per tile each | the working raster, u64 per
-    // cell, unless the caller's sum serves
-    const size_t head = 512;
-    static_assert(sizeof(dinfacc_counters) <= head, "counters outgrew their block");
-    const size_t per_tile = hdem_round16((size_t)tiles * 12);
-    const size_t bytes = head + per_tile + (sum ? 0 : (size_t)cells * 8);
-    char *ws = static_cast<char *>(hdem_arena(ctx, bytes));
-    if (!ws) return HDEM_ERR_OOM;
-    dinfacc_counters *cnt = reinterpret_cast<dinfacc_counters *>(ws);
-    uint32_t *left = reinterpret_cast<uint32_t *>(ws + head);
-    uint32_t *stamp = left + tiles, *list = stamp + tiles;
-    uint64_t *work = sum ? reinterpret_cast<uint64_t *>(sum)
-                         : reinterpret_cast<uint64_t *>(ws + head + per_tile);
-    const uint64_t unit = 1ull << frac_bits;
-
-    hdem_event_timer<4> phases(ctx, stats != nullptr);
-    if (int rc = phases.start()) return rc;
-    HDEM_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(dinfacc_counters), ctx->stream));
-    const dim3 grid((unsigned)tiles);
-
-    phases.mark(0);
-    hipLaunchKernelGGL(dinfacc_classify_kernel, grid, dim3(NT), 0, ctx->stream, words, H, W,
-                       tiles_x, work, left, stamp, list, cnt);
-    phases.mark(1);
-    // one host read per round: the length of the round's list, which is its grid
-    dinfacc_counters host = {};
-    int64_t rounds = 0, visits = 0;
-    for (;; ++rounds) {
-        HDEM_HIP_CHECK(hipGetLastError());
-        HDEM_HIP_CHECK(hipMemcpyAsync(&host, cnt, sizeof(host), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-        HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (host.bad || host.outside || !host.listed || rounds > cells) break;
-        visits += host.listed;
-        hipLaunchKernelGGL(dinfacc_visit_kernel, dim3(host.listed), dim3(NT), 0, ctx->stream,
-                           words, work, H, W, tiles_x, list, (uint32_t)rounds, unit, stamp, left);
-        HDEM_HIP_CHECK(hipMemsetAsync(&cnt->listed, 0, sizeof(cnt->listed), ctx->stream));
-        hipLaunchKernelGGL(dinfacc_schedule_kernel, dim3((unsigned)((tiles + NT - 1) / NT)),
-                           dim3(NT), 0, ctx->stream, g.tiles_y, tiles_x, (uint32_t)rounds + 1,
-                           left, stamp, list, cnt);
-    }
-    phases.mark(2);
-    const bool refused = host.bad || host.outside;
-    if (!refused) {
-        hipLaunchKernelGGL(dinfacc_final_kernel, grid, dim3(NT), 0, ctx->stream, work, H, W,
-                           tiles_x, std::ldexp(1.0, -frac_bits), sum, value, cnt);
-        HDEM_HIP_CHECK(hipGetLastError());
-        HDEM_HIP_CHECK(hipMemcpyAsync(&host, cnt, sizeof(host), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-    }
-    phases.mark(3);
-    HDEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-
-    st.rounds = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
-    st.tile_visits = visits;
-    st.split_cells = (int64_t)host.split;
-    st.terminal_cells = (int64_t)host.terminal;
-    st.invalid = (int64_t)host.bad;
-    st.outside = (int64_t)host.outside;
-    st.unresolved = (int64_t)host.unresolved;
-    st.tile_h = TS;
-    st.tile_w = TS;
-    phases.read(&st.ms_classify, &st.ms_relax, &st.ms_final);
-    d8_publish(stats, st);
-    HDEM_REQUIRE(!host.bad, HDEM_ERR_BAD_ARG,
-                 "invalid D-infinity word in %llu cells: the facet is 0 ... 8 in bits 16-19, q is "
-                 "0 ... 32768 in bits 0-15 (0 with facet 0), every other bit is 0",
-                 host.bad);
-    HDEM_REQUIRE(!host.outside, HDEM_ERR_BAD_ARG,
-                 "D-infinity words send flow outside the raster in %llu cells", host.outside);
-    HDEM_REQUIRE(!host.unresolved, HDEM_ERR_BAD_ARG,
-                 "D-infinity words form a cycle: %llu cells never resolve", host.unresolved);
-    return HDEM_OK;
+    hdem_dinfsum_stats st = {};
+    d8_publish(stats, unweighted_stats(st));
+    const dinfacc_call a = {words, H, W, nullptr, 0, frac_bits, sum, value};
+    const int rc = dinfacc_dev(ctx, a, g, stats != nullptr, &st);
+    d8_publish(stats, unweighted_stats(st));
+    return rc;
 }
 
 extern "C" int hdem_dinfacc_u32(hdem_ctx *ctx, const uint32_t *words, int H, int W, int frac_bits,
@@ -644,6 +827,47 @@ extern "C" int hdem_dinfacc_u32(hdem_ctx *ctx, const uint32_t *words, int H, int
         if (int rc = dvalue.alloc(ctx, n * 4)) return rc;
     if (int rc = hdem_dinfacc_u32_dev(ctx, dwords.as<const uint32_t>(), H, W, frac_bits,
                                       dsum.as<int64_t>(), dvalue.as<float>(), flags, stats))
+        return rc;
+    if (sum)
+        if (int rc = dsum.download(sum, n * 8)) return rc;
+    return value ? dvalue.download(value, n * 4) : HDEM_OK;
+}
+
+extern "C" int hdem_dinfsum_u32_dev(hdem_ctx *ctx, const uint32_t *words, int H, int W,
+                                    const void *weights, int weight_type, int frac_bits,
+                                    int64_t *sum, float *value, int flags,
+                                    hdem_dinfsum_stats *stats)
+{
+    const dinfacc_call a = {words, H, W, weights, weight_type, frac_bits, sum, value};
+    d8_grid g;
+    if (int rc = dinfsum_check(ctx, a, flags, stats, &g)) return rc;
+    HDEM_HIP_CHECK(hipSetDevice(ctx->device));
+    hdem_dinfsum_stats st = {};
+    d8_publish(stats, st);
+    const int rc = dinfacc_dev(ctx, a, g, stats != nullptr, &st);
+    d8_publish(stats, st);
+    return rc;
+}
+
+extern "C" int hdem_dinfsum_u32(hdem_ctx *ctx, const uint32_t *words, int H, int W,
+                                const void *weights, int weight_type, int frac_bits, int64_t *sum,
+                                float *value, int flags, hdem_dinfsum_stats *stats)
+{
+    const dinfacc_call a = {words, H, W, weights, weight_type, frac_bits, sum, value};
+    d8_grid g;
+    if (int rc = dinfsum_check(ctx, a, flags, stats, &g)) return rc;
+    HDEM_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)H * W;
+    hdem_dbuf dwords, dweights, dsum, dvalue;
+    if (int rc = dwords.upload(ctx, words, n * 4)) return rc;
+    if (int rc = dweights.upload(ctx, weights, n * weight_bytes(weight_type))) return rc;
+    if (sum)
+        if (int rc = dsum.alloc(ctx, n * 8)) return rc;
+    if (value)
+        if (int rc = dvalue.alloc(ctx, n * 4)) return rc;
+    if (int rc = hdem_dinfsum_u32_dev(ctx, dwords.as<const uint32_t>(), H, W, dweights.p,
+                                      weight_type, frac_bits, dsum.as<int64_t>(),
+                                      dvalue.as<float>(), flags, stats))
         return rc;
     if (sum)
         if (int rc = dsum.download(sum, n * 8)) return rc;

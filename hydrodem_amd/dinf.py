@@ -1,11 +1,12 @@
 """
-D-infinity flow direction and accumulation (``hdem_dinf_f32`` / ``hdem_dinfacc_u32`` and their
-``_dev`` twins): the binding, written once for host arrays and device rasters with the two
-sides of :mod:`hydrodem_amd.backend`, and the host helpers for the D-infinity word.
+D-infinity flow direction, accumulation and weighted accumulation (``hdem_dinf_f32`` /
+``hdem_dinfacc_u32`` / ``hdem_dinfsum_u32`` and their ``_dev`` twins): the binding, written once
+for host arrays and device rasters with the two sides of :mod:`hydrodem_amd.backend`, and the
+host helpers for the D-infinity word.
 
 The word, one uint32 per cell: ``q`` in bits 0-15 (0 ... 32768, the share of the diagonal
 receiver in units of 2^-15), the facet in bits 16-19 (0: no outflow; 1 ... 8 as in Tarboton 1997,
-``FACETS``).  ``include/hydrodem_hip.h`` (A20, A21) has the contract.
+``FACETS``).  ``include/hydrodem_hip.h`` (A20, A21, A22) has the contract.
 """
 # pylint: disable=protected-access,too-many-arguments
 
@@ -16,6 +17,7 @@ import math
 import numpy as np
 
 from . import backend
+from .flowsum import WEIGHT_TYPES, Q_MAX
 
 Q_ONE = 32768               # q of "everything to the diagonal receiver"
 # facet -> ((dy, dx) of the cardinal receiver e1, of the diagonal receiver e2, ac, af); north is
@@ -30,6 +32,7 @@ D8_WORDS = {1: (1, 0), 64: (2, 0), 16: (4, 0), 4: (6, 0),
 D8_EIGHTHS = {1: 0, 128: 1, 64: 2, 32: 3, 16: 4, 8: 5, 4: 6, 2: 7}
 OUTPUTS = (("sum", np.int64), ("value", np.float32))    # in the order of the C ABI's pointers
 EXTRAS = ("angle", "slope")                             # float32, optional, of the direction
+TOTAL_LIMIT = 2 ** 48       # the quantised weights of a raster sum to less than this
 
 
 # ---------------------------------------------------------------------------
@@ -143,6 +146,50 @@ def dinfacc_args(words, frac_bits=16, want=("value",)):
     return frac_bits, want
 
 
+def quantise(weights, frac_bits=16):
+    """q(w) as the weighted accumulation computes it, int64: ``w << frac_bits`` for uint8 and
+    uint32 weights, ``rint(float64(w) * 2^frac_bits)`` for float32 ones (the product is exact:
+    one rounding, to nearest even), 0 for a NaN.  Range checks are the caller's."""
+    weights = np.asarray(weights)
+    if weights.dtype != np.float32:
+        return weights.astype(np.int64) << np.int64(frac_bits)
+    scaled = np.rint(weights.astype(np.float64) * 2.0 ** frac_bits)
+    return np.where(np.isnan(scaled), 0.0, scaled).astype(np.int64)
+
+
+def dinfsum_args(words, weights, frac_bits=16, want=("value",)):
+    """The checks of the weighted accumulation that need no device: ``words`` and ``weights`` are
+    anything with ``dtype`` and ``shape``.  Returns the weight type and ``frac_bits`` for the C
+    call and ``want`` as a tuple in the ABI's order."""
+    if words is None:
+        raise ValueError("weighted D-infinity flow accumulation needs the words it routes along")
+    shape = backend._check(words, np.uint32, "weighted D-infinity flow accumulation takes",
+                           "uint32 D-infinity words",
+                           flat="weighted D-infinity flow accumulation takes")
+    if weights is None:
+        raise ValueError("weighted D-infinity flow accumulation needs the weights it sums")
+    if np.dtype(weights.dtype) not in WEIGHT_TYPES:
+        raise ValueError("the weights are float32, uint32 or uint8, got "
+                         f"{np.dtype(weights.dtype)}")
+    backend._check(weights, None, "the weights are", like=("the words", shape))
+    most = 30 if np.dtype(weights.dtype) == np.float32 else 16
+    if isinstance(frac_bits, bool) or not isinstance(frac_bits, (int, np.integer)) or \
+            not 0 <= int(frac_bits) <= most:
+        raise ValueError(f"frac_bits is an integer in 0 ... {most} for {np.dtype(weights.dtype)} "
+                         f"weights, got {frac_bits!r}")
+    if isinstance(want, str):
+        want = (want,)
+    names = [n for n, _ in OUTPUTS]
+    unknown = [w for w in want if w not in names]
+    if unknown:
+        raise ValueError(f"unknown D-infinity accumulation outputs {unknown}: choose among "
+                         f"{names}")
+    want = tuple(n for n in names if n in want)
+    if not want:
+        raise ValueError(f"no output wanted: choose among {names}")
+    return WEIGHT_TYPES[np.dtype(weights.dtype)], int(frac_bits), want
+
+
 # ---------------------------------------------------------------------------
 # the calls
 # ---------------------------------------------------------------------------
@@ -212,3 +259,43 @@ def dinfacc(words, frac_bits=16, want=("value",)):
     """D-infinity flow accumulation of host arrays (``hdem_dinfacc_u32``; see
     :func:`dinfacc_dev`): ``{name: ndarray}`` and the stats dict."""
     return _dinfacc(backend._HOST, words, frac_bits, want, None)
+
+
+def _dinfsum(side, words, weights, frac_bits, want, out):
+    words = side.take("words", words, required=True)
+    weights = side.take("weights", weights, required=True)
+    weight_type, frac_bits, want = dinfsum_args(words, weights, frac_bits, want)
+    out = dict(out or {})
+    for name, dtype in OUTPUTS:
+        if name in out:
+            if name not in want:
+                raise ValueError(f"out has {name}, which is not wanted")
+            backend._check(out[name], dtype, f"out[{name!r}] is",
+                           like=("the words", tuple(words.shape)))
+    c = side.context(words)
+    st = backend._DInfSumStats()
+    with contextlib.ExitStack() as stack:
+        outs = {name: side.result(stack, out.get(name), words.shape, dtype, c)
+                for name, dtype in OUTPUTS if name in want}
+        side.call(c, "hdem_dinfsum_u32", side.address(words), *words.shape,
+                  side.address(weights), weight_type, frac_bits,
+                  *[side.address(outs.get(name)) for name, _ in OUTPUTS], 0, ctypes.byref(st))
+    return outs, st.as_dict()
+
+
+def dinfsum_dev(words, weights, frac_bits=16, want=("value",), out=None):
+    """Weighted D-infinity flow accumulation of a uint32 word raster (``hdem_dinfsum_u32_dev``):
+    ``A[c] = q(w[c])`` plus the shares its donors send it, in integers.  ``weights``: a uint8,
+    uint32 (``q = w << frac_bits``, ``frac_bits`` 0 ... 16) or float32 raster
+    (``q = rint(w * 2^frac_bits)``, ``frac_bits`` 0 ... 30).  ``want``: ``sum`` (int64 ``A``)
+    and / or ``value`` (float32 ``A * 2^-frac_bits``, in weight units).  ``out``:
+    ``{name: DeviceRaster}`` to write into.  Returns ``{name: DeviceRaster}`` and the stats dict
+    (the accumulation's, ``nan_weights``, ``bad_weights``, ``total``).  Synchronises once per
+    round."""
+    return _dinfsum(backend._DEVICE, words, weights, frac_bits, want, out)
+
+
+def dinfsum(words, weights, frac_bits=16, want=("value",)):
+    """Weighted D-infinity flow accumulation of host arrays (``hdem_dinfsum_u32``; see
+    :func:`dinfsum_dev`): ``{name: ndarray}`` and the stats dict."""
+    return _dinfsum(backend._HOST, words, weights, frac_bits, want, None)

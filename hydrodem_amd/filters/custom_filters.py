@@ -27,8 +27,9 @@ New operators (the reference has neither): ``SinkFill``,
 ``D8FlowDirection``, ``ResolveFlats``, ``FlowAccumulation``, ``WeightedFlowAccumulation``,
 ``UpstreamExtreme``, ``BreachDepressions``, ``Watersheds``, ``FlowDistance``,
 ``FlowPathSum``, ``FlowPathExtreme``, ``HeightAboveDrainage``, ``UpstreamFlowLength``,
-``StreamOrder``, ``StreamNetwork``, ``DInfFlowDirection``, ``DInfFlowAccumulation`` and the
-chains ``DemToHAND``, ``DemToStreamOrder``, ``DemToStreamNetwork`` and ``DemToDInfArea``, shaped
+``StreamOrder``, ``StreamNetwork``, ``DInfFlowDirection``, ``DInfFlowAccumulation``,
+``WeightedDInfFlowAccumulation``, ``AreaWetnessIndex`` and the chains ``DemToHAND``,
+``DemToStreamOrder``, ``DemToStreamNetwork``, ``DemToDInfArea`` and ``DemToDInfWetness``, shaped
 like every other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
@@ -2139,6 +2140,220 @@ class DemToDInfArea(ComposedFilter):  # pylint: disable=too-few-public-methods,t
                 self.filled, self.codes, self.words = filled, codes, words
                 stack.pop_all()                     # the caller's to free from here on
             return outs[self.output]
+
+
+class WeightedDInfFlowAccumulation(Filter):  # pylint: disable=too-few-public-methods
+    """Weighted D-infinity flow accumulation (new operator; TauDEM ``areadinf -wg``).  Input: a
+    uint32 H x W raster of D-infinity words as ``DInfFlowDirection`` returns them.  ``weights``:
+    an H x W NumPy array or ``DeviceRaster`` of uint8, uint32 or float32 (float64 is refused, not
+    narrowed).  Every cell's weight is quantised to an integer ``q``: ``w << frac_bits`` for the
+    integer types (``frac_bits`` 0 ... 16: a cell that splits an integer load still needs
+    resolution below one unit), ``rint(float64(w) * 2^frac_bits)`` for float32 (``frac_bits``
+    0 ... 30).  ``A[c] = q[c] + sum(share(d -> c))`` with the shares of
+    ``DInfFlowAccumulation``, in integers: every unit of every weight arrives at a cell without
+    outflow, and the result is identical from run to run.
+
+    ``output``: ``"value"`` float32 ``float32(float64(A) * 2^-frac_bits)``, in weight units;
+    ``"sum"`` int64 ``A``.
+
+    A NaN weight contributes 0 (``stats["nan_weights"]`` counts them).  ``ValueError`` for
+    operands of another type, dtype or shape, ``frac_bits`` out of range for the weights, an
+    unknown ``output`` (all before the device is touched), for a negative or infinite weight, a
+    quantised weight above 2^31 - 1, quantised weights that sum to 2^48 or more (so that no
+    share can overflow), an invalid word, a receiver outside the raster, words that form a
+    cycle and more than 2^32 - 1 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        those of ``DInfFlowAccumulation``, nan_weights, bad_weights and total (the sum of the
+        quantised weights: what the cells without outflow hold between them) of the last call.
+    """
+
+    auto_device = False     # the input is uint32 words, not a float32 raster
+    WEIGHT_TYPES = (np.uint8, np.uint32, np.float32)
+    OUTPUTS = {name: np.dtype(dtype) for name, dtype in _dinf.OUTPUTS}
+
+    def __init__(self, weights, frac_bits=16, output="value"):
+        if weights is None:
+            raise ValueError("WeightedDInfFlowAccumulation needs the weights it sums")
+        self.weights = _Given(weights, "weights", self.WEIGHT_TYPES).value
+        if not isinstance(output, str) or output not in self.OUTPUTS:
+            raise ValueError(f"output is one of {list(self.OUTPUTS)}, got {output!r}")
+        self.frac_bits, self.output = frac_bits, output
+        self.dtype = self.OUTPUTS[output]
+        self.stats = {}
+        # everything but the shapes, on 1 x 1 stand-ins
+        _dinf.dinfsum_args(np.empty((1, 1), np.uint32), _Given(self.weights).stand_in(),
+                           frac_bits, output)
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _dinf.dinfsum_args(image_to_filter, self.weights, self.frac_bits, self.output)
+        outs, self.stats = _dinf.dinfsum(image_to_filter, _Given(self.weights).host(),
+                                         self.frac_bits, self.output)
+        return outs[self.output]
+
+    def apply_device(self, raster):
+        _dinf.dinfsum_args(raster, self.weights, self.frac_bits, self.output)
+        with _Given(self.weights).device(raster.ctx) as weights:
+            outs, self.stats = _dinf.dinfsum_dev(raster, weights, self.frac_bits, self.output)
+        return outs[self.output]
+
+
+class AreaWetnessIndex(Filter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """The topographic wetness index ``ln(a / max(tan b, min_slope))`` of a float32 DEM and a
+    float32 catchment ``area`` in cells -- the ``value`` of ``DInfFlowAccumulation`` or
+    ``WeightedDInfFlowAccumulation`` (TauDEM ``twi`` on ``sca`` and ``slp``).  ``a`` is the area
+    times ``sqrt(dx dy)``; ``tan b`` is ``given_slope`` where one is passed (float32, the D-infinity
+    ``slope``), else Horn's tangent of the DEM.  The arithmetic is ``TerrainAttributes``'s, with
+    ``area`` where that has ``float32(accumulation)``.
+
+    ``want`` names outputs of ``hydrodem_amd.terrain.TERRAIN_OUTPUTS`` (not ``d8_slope``); the
+    first is returned, and with ``keep_partial_results=True`` the same launch writes the others
+    and leaves them in the attributes of their names, as ``TerrainAttributes`` does.  ``area``
+    and ``given_slope`` are arrays or ``DeviceRaster``s of the DEM's shape.  A NaN area gives
+    NaN; zero and negative areas go through the arithmetic as they are
+    (``stats["nonpositive_area"]`` counts them).
+
+    ``ValueError`` for operands of another type, dtype or shape, unknown outputs, ``twi`` or
+    ``spi`` without the area, a ``cellsize``, ``z_factor`` or ``min_slope`` that is not finite
+    and positive: all before the device is touched.
+    """
+
+    auto_device = True      # device form == host form for a float32 raster
+
+    def __init__(self, area, given_slope=None, cellsize=1.0, z_factor=1.0, min_slope=1e-3,
+                 want=("twi",), keep_partial_results=False):
+        self.want = (want,) if isinstance(want, str) else tuple(want)
+        self.cellsize, self.z_factor, self.min_slope = cellsize, z_factor, min_slope
+        self.area = _Given(area, "area", (np.float32,)).value
+        self.given_slope = _Given(given_slope, "given_slope", (np.float32,)).value
+        self.slope = "horn" if given_slope is None else "given"
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        for name in _terrain.TERRAIN_OUTPUTS:
+            setattr(self, name, None)
+        # everything but the shapes, on 1 x 1 stand-ins
+        self._args(np.zeros((1, 1), np.float32), _Given(self.area).stand_in(),
+                   _Given(self.given_slope).stand_in())
+
+    def _args(self, dem, area, given_slope):
+        return _terrain.terrain_area_args(dem, self.want, self.cellsize, self.z_factor, area,
+                                          given_slope, None, self.min_slope, self.slope)
+
+    def _run(self, run, dem, area, given_slope):
+        want = self.want if self.keep_partial_results else self.want[:1]
+        outs, self.stats = run(dem, want, self.cellsize, self.z_factor, area, given_slope, None,
+                               self.min_slope, self.slope)
+        for name in _terrain.TERRAIN_OUTPUTS:
+            setattr(self, name, outs.get(name) if name != self.want[0] else None)
+        return outs[self.want[0]]
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        self._args(image_to_filter, self.area, self.given_slope)
+        return self._run(_terrain.terrain_area, image_to_filter, _Given(self.area).host(),
+                         _Given(self.given_slope).host())
+
+    def apply_device(self, raster):
+        self._args(raster, self.area, self.given_slope)
+        with _Given(self.area).device(raster.ctx) as area, \
+                _Given(self.given_slope).device(raster.ctx) as given_slope:
+            return self._run(_terrain.terrain_area_dev, raster, area, given_slope)
+
+
+class DemToDInfWetness(ComposedFilter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """A float32 DEM to its D-infinity wetness index in one device-resident chain:
+    ``SinkFill(epsilon)`` and ``D8FlowDirection`` (one call), ``DInfFlowDirection`` on the
+    **filled** DEM with the chain's D8 codes as fallback, ``DInfFlowAccumulation`` -- or
+    ``WeightedDInfFlowAccumulation`` when ``weights`` (uint8, uint32 or float32, array or
+    ``DeviceRaster``) is given -- and ``AreaWetnessIndex`` on the filled DEM with that area.
+    ``slope="dinf"`` takes the D-infinity slope of the direction launch as ``tan b``,
+    ``slope="horn"`` Horn's tangent.  Nothing is downloaded in between.  ``flats`` as in
+    ``DemToHAND``; ``cellsize`` is a number or ``(dx, dy)`` as in ``DInfFlowDirection``.
+
+    ``stats`` maps ``SinkFill``, ``DInfFlowDirection``, ``DInfFlowAccumulation`` (or
+    ``WeightedDInfFlowAccumulation``) and ``AreaWetnessIndex`` (and ``ResolveFlats``) to the
+    stats of their stage.  With ``keep_partial_results=True`` the last call leaves ``filled``,
+    ``codes``, ``words``, ``area`` (and ``dinf_slope`` with ``slope="dinf"``): host arrays after
+    ``apply``, device rasters (the caller's to free) after ``apply_device``; otherwise they are
+    ``None``.  A failing stage leaves nothing allocated."""
+
+    SLOPES = ("dinf", "horn")
+    KEPT = ("filled", "codes", "words", "area", "dinf_slope")
+
+    def __init__(self, *, epsilon=1e-3, flats="keep", cellsize=1.0, frac_bits=16,
+                 min_slope=1e-3, slope="dinf", weights=None, keep_partial_results=False):
+        super().__init__()
+        self.flats = _check_flats(flats)
+        if slope not in self.SLOPES:
+            raise ValueError(f"slope is 'dinf' or 'horn', got {slope!r}")
+        self.weights = _Given(weights, "weights",
+                              WeightedDInfFlowAccumulation.WEIGHT_TYPES).value
+        dx, dy = _dinf.cellsizes(cellsize)
+        # the checks of the later stages' operands, on stand-ins of the types the chain makes
+        words, area = np.zeros((1, 1), np.uint32), np.zeros((1, 1), np.float32)
+        if weights is None:
+            _dinf.dinfacc_args(words, frac_bits, "value")
+        else:
+            _dinf.dinfsum_args(words, _Given(self.weights).stand_in(), frac_bits, "value")
+        _terrain.terrain_area_args(area, ("twi",), (dy, dx), 1.0, area,
+                                   area if slope == "dinf" else None, None, min_slope,
+                                   "given" if slope == "dinf" else "horn")
+        self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection(),
+                        DInfFlowDirection(cellsize=cellsize)]
+        self.cellsize, self.frac_bits, self.min_slope = cellsize, frac_bits, min_slope
+        self.slope, self.keep_partial_results = slope, keep_partial_results
+        self.stats = {}
+        for name in self.KEPT:
+            setattr(self, name, None)
+
+    def _kept(self):
+        return tuple(n for n in self.KEPT if n != "dinf_slope" or self.slope == "dinf")
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("DemToDInfWetness", image_to_filter, np.float32, "a float32 DEM")
+        if self.weights is not None:
+            _dinf.dinfsum_args(np.empty(image_to_filter.shape, np.uint32), self.weights,
+                               self.frac_bits, "value")
+        return _through_device(self, image_to_filter,
+                               self._kept() if self.keep_partial_results else ())
+
+    def apply_device(self, raster):
+        _check_raster("DemToDInfWetness", raster, np.float32, "a float32 DEM")
+        fill, _, direct = self.filters
+        for name in self.KEPT:
+            setattr(self, name, None)
+        dx, dy = _dinf.cellsizes(self.cellsize)
+        given = self.slope == "dinf"
+        with contextlib.ExitStack() as stack:
+            filled, codes, resolve_stats = _fill_d8(stack, raster, fill, self.flats)
+            words, extras, direct.stats = _dinf.dinf_dev(filled, self.cellsize, codes,
+                                                         ("slope",) if given else ())
+            stack.enter_context(words)
+            dinf_slope = stack.enter_context(extras["slope"]) if given else None
+            if self.weights is None:
+                stage = "DInfFlowAccumulation"
+                outs, acc_stats = _dinf.dinfacc_dev(words, self.frac_bits, "value")
+            else:
+                stage = "WeightedDInfFlowAccumulation"
+                with _Given(self.weights).device(raster.ctx) as weights:
+                    outs, acc_stats = _dinf.dinfsum_dev(words, weights, self.frac_bits, "value")
+            area = stack.enter_context(outs["value"])
+            outs, stats = _terrain.terrain_area_dev(
+                filled, ("twi",), (dy, dx), 1.0, area, dinf_slope, None, self.min_slope,
+                "given" if given else "horn")
+            self.stats = {"SinkFill": fill.stats, "DInfFlowDirection": direct.stats,
+                          stage: acc_stats, "AreaWetnessIndex": stats}
+            if resolve_stats is not None:
+                self.stats["ResolveFlats"] = resolve_stats
+            if self.keep_partial_results:
+                self.filled, self.codes, self.words, self.area = filled, codes, words, area
+                self.dinf_slope = dinf_slope
+                stack.pop_all()                     # the caller's to free from here on
+            return outs["twi"]
 
 
 class DemToStreamOrder(ComposedFilter):  # pylint: disable=too-few-public-methods

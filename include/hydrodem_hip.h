@@ -1452,6 +1452,108 @@ int hdem_dinfacc_u32_dev(hdem_ctx *ctx, const uint32_t *words, int H, int W, int
                          int64_t *sum, float *value, int flags,
                          hdem_dinfacc_stats *stats);   /* device pointers */
 
+/* ---- A22  WeightedDInfFlowAccumulation.apply  (new operator: weighted D-infinity accumulation) ----
+ * words: uint32 H x W, the D-infinity words of A20, validated exactly as A21 validates them (the
+ * same refusals, the same counts).  weights is H x W of weight_type (hdem_flowsum_weight_type):
+ *   HDEM_FLOWSUM_F32                    q(w) = (int64)rint((double)w * 2^frac_bits), frac_bits
+ *                                       0 ... 30: the exact double product rounded once, to
+ *                                       nearest even (A13's rule); -0.0 counts as 0
+ *   HDEM_FLOWSUM_U8, HDEM_FLOWSUM_U32   q(w) = w << frac_bits, frac_bits 0 ... 16.  A deliberate
+ *                                       difference from A16, which takes integer weights at
+ *                                       frac_bits 0 only: a D-infinity cell splits its load, so
+ *                                       an integer load still needs resolution below one unit.
+ * A NaN weight contributes 0 and is counted in stats->nan_weights.  A negative or infinite
+ * weight, and any q(w) > 2^31 - 1, is refused with their count (stats->bad_weights).
+ * total = sum of q(w) over the raster is summed exactly in uint64 while the words are classified
+ * (fewer than 2^32 cells, each below 2^31: no overflow) and total >= 2^48 is refused with the
+ * total in the text.  That is what keeps the share product below 2^63: a cell's A is a sum of
+ * parts of distinct cells' q, so A <= total < 2^48, and q of a word is <= 2^15.  total is also the
+ * conservation check: the sum of A over the cells with facet 0 equals it.
+ *   A[c] = q(w[c]) + sum over the donors d of c of share(d -> c)
+ *   to_diag(d) = (A[d] * q[d]) >> 15   (uint64)        to_card(d) = A[d] - to_diag(d)
+ * as in A21.  Integer adds only: identical from run to run, whatever the schedule, and between
+ * the host and device forms.  With uint8 weights of 1 the result is A21's at the same frac_bits.
+ *   sum     int64, A
+ *   value   float32, (float)((double)A * 2^-frac_bits)
+ * At least one of the two is wanted.  sum may serve as the working raster, as in A21: the
+ * kernels are A21's, instantiated with the cell's own term read from its working word (classify
+ * writes q(w) there, bit 63 clear) instead of the constant U.
+ * HDEM_ERR_BAD_ARG before any launch: a null words or weights, neither output, an unknown
+ * weight_type, frac_bits out of range for the type, unknown flags, more than 2^32 - 1 cells, an
+ * output that overlaps words, weights or the other output.  After classify, in one read of the
+ * counters and in this order: invalid words, receivers outside the raster, weights out of range,
+ * a total of 2^48 or more.  After the last round: words that form a cycle.  The outputs are
+ * unspecified then.
+ * Workspace and synchronisation as A21.  stats may be NULL; otherwise the caller sets
+ * stats->struct_size = sizeof(hdem_dinfsum_stats) first (104 bytes in this version; a shorter
+ * struct is filled as far as it goes).  The struct opens with the fields of hdem_dinfacc_stats.
+ * rounds and tile_visits depend on the schedule; every other count does not. */
+typedef struct hdem_dinfsum_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_dinfsum_stats), set by the caller            */
+    int32_t rounds;          /* rounds of tile visits that had work                          */
+    int64_t tile_visits;     /* workgroups launched over all rounds                          */
+    int64_t split_cells;     /* cells with two receivers (0 < q < 32768)                     */
+    int64_t terminal_cells;  /* cells with facet 0                                           */
+    int64_t invalid;         /* invalid words: refused                                       */
+    int64_t outside;         /* cells with a receiver outside the raster: refused            */
+    int64_t unresolved;      /* cells that never became final (a cycle): refused             */
+    int32_t tile_h, tile_w;
+    float ms_classify;       /* (HIP events; profiling)                                      */
+    float ms_relax;          /* all rounds, the host reads included                          */
+    float ms_final;
+    int32_t reserved;        /* 0                                                            */
+    int64_t nan_weights;     /* NaN weights: each contributed 0                              */
+    int64_t bad_weights;     /* negative, infinite or above 2^31 - 1 once quantised: refused */
+    uint64_t total;          /* the sum of q(w) over the raster; >= 2^48: refused            */
+} hdem_dinfsum_stats;        /* sizeof == 104 */
+int hdem_dinfsum_u32(hdem_ctx *ctx, const uint32_t *words, int H, int W, const void *weights,
+                     int weight_type, int frac_bits, int64_t *sum, float *value, int flags,
+                     hdem_dinfsum_stats *stats);       /* host pointers, synchronous */
+int hdem_dinfsum_u32_dev(hdem_ctx *ctx, const uint32_t *words, int H, int W, const void *weights,
+                         int weight_type, int frac_bits, int64_t *sum, float *value, int flags,
+                         hdem_dinfsum_stats *stats);   /* device pointers */
+
+/* ---- A23  AreaWetnessIndex.apply  (new operator: A14 on a float32 catchment area) ----
+ * A sibling of A14: the same launch, edge rule, order of float32 operations and eight outputs.
+ * Two inputs differ.
+ * area (float32 H x W, in place of acc): the catchment area in cells, e.g. the value output of
+ * A21 or A22.   a = area * (float)sqrt(dx * dy).   A NaN area gives NaN twi and spi.  Zero and
+ * negative areas are not refused: they go through the IEEE arithmetic as they are (twi of a
+ * zero area is -inf, of a negative one NaN) and are counted in stats->nonpositive_area.  With an
+ * integer-valued area below 2^24 the call writes the bytes A14 writes for the uint32 acc of the
+ * same values.
+ * given_slope (float32 H x W, optional) with HDEM_TERRAIN_TWI_GIVEN: twi and spi take
+ * t = given_slope[c] as it is (the slope output of A20; NaN where the dem is NaN, as every
+ * output there).  The floor applies as in A14,
+ * t < min_slope ? min_slope : t, a NaN t stays NaN, and floored_cells counts.  The flag excludes
+ * HDEM_TERRAIN_TWI_D8; the flag without the raster and the raster without the flag are refused.
+ * twi and spi need area; d8_slope and HDEM_TERRAIN_TWI_D8 need d8.  Everything else -- refusals,
+ * exactness, subsets of outputs, the synchronisation -- is A14's.  stats may be NULL; otherwise
+ * the caller sets stats->struct_size = sizeof(hdem_terrain_area_stats) first (48 bytes in this
+ * version; a shorter struct is filled as far as it goes). */
+#define HDEM_TERRAIN_TWI_GIVEN 2    /* twi and spi take given_slope as their t */
+typedef struct hdem_terrain_area_stats {
+    uint32_t struct_size;     /* in: sizeof(hdem_terrain_area_stats), set by the caller       */
+    float ms_total;           /* the launch (HIP events; profiling)                           */
+    int64_t nan_cells;        /* cells whose dem is NaN                                       */
+    int64_t flat_cells;       /* cells with dzdx == 0 && dzdy == 0 (aspect -1)                */
+    int64_t floored_cells;    /* cells whose t was below min_slope (counted when twi is wanted) */
+    int64_t invalid_codes;    /* cells whose d8 byte is no D8 code: refused                   */
+    int64_t nonpositive_area; /* cells whose area is <= 0 (counted when twi or spi is wanted) */
+} hdem_terrain_area_stats;    /* sizeof == 48 */
+int hdem_terrain_area_f32(hdem_ctx *ctx, const float *dem, int H, int W, const float *area,
+                          const float *given_slope, const uint8_t *d8, double dx, double dy,
+                          double z_factor, double min_slope, float *dzdx, float *dzdy,
+                          float *tangent, float *degrees, float *aspect, float *d8_slope,
+                          float *twi, float *spi, int flags,
+                          hdem_terrain_area_stats *stats);    /* host pointers, synchronous */
+int hdem_terrain_area_f32_dev(hdem_ctx *ctx, const float *dem, int H, int W, const float *area,
+                              const float *given_slope, const uint8_t *d8, double dx, double dy,
+                              double z_factor, double min_slope, float *dzdx, float *dzdy,
+                              float *tangent, float *degrees, float *aspect, float *d8_slope,
+                              float *twi, float *spi, int flags,
+                              hdem_terrain_area_stats *stats);    /* device pointers */
+
 #ifdef __cplusplus
 }
 #endif
