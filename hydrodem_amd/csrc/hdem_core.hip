@@ -174,7 +174,23 @@ void *hdem_arena(hdem_ctx *ctx, size_t bytes)
 extern "C" int hdem_set_stream(hdem_ctx *ctx, void *hip_stream)
 {
     HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
-    ctx->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream;
+    const hipStream_t next = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream;
+    if (next == ctx->stream) return HDEM_OK;
+    // The arena, the Fourier scratch and plans, the fill workspace and the cached blocks stay
+    // with the context, and the operators that return without a host wait may still use them
+    // on the old stream: the new stream starts behind everything queued there.  No host wait.
+    // (An event of the pool the timers share, and it stays there: the wait is queued for the
+    // record made here, whatever the event records later.)
+    HDEM_HIP_CHECK(hipSetDevice(ctx->device));
+    if (ctx->event_pool.empty()) {
+        hipEvent_t fresh = nullptr;
+        HDEM_HIP_CHECK(hipEventCreate(&fresh));
+        ctx->event_pool.push_back(fresh);
+    }
+    const hipEvent_t ev = ctx->event_pool.back();
+    HDEM_HIP_CHECK(hipEventRecord(ev, ctx->stream));
+    HDEM_HIP_CHECK(hipStreamWaitEvent(next, ev, 0));
+    ctx->stream = next;
     return HDEM_OK;
 }
 

@@ -50,7 +50,12 @@ int hdem_device_count(int *count);
 int hdem_init(int device, hdem_ctx **ctx);    /* own stream + workspace     */
 int hdem_shutdown(hdem_ctx *ctx);
 /* Run on a caller-provided hipStream_t (e.g. torch's current stream);
- * NULL restores the context's own stream. */
+ * NULL restores the context's own stream.  When the stream changes, the new stream is
+ * ordered behind everything this context has queued on the old one (an event recorded there,
+ * hipStreamWaitEvent on the new stream; no host wait): the context's scratch -- the arena,
+ * the Fourier scratch and plans, the fill workspace -- goes with it, and an operator that
+ * returned without a host wait may still be using it.  Both streams must be alive at the
+ * call.  Setting the stream that is already in use does nothing. */
 int hdem_set_stream(hdem_ctx *ctx, void *hip_stream);
 int hdem_synchronize(hdem_ctx *ctx);
 

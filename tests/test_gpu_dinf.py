@@ -11,7 +11,6 @@ rounded to 15 bits, so two implementations a few ulp apart disagree only within 
 rounding boundary; a cell that differs is reported with both words.  The accumulation takes
 its words from the *reference* direction, so that question cannot reach it.
 """
-import contextlib
 import ctypes
 
 import numpy as np
@@ -26,6 +25,7 @@ from elevation_regimes import REGIMES, regime_raster
 from test_dinf import (accumulate_ref, counts_of, direction_ref, plane, random_dem, value_of)
 from test_flowacc import random_acyclic_codes, terminal_mask
 from test_gpu_flowacc import path_codes, spiral
+from test_gpu_scribble import Case, execute
 
 pytestmark = pytest.mark.gpu
 
@@ -428,51 +428,69 @@ def test_an_output_of_the_wrong_dtype_is_refused_and_the_c_entry_points_check_th
 # ---------------------------------------------------------------------------
 # poisoned scratch and output memory
 # ---------------------------------------------------------------------------
-def run_on_a_fresh_context(words, z, byte, own):
-    """One device call of each operator for all its outputs on a context of its own, with every
-    block the library hands out filled with ``byte`` first (``None``: no poison); ``own``: the
-    caller's poisoned rasters as ``out=``."""
-    ctx = backend.Context()
-    try:
-        with contextlib.ExitStack() as stack:
-            if byte is not None:
-                stack.enter_context(ctx.scribble(byte))
-            dw = stack.enter_context(DeviceRaster.from_host(words, dtype=np.uint32, ctx=ctx))
-            dz = stack.enter_context(DeviceRaster.from_host(z, dtype=F32, ctx=ctx))
-            out = {}
-            if own:
-                out = {name: stack.enter_context(DeviceRaster.empty(words.shape, dtype, ctx))
-                       for name, dtype in dinf.OUTPUTS + (("words", np.uint32),)}
-            host = {}
-            # the arena's working raster (value alone), then the caller's or the library's sum
-            alone, _ = dinf.dinfacc_dev(dw, 16, "value", {"value": out["value"]} if own else None)
-            host["alone"] = alone["value"].to_host()
-            if not own:
-                stack.enter_context(alone["value"])
-            dev, stats = dinf.dinfacc_dev(dw, 16, ("sum", "value"),
-                                          {k: out[k] for k in ("sum", "value")} if own else None)
-            made, extras, _ = dinf.dinf_dev(dz, 1.0, None, dinf.EXTRAS, out.get("words"))
-            for name, raster in {**dev, "words": made, **extras}.items():
-                if name not in out:
-                    stack.enter_context(raster)
-                else:
-                    assert raster is out[name]
-                host[name] = raster.to_host()
-            ctx.synchronize()
-        return host, schedule_free(stats)
-    finally:
-        ctx.close()
+def poison_words(shape, seed=33):
+    return {"words": random_acyclic_words(shape, seed=seed)}
+
+
+def poison_dem(shape, seed=33):
+    return {"z": random_dem(shape, seed=seed, nan=0.01)}
+
+
+def poison_run_acc(call, inp):
+    """The accumulation for ``value`` alone (the arena's working raster), then for both outputs
+    (the caller's or the library's sum as working raster)."""
+    words = inp["words"]
+    dw = call.up(words)
+    out = {name: call.out(words.shape, dtype) for name, dtype in dinf.OUTPUTS}
+    alone, _ = dinf.dinfacc_dev(dw, 16, "value", {"value": out["value"]} if call.own else None)
+    host = {"alone": alone["value"].to_host()}
+    if not call.own:
+        call.stack.enter_context(alone["value"])
+    dev, stats = dinf.dinfacc_dev(dw, 16, ("sum", "value"), out if call.own else None)
+    for name, raster in dev.items():
+        assert not call.own or raster is out[name]
+        host[name] = call.host(raster)
+    return host, schedule_free(stats)
+
+
+def poison_check_acc(inp, got):
+    assert np.array_equal(got["sum"], accumulate_ref(inp["words"]))
+    assert np.array_equal(got["alone"], got["value"])
+
+
+def poison_run_direction(call, inp):
+    """The direction for the words and both extras."""
+    dz = call.up(inp["z"])
+    made, extras, stats = dinf.dinf_dev(dz, 1.0, None, dinf.EXTRAS, call.out(dz.shape, np.uint32))
+    host = {name: call.host(raster) for name, raster in {"words": made, **extras}.items()}
+    return host, {k: v for k, v in stats.items() if not k.startswith("ms_")}
+
+
+def poison_check_direction(inp, got):
+    want_words, want_angle, want_slope, _ = direction_ref(inp["z"], 1.0, 1.0, None)
+    assert got["words"].dtype == np.uint32 and np.array_equal(got["words"], want_words)
+    assert np.array_equal(got["slope"].view(np.uint32), want_slope.view(np.uint32))
+    want32 = want_angle.astype(F32)
+    assert np.array_equal(got["angle"] < 0, want32 < 0)
+    assert int(ulps_apart(got["angle"], want32).max()) <= 1
+
+
+# (33, 257): a second 256-column tile of the direction kernel, one cell wide
+POISON_CASES = [Case("dinfacc", ((130, 197),), poison_words, poison_run_acc, poison_check_acc,
+                     True, frozenset()),
+                Case("dinf-direction", ((130, 197), (33, 257)), poison_dem, poison_run_direction,
+                     poison_check_direction, True, frozenset())]
 
 
 @pytest.mark.parametrize("own", [False, True], ids=["library_out", "callers_out"])
 def test_poisoned_memory_changes_no_byte(own):
-    words = random_acyclic_words((130, 197), seed=33)
-    z = random_dem((130, 197), seed=33, nan=0.01)
-    clean, clean_stats = run_on_a_fresh_context(words, z, None, own)
-    assert np.array_equal(clean["sum"], accumulate_ref(words))
-    assert np.array_equal(clean["alone"], clean["value"])
-    for byte in (0x00, 0xFF, 0x7F, 0x01):
-        got, stats = run_on_a_fresh_context(words, z, byte, own)
-        assert stats == clean_stats
-        for name, raster in clean.items():
-            assert got[name].tobytes() == raster.tobytes(), (name, hex(byte))
+    for entry in POISON_CASES:
+        inp = entry.build((130, 197))
+        clean, clean_stats = execute(entry, inp, None, own)
+        entry.check(inp, clean)
+        for byte in (0x00, 0xFF, 0x7F, 0x01):
+            got, stats = execute(entry, inp, byte, own)
+            assert stats == clean_stats
+            assert got.keys() == clean.keys()
+            for name, raster in clean.items():
+                assert got[name].tobytes() == raster.tobytes(), (entry.name, name, hex(byte))

@@ -7,7 +7,6 @@ every comparison is ``np.array_equal`` or byte equality.  The weights differ fro
 an own term that lands in the wrong cell shows; the shapes are those at which the tile structure
 of the accumulation can go wrong (tests/test_gpu_dinf.py) plus the two strips.
 """
-import contextlib
 import ctypes
 
 import numpy as np
@@ -21,6 +20,7 @@ from test_dinfsum import accumulate_weighted_ref, random_weights
 from test_flowacc import random_acyclic_codes, terminal_mask
 from test_gpu_dinf import random_acyclic_words, schedule_free
 from test_gpu_flowacc import path_codes
+from test_gpu_scribble import Case, execute
 
 pytestmark = pytest.mark.gpu
 
@@ -153,49 +153,46 @@ def test_two_runs_and_both_forms_give_identical_bytes():
 # ---------------------------------------------------------------------------
 # poisoned scratch and output memory
 # ---------------------------------------------------------------------------
-def run_on_a_fresh_context(words, weights, byte, own):
+def poison_inputs(shape, seed=33):
+    words = random_acyclic_words(shape, seed=seed)
+    return {"words": words, "weights": random_weights(words.shape, seed, F32, nan=0.02)}
+
+
+def poison_run(call, inp):
     """The device call for ``value`` alone (the arena's working raster) and for both outputs (the
-    caller's or the library's ``sum`` as working raster) on a context of its own, with every
-    block the library hands out filled with ``byte`` first (``None``: no poison)."""
-    ctx = backend.Context()
-    try:
-        with contextlib.ExitStack() as stack:
-            if byte is not None:
-                stack.enter_context(ctx.scribble(byte))
-            dw = stack.enter_context(DeviceRaster.from_host(words, dtype=np.uint32, ctx=ctx))
-            dq = stack.enter_context(DeviceRaster.from_host(weights, dtype=weights.dtype, ctx=ctx))
-            out = {}
-            if own:
-                out = {name: stack.enter_context(DeviceRaster.empty(words.shape, dtype, ctx))
-                       for name, dtype in dinf.OUTPUTS}
-            host = {}
-            alone, _ = dinf.dinfsum_dev(dw, dq, 16, "value", {"value": out["value"]} if own else None)
-            host["alone"] = alone["value"].to_host()
-            if not own:
-                stack.enter_context(alone["value"])
-            dev, stats = dinf.dinfsum_dev(dw, dq, 16, ("sum", "value"), out if own else None)
-            for name, raster in dev.items():
-                if own:
-                    assert raster is out[name]
-                else:
-                    stack.enter_context(raster)
-                host[name] = raster.to_host()
-            ctx.synchronize()
-        return host, {k: v for k, v in stats.items()
-                      if not k.startswith("ms_") and k not in ("rounds", "tile_visits")}
-    finally:
-        ctx.close()
+    caller's or the library's ``sum`` as working raster)."""
+    words = inp["words"]
+    dw, dq = call.up(words), call.up(inp["weights"])
+    out = {name: call.out(words.shape, dtype) for name, dtype in dinf.OUTPUTS}
+    alone, _ = dinf.dinfsum_dev(dw, dq, 16, "value", {"value": out["value"]} if call.own else None)
+    host = {"alone": alone["value"].to_host()}
+    if not call.own:
+        call.stack.enter_context(alone["value"])
+    dev, stats = dinf.dinfsum_dev(dw, dq, 16, ("sum", "value"), out if call.own else None)
+    for name, raster in dev.items():
+        assert not call.own or raster is out[name]
+        host[name] = call.host(raster)
+    return host, stats
+
+
+def poison_check(inp, got):
+    assert np.array_equal(got["sum"], accumulate_weighted_ref(inp["words"],
+                                                              dinf.quantise(inp["weights"], 16)))
+    assert np.array_equal(got["alone"], got["value"])
+
+
+# rounds, tile_visits: a tile reads what its neighbours write in the same launch
+POISON_CASE = Case("dinfsum", ((130, 197),), poison_inputs, poison_run, poison_check, True,
+                   frozenset(("rounds", "tile_visits")))
 
 
 @pytest.mark.parametrize("own", [False, True], ids=["library_out", "callers_out"])
 def test_poisoned_memory_changes_no_byte(own):
-    words = random_acyclic_words((130, 197), seed=33)
-    weights = random_weights(words.shape, 33, F32, nan=0.02)
-    clean, clean_stats = run_on_a_fresh_context(words, weights, None, own)
-    assert np.array_equal(clean["sum"], accumulate_weighted_ref(words, dinf.quantise(weights, 16)))
-    assert np.array_equal(clean["alone"], clean["value"])
+    inp = POISON_CASE.build((130, 197))
+    clean, clean_stats = execute(POISON_CASE, inp, None, own)
+    POISON_CASE.check(inp, clean)
     for byte in (0x00, 0xFF):           # 0xFF: FINAL set in every word classify does not write
-        got, stats = run_on_a_fresh_context(words, weights, byte, own)
+        got, stats = execute(POISON_CASE, inp, byte, own)
         assert stats == clean_stats
         for name, raster in clean.items():
             assert got[name].tobytes() == raster.tobytes(), (name, hex(byte))

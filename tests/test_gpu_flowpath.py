@@ -29,7 +29,6 @@ B done in place (one node array for source and destination) was not run: a torn 
 a stop's index where a slot number is expected, which is an out-of-bounds read and not a
 value-only mutant.
 """
-import contextlib
 import ctypes
 
 import numpy as np
@@ -44,7 +43,7 @@ from test_flowacc import acc_kahn, random_acyclic_codes, terminal_mask
 from test_flowpath import (Q_MAX, extreme_doubling, extreme_holds, sum_doubling, sum_holds,
                            value_of)
 from test_gpu_flowacc import path_codes, snake, spiral
-from test_gpu_scribble import D8_SHAPES, POISON
+from test_gpu_scribble import D8_SHAPES, POISON, Case, execute
 from test_gpu_scribble import codes_of as scribble_inputs
 from test_gpu_watersheds import RANDOM_SHAPES, rim_codes
 from test_watersheds import random_seeds
@@ -400,64 +399,56 @@ def test_2048_holds_the_local_proof():
 # ---------------------------------------------------------------------------
 # poisoned scratch and output memory
 # ---------------------------------------------------------------------------
-def run_on_a_fresh_context(inp, byte, own):
-    """A sum per unit length to the streams and a minimum to the outlet, all outputs, on a
-    context of its own with every block the library hands out filled with ``byte`` first
-    (``None``: no poison); ``own``: the caller's poisoned rasters as ``out=``."""
+POISON_TABLE_ROW = (10.0, 0.01, 0.01)                     # geographic_step_lengths past the rows
+
+
+def poison_table(rows):
+    return fp.geographic_step_lengths(rows, *POISON_TABLE_ROW)
+
+
+def poison_run(call, inp):
+    """A sum per unit length to the streams and a minimum to the outlet, all outputs."""
     codes = inp["codes"]
-    table = fp.geographic_step_lengths(codes.shape[0], 10.0, 0.01, 0.01)
     dtypes = {"stop": np.uint32, "sum": np.int64, "value": np.float32, "extreme": np.float32,
               "where": np.uint32}
-    ctx = backend.Context()
-    try:
-        with contextlib.ExitStack() as stack:
-            if byte is not None:
-                stack.enter_context(ctx.scribble(byte))
-            dc = stack.enter_context(DeviceRaster.from_host(codes, dtype=np.uint8, ctx=ctx))
-            dv = stack.enter_context(DeviceRaster.from_host(inp["dem"], dtype=np.float32, ctx=ctx))
-            da = stack.enter_context(DeviceRaster.from_host(inp["acc"], dtype=np.uint32, ctx=ctx))
+    dc, dv, da = call.up(codes), call.up(inp["dem"]), call.up(inp["acc"])
 
-            def out(names):
-                if not own:
-                    return None
-                return {n: stack.enter_context(DeviceRaster.empty(codes.shape, dtypes[n], ctx))
-                        for n in names}
-            sums, sum_stats = fp.flowpath_dev(dc, dv, "sum", da, 10, "length", table, 8,
-                                              SUM_ALL, out=out(SUM_ALL))
-            lows, low_stats = fp.flowpath_dev(dc, dv, "min", want=EXT_ALL, out=out(EXT_ALL))
-            host = {}
-            for prefix, rasters in (("sum_", sums), ("min_", lows)):
-                for name, raster in rasters.items():
-                    if not own:
-                        stack.enter_context(raster)
-                    host[prefix + name] = raster.to_host()
-            ctx.synchronize()
-        stats = {**{"sum_" + k: n for k, n in sum_stats.items()},
-                 **{"min_" + k: n for k, n in low_stats.items()}}
-        return host, {k: n for k, n in stats.items() if "ms_" not in k}, table
-    except backend.BackendError as exc:
-        # a HIP call failed: a kernel may have followed a poisoned index, and whatever runs on
-        # this device afterwards proves nothing
-        pytest.exit(f"a HIP call failed under {byte!r}: {exc}", returncode=3)
-    finally:
-        ctx.close()
+    def out(names):
+        return {n: call.out(codes.shape, dtypes[n]) for n in names} if call.own else None
+    sums, sum_stats = fp.flowpath_dev(dc, dv, "sum", da, 10, "length", poison_table(codes.shape[0]),
+                                      8, SUM_ALL, out=out(SUM_ALL))
+    lows, low_stats = fp.flowpath_dev(dc, dv, "min", want=EXT_ALL, out=out(EXT_ALL))
+    host = {prefix + name: call.host(raster) for prefix, rasters in (("sum_", sums), ("min_", lows))
+            for name, raster in rasters.items()}
+    stats = {**{"sum_" + k: n for k, n in sum_stats.items() if not k.startswith("ms_")},
+             **{"min_" + k: n for k, n in low_stats.items() if not k.startswith("ms_")}}
+    return host, stats
+
+
+def poison_check(inp, got):
+    codes = inp["codes"]
+    q = fp.quantise_steps(codes, inp["dem"], "length", poison_table(codes.shape[0]), 8)
+    stop, total = sum_doubling(codes, q, inp["acc"] >= 10)
+    assert np.array_equal(got["sum_stop"], stop) and np.array_equal(got["sum_sum"], total)
+    assert same(got["sum_value"], value_of(stop, total, 8))
+    stop, extreme, where = extreme_doubling(codes, inp["dem"], "min")
+    assert np.array_equal(got["min_stop"], stop) and same(got["min_extreme"], extreme)
+    assert np.array_equal(got["min_where"], where)
+
+
+# (no schedule set: forest_rounds too is compared, nothing jumps in place)
+POISON_CASE = Case("flowpath-sum-and-min", tuple(D8_SHAPES), scribble_inputs, poison_run,
+                   poison_check, True, frozenset())
 
 
 @pytest.mark.parametrize("own", [False, True], ids=["library_out", "callers_out"])
 @pytest.mark.parametrize("shape", D8_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_poisoned_memory_changes_no_byte(shape, own):
-    inp = scribble_inputs(shape, 5)
-    clean, clean_stats, table = run_on_a_fresh_context(inp, None, own)
-    codes = inp["codes"]
-    q = fp.quantise_steps(codes, inp["dem"], "length", table, 8)
-    stop, total = sum_doubling(codes, q, inp["acc"] >= 10)
-    assert np.array_equal(clean["sum_stop"], stop) and np.array_equal(clean["sum_sum"], total)
-    assert same(clean["sum_value"], value_of(stop, total, 8))
-    stop, extreme, where = extreme_doubling(codes, inp["dem"], "min")
-    assert np.array_equal(clean["min_stop"], stop) and same(clean["min_extreme"], extreme)
-    assert np.array_equal(clean["min_where"], where)
+    inp = POISON_CASE.build(shape, 5)
+    clean, clean_stats = execute(POISON_CASE, inp, None, own)
+    POISON_CASE.check(inp, clean)
     for byte in POISON:                                   # 0x00 first
-        got, stats, _ = run_on_a_fresh_context(inp, byte, own)
+        got, stats = execute(POISON_CASE, inp, byte, own)
         assert got.keys() == clean.keys()
         for name in clean:
             assert same(got[name], clean[name]), (name, hex(byte))

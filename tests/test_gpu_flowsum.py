@@ -6,7 +6,6 @@ across many, marked points, the ``value`` and ``mask`` formulas bit for bit, hos
 repeat equality, poisoned scratch and output memory, and the refusals, each followed by a
 correct call on the same context.
 """
-import contextlib
 import ctypes
 import functools
 
@@ -20,6 +19,7 @@ from hydrodem_amd.backend import DeviceRaster
 from test_flowacc import random_acyclic_codes
 from test_flowsum import downstream_union, wsum_kahn
 from test_gpu_flowacc import E, N, S, W_, path_codes, snake
+from test_gpu_scribble import Case, execute
 
 pytestmark = pytest.mark.gpu
 
@@ -241,45 +241,42 @@ def test_the_chain_from_a_dem_equals_the_staged_calls_and_the_reference():
 # ---------------------------------------------------------------------------
 # poisoned scratch and output memory
 # ---------------------------------------------------------------------------
-def run_on_a_fresh_context(codes, w, byte, own):
-    """One device call for all three outputs on a context of its own, with every block the
-    library hands out filled with ``byte`` first (``None``: no poison); ``own``: the caller's
-    poisoned rasters as ``out=``."""
-    ctx = backend.Context()
-    try:
-        with contextlib.ExitStack() as stack:
-            if byte is not None:
-                stack.enter_context(ctx.scribble(byte))
-            dc = stack.enter_context(DeviceRaster.from_host(codes, dtype=np.uint8, ctx=ctx))
-            dw = stack.enter_context(DeviceRaster.from_host(w, dtype=w.dtype, ctx=ctx))
-            out = None
-            if own:
-                out = {name: stack.enter_context(DeviceRaster.empty(codes.shape, dtype, ctx))
-                       for name, dtype in flowsum.FS_OUTPUTS}
-            dev, stats = flowsum.flowsum_dev(dc, dw, 16, ("sum", "value", "mask"), 100.0, out=out)
-            host = {}
-            for name, raster in dev.items():
-                if not own:
-                    stack.enter_context(raster)
-                else:
-                    assert raster is out[name]
-                host[name] = raster.to_host()
-            ctx.synchronize()
-        return host, {k: v for k, v in stats.items()
-                      if not k.startswith("ms_") and k != "max_hops"}
-    finally:
-        ctx.close()
+def poison_inputs(shape, seed=None):
+    codes = codes_of(shape, True) if shape[1] > 1 else np.full(shape, S, np.uint8)
+    return {"codes": codes, "w": random_weights("f16n", shape, np.random.default_rng(shape[0]))[0]}
+
+
+def poison_run(call, inp):
+    """One device call for all three outputs."""
+    codes = inp["codes"]
+    dc, dw = call.up(np.ascontiguousarray(codes)), call.up(inp["w"])
+    out = None
+    if call.own:
+        out = {name: call.out(codes.shape, dtype) for name, dtype in flowsum.FS_OUTPUTS}
+    dev, stats = flowsum.flowsum_dev(dc, dw, 16, ("sum", "value", "mask"), 100.0, out=out)
+    for name, raster in dev.items():
+        assert not call.own or raster is out[name]
+    return {name: call.host(raster) for name, raster in dev.items()}, stats
+
+
+def poison_check(inp, got):
+    assert np.array_equal(got["sum"], wsum_kahn(inp["codes"], flowsum.quantise(inp["w"], 16)))
+
+
+POISON_SHAPES = [(130, 197), (65, 1)]
+# max_hops: the walk that goes on at a node is the one whose atomic arrives last
+POISON_CASE = Case("flowsum-all", tuple(POISON_SHAPES), poison_inputs, poison_run, poison_check,
+                   True, frozenset(("max_hops",)))
 
 
 @pytest.mark.parametrize("own", [False, True], ids=["library_out", "callers_out"])
-@pytest.mark.parametrize("shape", [(130, 197), (65, 1)])
+@pytest.mark.parametrize("shape", POISON_SHAPES)
 def test_poisoned_memory_changes_nothing(shape, own):
-    codes = codes_of(shape, True) if shape[1] > 1 else np.full(shape, S, np.uint8)
-    w, _ = random_weights("f16n", shape, np.random.default_rng(shape[0]))
-    clean, clean_stats = run_on_a_fresh_context(codes, w, None, own)
-    assert np.array_equal(clean["sum"], wsum_kahn(codes, flowsum.quantise(w, 16)))
+    inp = POISON_CASE.build(shape)
+    clean, clean_stats = execute(POISON_CASE, inp, None, own)
+    POISON_CASE.check(inp, clean)
     for byte in (0x00, 0xFF):                                   # 0x00 first
-        got, stats = run_on_a_fresh_context(codes, w, byte, own)
+        got, stats = execute(POISON_CASE, inp, byte, own)
         for name in clean:
             assert same_bytes(got[name], clean[name]), (name, byte)
         assert stats == clean_stats, byte

@@ -16,6 +16,7 @@ import hdem_synth
 import hydrodem_amd as hd
 from hydrodem_amd import backend, streamnet, streamorder
 from test_flowacc import acc_kahn, random_acyclic_codes
+from test_gpu_scribble import Case, execute
 from test_streamnet import (COLUMNS, COUNTERS, accumulate_down, constructed, holds_known,
                             invariants_hold, random_dem, same_table, table_np)
 from test_streamorder import stream_of
@@ -247,19 +248,45 @@ def test_host_form_device_form_and_two_runs_are_identical(cases):
     assert all(isinstance(v, np.ndarray) for v in c[0].values())
 
 
+def poison_inputs(shape, seed=None):
+    """What the ``cases`` fixture makes for (shape, ramp=True)."""
+    codes = random_acyclic_codes(*shape, seed=shape[0] * 1000 + shape[1], ramp=True)
+    return {"codes": codes, "acc": acc_kahn(codes).astype(np.uint32),
+            "dem": random_dem(shape, shape[0] + shape[1])}
+
+
+def poison_run(call, inp, threshold=4):
+    """The stream order's three rasters, then the table and the row raster from them."""
+    dc, dacc, ddem = call.up(inp["codes"]), call.up(inp["acc"]), call.up(inp["dem"])
+    outs, st = streamorder.streamorder_dev(dc, dacc, threshold, ("order", "magnitude", "link"))
+    for raster in outs.values():
+        call.stack.enter_context(raster)
+    table, row, stats = streamnet.streamlinks_dev(
+        dc, outs["link"], st["links"], dacc, threshold, outs["order"], outs["magnitude"],
+        ddem, CELL, None, True)
+    assert backend.is_device_raster(row) and row.dtype == np.uint32
+    assert "row" not in table
+    return dict(table, row=call.host(row)), {k: stats[k] for k in COUNTERS}
+
+
+def poison_check(inp, got):
+    want, want_row, _ = table_np(inp["codes"], inp["acc"] >= 4, inp["dem"], CELL)
+    assert same_table({k: v for k, v in got.items() if k != "row"}, want)
+    assert np.array_equal(got["row"], want_row)
+
+
+POISON_CASE = Case("streamnet-table-and-row", ((129, 200), (130, 197)), poison_inputs, poison_run,
+                   poison_check, False, frozenset())
+
+
 @pytest.mark.parametrize("byte", [0x00, 0xFF, 0x7F])
 def test_poisoned_memory_changes_nothing(cases, byte):
     codes, acc, dem = cases((129, 200), True)
     want = run(codes, acc, 4, dem, CELL)
-    ctx = backend.Context()
-    try:
-        with ctx.scribble(byte):
-            got = on_device(ctx, codes, acc, dem)
-            ctx.synchronize()
-    finally:
-        ctx.close()
-    assert same_table(got[0], want[0]) and np.array_equal(got[1], want[1])
-    assert got[2] == {k: want[2][k] for k in COUNTERS}
+    got, counters = execute(POISON_CASE, {"codes": codes, "acc": acc, "dem": dem}, byte, False)
+    row = got.pop("row")
+    assert same_table(got, want[0]) and np.array_equal(row, want[1])
+    assert counters == {k: want[2][k] for k in COUNTERS}
 
 
 # ---------------------------------------------------------------------------

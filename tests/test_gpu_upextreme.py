@@ -7,7 +7,6 @@ output alone, host / device / repeat equality, poisoned scratch and output memor
 DEM against the NumPy carving and against the library's own fill, a trench with a closed form,
 and the refusals, each followed by a correct call on the same context.
 """
-import contextlib
 import ctypes
 import functools
 
@@ -20,6 +19,7 @@ from hydrodem_amd import backend, upextreme
 from hydrodem_amd.backend import DeviceRaster
 from test_flowacc import random_acyclic_codes
 from test_gpu_flowacc import E, N, S, W_, path_codes, snake
+from test_gpu_scribble import Case, execute
 from test_upextreme import NOWHERE, QUIET_NAN, carve_ref, raster_of, same_bytes, upext_kahn
 
 pytestmark = pytest.mark.gpu
@@ -169,56 +169,55 @@ def test_host_and_device_forms_and_a_repeat_are_byte_equal():
 # ---------------------------------------------------------------------------
 # poisoned scratch and output memory
 # ---------------------------------------------------------------------------
-def run_on_a_fresh_context(codes, v, byte, own):
-    """One device call of each operator for all its outputs on a context of its own, with every
-    block the library hands out filled with ``byte`` first (``None``: no poison); ``own``: the
-    caller's poisoned rasters as ``out=``."""
-    ctx = backend.Context()
+def poison_inputs(shape, seed=None):
+    codes = codes_of(shape, True) if shape[1] > 1 else np.full(shape, S, np.uint8)
+    return {"codes": codes, "v": random_values("f32n", shape, np.random.default_rng(shape[0]))}
+
+
+def poison_run(call, inp):
+    """One device call of each operator for all its outputs."""
+    codes, v = inp["codes"], inp["v"]
     dtypes = {"extreme": v.dtype, "where": np.uint32, "carved": np.float32, "source": np.uint32}
-    try:
-        with contextlib.ExitStack() as stack:
-            if byte is not None:
-                stack.enter_context(ctx.scribble(byte))
-            dc = stack.enter_context(DeviceRaster.from_host(codes, dtype=np.uint8, ctx=ctx))
-            dv = stack.enter_context(DeviceRaster.from_host(v, dtype=v.dtype, ctx=ctx))
-            out = {}
-            if own:
-                out = {name: stack.enter_context(DeviceRaster.empty(codes.shape, dtype, ctx))
-                       for name, dtype in dtypes.items()}
-            dev, stats = upextreme.upextreme_dev(
-                dc, dv, "max", BOTH, out={k: out[k] for k in BOTH} if own else None)
-            carved, breach_stats = upextreme.breach_dev(
-                dv, dc, ("carved", "source"),
-                out={k: out[k] for k in ("carved", "source")} if own else None)
-            dev.update(carved)
-            host = {}
-            for name, raster in dev.items():
-                if not own:
-                    stack.enter_context(raster)
-                else:
-                    assert raster is out[name]
-                host[name] = raster.to_host()
-            ctx.synchronize()
-        stats = {**stats, **{"breach_" + k: n for k, n in breach_stats.items()}}
-        return host, {k: n for k, n in stats.items()
-                      if "ms_" not in k and not k.endswith("max_hops")}
-    finally:
-        ctx.close()
+    dc, dv = call.up(np.ascontiguousarray(codes)), call.up(v)
+    out = {name: call.out(codes.shape, dtype) for name, dtype in dtypes.items()}
+    dev, stats = upextreme.upextreme_dev(
+        dc, dv, "max", BOTH, out={k: out[k] for k in BOTH} if call.own else None)
+    carved, breach_stats = upextreme.breach_dev(
+        dv, dc, ("carved", "source"),
+        out={k: out[k] for k in ("carved", "source")} if call.own else None)
+    dev.update(carved)
+    for name, raster in dev.items():
+        assert not call.own or raster is out[name]
+    host = {name: call.host(raster) for name, raster in dev.items()}
+    stats = {**{k: n for k, n in stats.items() if not k.startswith("ms_")},
+             **{"breach_" + k: n for k, n in breach_stats.items() if not k.startswith("ms_")}}
+    return host, stats
+
+
+def poison_check(inp, got):
+    codes, v = inp["codes"], inp["v"]
+    want_extreme, want_where = upext_kahn(codes, v, "max")
+    assert same_bytes(got["extreme"], want_extreme) and same_bytes(got["where"], want_where)
+    want_carved, want_source, _, _ = carve_ref(v, codes)
+    assert same_bytes(got["carved"], want_carved) and same_bytes(got["source"], want_source)
+
+
+POISON_SHAPES = [(130, 197), (65, 1)]
+# max_hops: the walk that goes on at a node is the one whose atomic arrives last
+POISON_CASE = Case("upextreme-max-and-breach", tuple(POISON_SHAPES), poison_inputs, poison_run,
+                   poison_check, True, frozenset(("max_hops", "breach_max_hops")))
 
 
 @pytest.mark.parametrize("own", [False, True], ids=["library_out", "callers_out"])
-@pytest.mark.parametrize("shape", [(130, 197), (65, 1)])
+@pytest.mark.parametrize("shape", POISON_SHAPES)
 def test_poisoned_memory_changes_nothing(shape, own):
-    codes = codes_of(shape, True) if shape[1] > 1 else np.full(shape, S, np.uint8)
-    v = random_values("f32n", shape, np.random.default_rng(shape[0]))
-    clean, clean_stats = run_on_a_fresh_context(codes, v, None, own)
-    want_extreme, want_where = upext_kahn(codes, v, "max")
-    assert same_bytes(clean["extreme"], want_extreme) and same_bytes(clean["where"], want_where)
-    want_carved, want_source, pits, lowered = carve_ref(v, codes)
-    assert same_bytes(clean["carved"], want_carved) and same_bytes(clean["source"], want_source)
+    inp = POISON_CASE.build(shape)
+    clean, clean_stats = execute(POISON_CASE, inp, None, own)
+    POISON_CASE.check(inp, clean)
+    _, _, pits, lowered = carve_ref(inp["v"], inp["codes"])
     assert clean_stats["breach_pits"] == pits and clean_stats["breach_lowered"] == lowered
     for byte in (0x00, 0xFF):                                   # 0x00 first
-        got, stats = run_on_a_fresh_context(codes, v, byte, own)
+        got, stats = execute(POISON_CASE, inp, byte, own)
         for name in clean:
             assert same_bytes(got[name], clean[name]), (name, byte)
         assert stats == clean_stats, byte

@@ -6,7 +6,6 @@ the zone rasters that strain the tiling, the ranks and the per-tile table, with 
 type; against the library's own operators; across the two forms, column subsets and poisoned
 memory; and the refusals, each an ordinary error return in bounded time.
 """
-import contextlib
 import ctypes
 
 import numpy as np
@@ -16,6 +15,7 @@ import hdem_synth
 import hydrodem_amd as hd
 from hydrodem_amd import backend, zonal
 from test_flowacc import random_acyclic_codes
+from test_gpu_scribble import Case, execute
 from test_zonal import (COUNTERS, SHAPES, ZONE_KINDS, blobs, float_values, multiples, one_zone,
                         salt_and_pepper, same_bits, same_table, zonal_np)
 
@@ -271,36 +271,39 @@ def test_broadcast_is_a_lookup_by_rank(shape):
     assert same_bits(empty.broadcast("count", 3), np.full(shape, 3, U32))
 
 
-def poisoned_run(zones, values, byte):
-    """Count, table and broadcast of device rasters on a fresh context, under ``byte``."""
-    ctx = backend.Context()
-    try:
-        with contextlib.ExitStack() as stack:
-            if byte is not None:
-                stack.enter_context(ctx.scribble(byte))
-            dz = stack.enter_context(backend.DeviceRaster.from_host(zones, ctx=ctx))
-            dv = stack.enter_context(backend.DeviceRaster.from_host(values, ctx=ctx))
-            count, count_stats = zonal.zonal_count_dev(dz)
-            table, stats = zonal.zonal_dev(dz, dv)
-            table["raster"] = stack.enter_context(
-                zonal.zonal_broadcast_dev(dz, table["count"], 0xABCD)).to_host()
-            ctx.synchronize()
-        assert count == stats["zones"] == count_stats["zones"]
-        return table, {k: stats[k] for k in COUNTERS}
-    finally:
-        ctx.close()
-
-
-@pytest.mark.parametrize("shape", [(130, 197), (64, 64)], ids=by_shape)
-def test_poisoned_memory_changes_nothing(shape):
-    zones = blobs(shape, 12)
+def poison_inputs(shape, seed=12):
+    zones = blobs(shape, seed)
     zones[:40, :50] = np.arange(1, 2001, dtype=U32).reshape(40, 50)     # a tile past its table
-    values = float_values(shape, 12)
-    want, counters = poisoned_run(zones, values, None)
-    assert same_table({k: v for k, v in want.items() if k != "raster"},
-                      zonal_np(zones, values)[0])
+    return {"zones": zones, "values": float_values(shape, seed)}
+
+
+def poison_run(call, inp):
+    """Count, table and broadcast of device rasters."""
+    dz, dv = call.up(inp["zones"]), call.up(inp["values"])
+    count, count_stats = zonal.zonal_count_dev(dz)
+    table, stats = zonal.zonal_dev(dz, dv)
+    table["raster"] = call.host(zonal.zonal_broadcast_dev(dz, table["count"], 0xABCD))
+    assert count == stats["zones"] == count_stats["zones"]
+    return table, {k: stats[k] for k in COUNTERS}
+
+
+def poison_check(inp, got):
+    assert same_table({k: v for k, v in got.items() if k != "raster"},
+                      zonal_np(inp["zones"], inp["values"])[0])
+
+
+POISON_SHAPES = [(130, 197), (64, 64)]
+POISON_CASE = Case("zonal-count-table-broadcast", tuple(POISON_SHAPES), poison_inputs, poison_run,
+                   poison_check, False, frozenset())
+
+
+@pytest.mark.parametrize("shape", POISON_SHAPES, ids=by_shape)
+def test_poisoned_memory_changes_nothing(shape):
+    inp = POISON_CASE.build(shape)
+    want, counters = execute(POISON_CASE, inp, None, False)
+    POISON_CASE.check(inp, want)
     for byte in (0x00, 0xFF, 0x7F, 0x01):       # 0x00 first: the most forgiving poison
-        got, got_counters = poisoned_run(zones, values, byte)
+        got, got_counters = execute(POISON_CASE, inp, byte, False)
         assert list(got) == list(want) and got_counters == counters, hex(byte)
         for name in want:
             assert same_bits(got[name], want[name]), (hex(byte), name)
