@@ -247,6 +247,18 @@ class _DInfSumStats(_SizedStats):
                                          ("total", ctypes.c_uint64)]
 
 
+class _MFDStats(_SizedStats):
+    """``hdem_mfd_stats`` (the binding is hydrodem_amd/mfd.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("ms_total", ctypes.c_float),
+                ("no_flow", ctypes.c_int64), ("fallback_cells", ctypes.c_int64),
+                ("split_cells", ctypes.c_int64)]
+
+
+class _MFDAccStats(_SizedStats):
+    """``hdem_mfdacc_stats``: the struct of the weighted D-infinity accumulation."""
+    _fields_ = list(_DInfSumStats._fields_)
+
+
 class _TerrainAreaStats(_SizedStats):
     """``hdem_terrain_area_stats``: the terrain fields, then the cells whose area is <= 0."""
     _fields_ = _TerrainStats._fields_ + [("nonpositive_area", ctypes.c_int64)]
@@ -410,6 +422,10 @@ SIGNATURES = {
                              [_vp] * 8 + [_i, _c.POINTER(_TerrainAreaStats)],
     "hdem_terrain_area_f32_dev": [_vp, _vp, _i, _i, _vp, _vp, _vp] + [_c.c_double] * 4 +
                                  [_vp] * 8 + [_i, _c.POINTER(_TerrainAreaStats)],
+    # one symbol each: HDEM_ON_DEVICE in the flags says whose pointers (hydrodem_amd/mfd.py)
+    "hdem_mfd_f32": [_vp, _vp, _i, _i, _vp] + [_c.c_double] * 5 + [_vp, _vp, _i,
+                                                                  _c.POINTER(_MFDStats)],
+    "hdem_mfdacc_u64": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _c.POINTER(_MFDAccStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 
@@ -607,7 +623,7 @@ def device_count():
 
 _DTYPES = {np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.uint8),
            np.dtype(np.complex64), np.dtype(np.complex128), np.dtype(np.int64),
-           np.dtype(np.uint32)}
+           np.dtype(np.uint32), np.dtype(np.uint64)}
 
 
 class _HostBlocks:

@@ -28,9 +28,10 @@ New operators (the reference has neither): ``SinkFill``,
 ``UpstreamExtreme``, ``BreachDepressions``, ``Watersheds``, ``FlowDistance``,
 ``FlowPathSum``, ``FlowPathExtreme``, ``HeightAboveDrainage``, ``UpstreamFlowLength``,
 ``StreamOrder``, ``StreamNetwork``, ``DInfFlowDirection``, ``DInfFlowAccumulation``,
-``WeightedDInfFlowAccumulation``, ``AreaWetnessIndex`` and the chains ``DemToHAND``,
-``DemToStreamOrder``, ``DemToStreamNetwork``, ``DemToDInfArea`` and ``DemToDInfWetness``, shaped
-like every other ``Filter``.
+``WeightedDInfFlowAccumulation``, ``AreaWetnessIndex``, ``MFDFlowDirection``,
+``MFDFlowAccumulation`` and the chains ``DemToHAND``, ``DemToStreamOrder``,
+``DemToStreamNetwork``, ``DemToDInfArea``, ``DemToDInfWetness`` and ``DemToMFDArea``, shaped like
+every other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -71,6 +72,7 @@ from .. import flowsum as _flowsum
 from .. import upextreme as _upextreme
 from .. import flowpath as _flowpath
 from .. import dinf as _dinf
+from .. import mfd as _mfd
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -2354,6 +2356,182 @@ class DemToDInfWetness(ComposedFilter):  # pylint: disable=too-few-public-method
                 self.dinf_slope = dinf_slope
                 stack.pop_all()                     # the caller's to free from here on
             return outs["twi"]
+
+
+class MFDFlowDirection(Filter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """Multiple-flow-direction flow direction (new operator; Quinn 1991, Freeman 1991, Holmgren
+    1994; Whitebox ``FD8FlowAccumulation``, SAGA "MFD").  Input: a float32 H x W DEM, NaN where
+    there is no data.  Returns one uint64 word per cell (``hydrodem_amd.mfd``): a cell sends
+    flow to every lower neighbour in proportion to ``c * (slope / steepest slope) ** exponent``,
+    ``c`` being ``w_card`` for the four cardinal and ``w_diag`` for the four diagonal
+    neighbours; the shares are quantised to 2^-8 and the steepest-weighted receiver takes the
+    rest.  The slopes are float64 on the float32 elevations, the power is the contract's own
+    (no math library), so the words are the same bits everywhere.  Cells without a lower
+    neighbour, NaN cells and infinite ones get 0: no outflow.  Cells on the raster's edge route
+    like any other, among the neighbours they have.
+
+    ``method``: ``"freeman"`` (exponent 1.1), ``"quinn"`` (exponent 1, contour-length weights
+    0.5 and 0.354), ``"holmgren"`` with the caller's ``exponent`` (0.25 ... 16), or an
+    ``(exponent, w_card, w_diag)`` triple.  ``cellsize``: a number or ``(dx, dy)``.
+    ``fallback``: uint8 ESRI D8 codes of the DEM's shape (array or ``DeviceRaster``); a cell that
+    would get 0 takes its code's direction, so that the flats of an exact fill routed by
+    ``ResolveFlats`` keep draining.  With ``keep_partial_results=True`` the launch also writes
+    ``slope`` (float32: the steepest downward slope, 0 where there is none, NaN at NaN; what
+    ``AreaWetnessIndex`` takes as ``given_slope``) and leaves it in the attribute of that name:
+    a host array after ``apply``, a device raster (the caller's to free) after ``apply_device``.
+
+    ``ValueError`` for a dtype other than float32, a raster that is not 2-D, an unknown
+    ``method``, an ``exponent`` out of range, a ``cellsize`` that is not finite and positive, a
+    ``fallback`` of another type, dtype or shape (all before the device is touched) and a
+    fallback byte that is no D8 code.
+
+    Attributes
+    ----------
+    stats : dict
+        no_flow (cells with word 0), fallback_cells, split_cells (cells with more than one
+        receiver) of the last call; ms_total when profiling.
+    """
+
+    auto_device = False     # words are uint64: no float32 chain goes on from them
+
+    def __init__(self, method="freeman", exponent=None, cellsize=1.0, fallback=None,
+                 keep_partial_results=False):
+        self.method, self.exponent, self.cellsize = method, exponent, cellsize
+        self.fallback = _Given(fallback, "fallback", (np.uint8,)).value
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.slope = None
+        _mfd.mfd_args(np.zeros((1, 1), np.float32), method, exponent, cellsize,
+                      _Given(self.fallback).stand_in())
+
+    def _want(self):
+        return _mfd.EXTRAS if self.keep_partial_results else ()
+
+    def _keep(self, words, extras, stats):
+        self.stats = stats
+        self.slope = extras.get("slope")
+        return words
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _mfd.mfd_args(image_to_filter, self.method, self.exponent, self.cellsize, self.fallback)
+        return self._keep(*_mfd.mfd(image_to_filter, self.method, self.exponent, self.cellsize,
+                                    _Given(self.fallback).host(), self._want()))
+
+    def apply_device(self, raster):
+        _mfd.mfd_args(raster, self.method, self.exponent, self.cellsize, self.fallback)
+        with _Given(self.fallback).device(raster.ctx) as fallback:
+            return self._keep(*_mfd.mfd_dev(raster, self.method, self.exponent, self.cellsize,
+                                            fallback, self._want()))
+
+
+class MFDFlowAccumulation(Filter):  # pylint: disable=too-few-public-methods
+    """Multiple-flow-direction flow accumulation (new operator).  Input: a uint64 H x W raster of
+    MFD words as ``MFDFlowDirection`` returns them.  ``A[c] = own(c)`` plus what the
+    8-neighbours whose word names ``c`` send it: a donor with amount ``A`` sends
+    ``(A * p) >> 8`` along each share ``p`` and the rest to its main receiver.  ``own`` is
+    ``2^frac_bits`` (``frac_bits`` 0 ... 16), or with ``weights`` (an H x W NumPy array or
+    ``DeviceRaster`` of uint8, uint32 or float32) the weight quantised as
+    ``WeightedDInfFlowAccumulation`` does (``frac_bits`` 0 ... 30 for float32).  Integers
+    throughout: every unit arrives at a cell without outflow, and the result is identical from
+    run to run.
+
+    ``output``: ``"value"`` float32 ``float32(float64(A) * 2^-frac_bits)``; ``"sum"`` int64
+    ``A``.
+
+    ``ValueError`` for operands of another type, dtype or shape, ``frac_bits`` out of range, an
+    unknown ``output`` (all before the device is touched), an invalid word, a receiver outside
+    the raster, words that form a cycle (only user-supplied words can), weights that
+    ``WeightedDInfFlowAccumulation`` refuses and more than 2^32 - 1 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        split_cells (cells with more than one receiver), terminal_cells, invalid, outside,
+        unresolved, rounds and tile_visits (these two depend on the schedule), tile_h / tile_w,
+        nan_weights, bad_weights and total of the last call; phase times when profiling is on.
+    """
+
+    auto_device = False     # the input is uint64 words, not a float32 raster
+    WEIGHT_TYPES = (np.uint8, np.uint32, np.float32)
+    OUTPUTS = {name: np.dtype(dtype) for name, dtype in _mfd.OUTPUTS}
+
+    def __init__(self, frac_bits=16, output="value", weights=None):
+        self.weights = _Given(weights, "weights", self.WEIGHT_TYPES).value
+        if not isinstance(output, str) or output not in self.OUTPUTS:
+            raise ValueError(f"output is one of {list(self.OUTPUTS)}, got {output!r}")
+        self.frac_bits, self.output = frac_bits, output
+        self.dtype = self.OUTPUTS[output]
+        self.stats = {}
+        # everything but the shapes, on 1 x 1 stand-ins
+        _mfd.mfdacc_args(np.empty((1, 1), np.uint64), _Given(self.weights).stand_in(),
+                         frac_bits, output)
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _mfd.mfdacc_args(image_to_filter, self.weights, self.frac_bits, self.output)
+        outs, self.stats = _mfd.mfdacc(image_to_filter, _Given(self.weights).host(),
+                                       self.frac_bits, self.output)
+        return outs[self.output]
+
+    def apply_device(self, raster):
+        _mfd.mfdacc_args(raster, self.weights, self.frac_bits, self.output)
+        with _Given(self.weights).device(raster.ctx) as weights:
+            outs, self.stats = _mfd.mfdacc_dev(raster, weights, self.frac_bits, self.output)
+        return outs[self.output]
+
+
+class DemToMFDArea(ComposedFilter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """A float32 DEM to its multiple-flow-direction catchment area in one device-resident chain:
+    ``SinkFill(epsilon)`` and ``D8FlowDirection`` (one call, as in ``HydroConditioning``),
+    ``MFDFlowDirection`` on the **filled** DEM with the chain's D8 codes as fallback, then
+    ``MFDFlowAccumulation``.  Nothing is downloaded in between.  ``flats`` as in ``DemToHAND``:
+    with ``"resolve"`` the fallback codes cross the flats, so an exact fill (``epsilon=0``)
+    drains; ``method``, ``exponent``, ``cellsize``, ``frac_bits`` and ``output`` as in the two
+    operators.
+
+    ``stats`` maps ``SinkFill``, ``MFDFlowDirection`` and ``MFDFlowAccumulation`` (and
+    ``ResolveFlats``) to the stats of their stage.  With ``keep_partial_results=True`` the last
+    call leaves ``filled``, ``codes`` and ``words``: host arrays after ``apply``, device rasters
+    (the caller's to free) after ``apply_device``; otherwise they are ``None``."""
+
+    def __init__(self, *, epsilon=1e-3, flats="keep", method="freeman", exponent=None,
+                 cellsize=1.0, frac_bits=16, output="value", keep_partial_results=False):
+        super().__init__()
+        self.flats = _check_flats(flats)
+        self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection(),
+                        MFDFlowDirection(method=method, exponent=exponent, cellsize=cellsize),
+                        MFDFlowAccumulation(frac_bits=frac_bits, output=output)]
+        self.method, self.exponent, self.cellsize = method, exponent, cellsize
+        self.frac_bits, self.output = frac_bits, output
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.filled = self.codes = self.words = None
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("DemToMFDArea", image_to_filter, np.float32, "a float32 DEM")
+        return _through_device(self, image_to_filter,
+                               ("filled", "codes", "words") if self.keep_partial_results else ())
+
+    def apply_device(self, raster):
+        _check_raster("DemToMFDArea", raster, np.float32, "a float32 DEM")
+        fill, _, direct, accumulate = self.filters
+        self.filled = self.codes = self.words = None
+        with contextlib.ExitStack() as stack:
+            filled, codes, resolve_stats = _fill_d8(stack, raster, fill, self.flats)
+            words, _, direct.stats = _mfd.mfd_dev(filled, self.method, self.exponent,
+                                                  self.cellsize, codes)
+            stack.enter_context(words)
+            outs, accumulate.stats = _mfd.mfdacc_dev(words, None, self.frac_bits, self.output)
+            self.stats = {"SinkFill": fill.stats, "MFDFlowDirection": direct.stats,
+                          "MFDFlowAccumulation": accumulate.stats}
+            if resolve_stats is not None:
+                self.stats["ResolveFlats"] = resolve_stats
+            if self.keep_partial_results:
+                self.filled, self.codes, self.words = filled, codes, words
+                stack.pop_all()                     # the caller's to free from here on
+            return outs[self.output]
 
 
 class DemToStreamOrder(ComposedFilter):  # pylint: disable=too-few-public-methods

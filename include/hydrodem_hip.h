@@ -1559,6 +1559,113 @@ int hdem_terrain_area_f32_dev(hdem_ctx *ctx, const float *dem, int H, int W, con
                               float *twi, float *spi, int flags,
                               hdem_terrain_area_stats *stats);    /* device pointers */
 
+/* ---- A24  MFDFlowDirection.apply  (new operator: multiple-flow-direction flow direction) ----
+ * Quinn 1991, Freeman 1991, Holmgren 1994: a cell sends flow to every lower neighbour.
+ * The MFD word, one uint64 per cell, is what A24 writes and A25 reads.  Directions are numbered as
+ * in A20's kernels, counter-clockwise from east: 0 = E, 1 = NE, 2 = N, 3 = NW, 4 = W, 5 = SW,
+ * 6 = S, 7 = SE; north is row - 1.
+ *   bit 59      the cell has outflow; if it is 0 the whole word is 0
+ *   bits 56-58  m, the direction of the main receiver
+ *   bits 0-55   seven 8-bit fields p_1 ... p_7 (p_j in bits 8 (j - 1) ... 8 j - 1): the share, in
+ *               units of 2^-8, of the neighbour in direction (m + j) & 7; 0: no flow that way
+ *   bits 60-63  0
+ * A word is valid when it is 0, or bit 59 is set, bits 60-63 are 0 and p_1 + ... + p_7 <= 255.
+ * A cell with amount A sends (A * p_j) >> 8 to each receiver with p_j > 0 and A minus the sum of
+ * those to the main receiver: every unit is conserved and the arithmetic is shifts only.  The
+ * canonical word of a D8 code is m = its direction with every p_j = 0.  The 8-bit resolution is
+ * deliberate -- eight shares have to fit 64 bits -- and a share below 1 / 512 is lost to the main
+ * receiver.
+ *
+ * dem: float32 H x W, NaN is nodata.  All arithmetic is float64 on the float32 elevations, one
+ * rounding per operation, no fused multiply-add.  For a cell with a finite elevation z0:
+ *   1. for each direction d whose neighbour z_d is inside the raster and not NaN, with
+ *      drop = z0 - z_d > 0:  s_d = drop / dist_d, dist_d = dx (E, W), dy (N, S) or
+ *      diag = sqrt(dx * dx + dy * dy) (the host computes diag once); s_d = 0 otherwise
+ *   2. no s_d > 0: the word is 0 (stats->no_flow), unless fallback (optional, uint8 ESRI D8 codes,
+ *      H x W) holds a code other than 0 for the cell: then the code's canonical word
+ *      (stats->fallback_cells).  A fallback byte that is no D8 code is counted and refused as in
+ *      A20.  A cell whose elevation is NaN or infinite goes this way too.
+ *   3. s_max = the greatest s_d;  t_d = 1 where s_d == s_max, else s_d / s_max
+ *   4. f_d = c_d * pw(t_d, exponent) with c_d = w_card for even d, w_diag for odd d; pw is skipped
+ *      (f_d = c_d * t_d) when exponent == 1.0; f_d = 0 where s_d = 0 or t_d < 2^-64
+ *   5. m = the direction of the greatest f_d, the lowest d among equals
+ *   6. F = ((((((f_0 + f_1) + f_2) + f_3) + f_4) + f_5) + f_6) + f_7
+ *   7. for d != m with f_d > 0:  p = (uint64)floor((256.0 * f_d) / F + 0.5), the field of
+ *      j = (d - m) & 7.  f_d <= f_m gives p <= 128, and the non-main shares sum to at most
+ *      256 * 7 / 8 + 3.5, so the sum of the fields stays <= 255.  Two equal receivers get 128 each.
+ * pw(t, e) is not the math library's pow: two libraries a last-place unit apart would disagree on
+ * whole families of symmetric cells, where a quotient lands on a rounding boundary.  It is this
+ * sequence of float64 operations (constants written 1.0 / n are the correctly rounded quotients):
+ *   (m, k) = frexp(t)                          t = m * 2^k, m in [0.5, 1)
+ *   if m < 0.7071067811865476:  m = m * 2.0, k = k - 1
+ *   s = (m - 1.0) / (m + 1.0);   s2 = s * s
+ *   r = 1.0 / 15.0;   then for n = 13, 11, 9, 7, 5, 3, 1:  r = r * s2 + 1.0 / n
+ *   l2 = (double)k + ((2.0 * s) * r) * 1.4426950408889634
+ *   y = e * l2;   n = floor(y + 0.5);   u = (y - n) * 0.6931471805599453
+ *   p = 1.0;   then for i = 12, 11, ..., 2:  p = 1.0 + (u * p) * (1.0 / i);   p = 1.0 + u * p
+ *   pw = ldexp(p, (int)n)
+ * pw(1, e) is 1 exactly (s = 0, k = 0, y = 0).  For t in [2^-64, 1] and e in [0.25, 16] the
+ * truncation of the two series is below 1e-12 and the rounding of y (|y| <= 1024) below 1e-12:
+ * pw is within 1e-9 of the real power with a wide margin, where a share is quantised in steps of
+ * 2^-9 of the total.
+ * Optional float32 output (NULL: no store):
+ *   slope   (float)s_max; 0 where no neighbour lies lower (a fallback cell too, as in A20), NaN
+ *           where the dem is NaN.  It is what A23 takes as given_slope.
+ * One radius-1 stencil launch on the tile staging of A14.  The words and slope are the same bits
+ * from run to run, between the host and device forms, and equal to the formulas above evaluated
+ * in IEEE float64.  The combined graph is acyclic for A20's reason: every receiver with a share
+ * is strictly lower, and fallback steps (A8) lower the flat distance.
+ *
+ * One symbol, no _dev twin: the pointers are host pointers by default (staged through device
+ * buffers of the context, synchronous) and device pointers when flags has HDEM_ON_DEVICE; both
+ * run the same body behind the same checks.  HDEM_ERR_BAD_ARG before the launch: a null context,
+ * dem or words, dx or dy not finite and > 0, exponent outside [0.25, 16], w_card or w_diag not
+ * finite and > 0, unknown flags; after it: a fallback byte that is no D8 code.  No workspace but
+ * 32 bytes of counters; the call synchronises the context's stream once to read them.  stats may
+ * be NULL; otherwise the caller sets stats->struct_size first; ms_total is filled while profiling
+ * is on. */
+#define HDEM_ON_DEVICE 0x40000000    /* A24, A25: the raster pointers are device pointers */
+typedef struct hdem_mfd_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_mfd_stats), set by the caller                */
+    float ms_total;          /* the launch (HIP events; profiling)                           */
+    int64_t no_flow;         /* cells whose word is 0                                        */
+    int64_t fallback_cells;  /* cells that took their direction from fallback                */
+    int64_t split_cells;     /* cells with more than one receiver                            */
+} hdem_mfd_stats;            /* sizeof == 32 */
+int hdem_mfd_f32(hdem_ctx *ctx, const float *dem, int H, int W, const uint8_t *fallback, double dx,
+                 double dy, double exponent, double w_card, double w_diag, uint64_t *words,
+                 float *slope, int flags, hdem_mfd_stats *stats);
+
+/* ---- A25  MFDFlowAccumulation.apply  (new operator: MFD flow accumulation, weighted or not) ----
+ * words: uint64 H x W, the MFD words of A24.  A donor of a cell c is an 8-neighbour whose word
+ * names c: as its main receiver, or with a share field > 0.
+ *   A[c] = own(c) + sum over the donors d of c of what d sends to c      (A24: shifts only)
+ * weights NULL (weight_type 0): own = 2^frac_bits, frac_bits 0 ... 16.  Otherwise own = q(w[c])
+ * exactly as A22 quantises it: the types, the frac_bits ranges, the NaN rule, the refusals and
+ * the total-below-2^48 rule are A22's.  A < 2^48 and a share field <= 255 keep every product
+ * below 2^56.  Integer adds only: identical from run to run, whatever the schedule, and between
+ * the host and device forms; the sum of A over the cells with word 0 is the total of the own
+ * terms.  On canonical words the result is A21's on the canonical D-infinity words of the same
+ * codes, and with uint8 weights of 1 it is the unweighted result at the same frac_bits.
+ *   sum     int64, A          (may serve as the working raster, as in A21)
+ *   value   float32, (float)((double)A * 2^-frac_bits)
+ * At least one of the two is wanted.  The scheme is A21's -- classify, rounds of tile visits, a
+ * schedule kernel, a streaming final pass, one host read per round -- with the routing of the MFD
+ * word; a tile visit holds 16 B per cell of LDS (a uint64 value and a uint64 word).
+ * One symbol, as A24: host pointers, or device pointers with HDEM_ON_DEVICE in flags.
+ * HDEM_ERR_BAD_ARG before any launch: a null context or words, neither output, a weight type
+ * without weights or an unknown one, frac_bits out of range, unknown flags, more than 2^32 - 1
+ * cells, an output that overlaps an input or the other output.  After classify, with the count
+ * in the text and in this order: invalid words, receivers outside the raster, weights out of
+ * range, a total of 2^48 or more.  After the last round: words that form a cycle ("N cells never
+ * resolve"; the rounds are bounded by H * W + 1).  The outputs are unspecified then.
+ * stats: the struct of A22 (104 bytes; a shorter one is filled as far as it goes); split_cells
+ * counts the cells with more than one receiver, terminal_cells those with word 0. */
+typedef hdem_dinfsum_stats hdem_mfdacc_stats;
+int hdem_mfdacc_u64(hdem_ctx *ctx, const uint64_t *words, int H, int W, const void *weights,
+                    int weight_type, int frac_bits, int64_t *sum, float *value, int flags,
+                    hdem_mfdacc_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
