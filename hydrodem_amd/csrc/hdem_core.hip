@@ -275,7 +275,9 @@ extern "C" int hdem_trim(hdem_ctx *ctx, size_t *released)
         ctx->coarse_buf = nullptr;
         ctx->coarse_bytes = 0;
     }
-    for (int k = 0; k < 2; ++k)
+    // (a prepared hub start lives in hub_buf[0] until its raster is made and its levels are
+    // consumed: hdem_fill_hub_prepare_dev)
+    for (int k = ctx->hub_prep_z ? 1 : 0; k < 2; ++k)
         if (ctx->hub_buf[k]) {
             bytes += ctx->hub_bytes[k];
             (void)hipFree(ctx->hub_buf[k]);

@@ -73,20 +73,24 @@ struct hdem_ctx {
     bool fill_quiescent = false;       // ... and the last call left nothing to do
     int *fill_seam_words = nullptr;    // device: [0] queued after a deferred call, [1]/[2] ghost row changed
     bool fill_stats_carry = false;     // deferred calls' counters are still in the workspace
-    // coarse start of the sink fill: a caller's filled coarse raster for the next INIT call
-    // (hdem_set_fill_coarse_start), and the buffer of the library's own coarse pre-solve
+    // coarse start of the sink fill: a caller's filled coarse raster for the next fill call
+    // (hdem_set_fill_coarse_start; that call takes it, refused or not), and the buffer of the
+    // library's own coarse pre-solve
     const float *start_coarse = nullptr;
     const int32_t *start_row_map = nullptr;
-    int start_cw = 0, start_shift = 0;
+    int start_ch = 0, start_cw = 0, start_shift = 0;
     void *coarse_buf = nullptr;
     size_t coarse_bytes = 0;
     void *hub_buf[2] = {nullptr, nullptr};   // hub start of the sink fill: rim lines, hub raster
     size_t hub_bytes[2] = {0, 0};            // ([1]: of the hub raster's own fill)
     // ... prepared for a row-block partition (hdem_fill_hub_prepare_dev), and the levels the
-    // partition worked out for the next INIT fill of that block
+    // partition worked out for the next fill call (which takes them, refused or not).  While
+    // hub_prep_z is set hdem_trim keeps hub_buf[0]; hub_prep_lines: its rim lines are still
+    // those of the preparation (no own hub start at depth 0 and no other preparation since)
     const float *hub_prep_z = nullptr;
     float *hub_prep_w = nullptr;
     int hub_prep_h = 0, hub_prep_cols = 0, hub_prep_flags = 0;
+    bool hub_prep_lines = false;
     const float *hub_levels_given = nullptr;
     void *arena = nullptr;             // scratch of the multi-kernel chains, grown on demand
     size_t arena_bytes = 0;

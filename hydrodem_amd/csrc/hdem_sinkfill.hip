@@ -1824,6 +1824,13 @@ extern "C" int hdem_fill_hub_prepare_dev(hdem_ctx *ctx, const float *z, int H, i
     HDEM_REQUIRE(z != w, HDEM_ERR_BAD_ARG, "sink fill cannot run in place");
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     const fill_knobs kn = fill_read_knobs();
+    const int ghost_flags = flags & (HDEM_FILL_GHOST_TOP | HDEM_FILL_GHOST_BOTTOM);
+    // A preparation that is still open (its levels not consumed) and was made for another
+    // block is written over here.  hdem_fill_hub_raster_dev names no block, so it cannot tell
+    // which of the two its caller means: it refuses, and the caller prepares again.
+    const bool over_another = ctx->hub_prep_z &&
+                              !(ctx->hub_prep_z == z && ctx->hub_prep_w == w && ctx->hub_prep_h == H &&
+                                ctx->hub_prep_cols == W && ctx->hub_prep_flags == ghost_flags);
     hub_bufs hb;
     if (int rc = hub_alloc(ctx, 0, H, W, &hb)) return rc;
     {
@@ -1835,7 +1842,8 @@ extern "C" int hdem_fill_hub_prepare_dev(hdem_ctx *ctx, const float *z, int H, i
     ctx->hub_prep_w = w;
     ctx->hub_prep_h = H;
     ctx->hub_prep_cols = W;
-    ctx->hub_prep_flags = flags & (HDEM_FILL_GHOST_TOP | HDEM_FILL_GHOST_BOTTOM);
+    ctx->hub_prep_flags = ghost_flags;
+    ctx->hub_prep_lines = !over_another;
     ctx->hub_levels_given = nullptr;
     return HDEM_OK;
 }
@@ -1844,6 +1852,14 @@ extern "C" int hdem_fill_hub_raster_dev(hdem_ctx *ctx, float *raster)
 {
     HDEM_REQUIRE(ctx && raster, HDEM_ERR_BAD_ARG, "null argument");
     HDEM_REQUIRE(ctx->hub_prep_z, HDEM_ERR_BAD_ARG, "no prepared hub start (hdem_fill_hub_prepare_dev)");
+    if (!ctx->hub_prep_lines) {
+        // (dropped, so that hdem_trim may take the buffer and the next preparation is the only one)
+        ctx->hub_prep_z = nullptr;
+        ctx->hub_levels_given = nullptr;
+        hdem_set_error("the prepared hub start was overwritten: another fill or another "
+                       "hdem_fill_hub_prepare_dev has used the hub buffer since; prepare again");
+        return HDEM_ERR_BAD_ARG;
+    }
     HDEM_HIP_CHECK(hipSetDevice(ctx->device));
     hub_bufs hb;
     if (int rc = hub_alloc(ctx, 0, ctx->hub_prep_h, ctx->hub_prep_cols, &hb)) return rc;
@@ -1931,6 +1947,31 @@ enum fill_role {                   // (the value is fill_async_kernel's ROLE)
     FILL_PRESOLVE = 1,             // the fill of a start raster: K_FILL_COARSE, nobody waits for it
 };
 
+// What the caller armed for "the next fill" (hdem_set_fill_hub_levels,
+// hdem_set_fill_coarse_start): taken out of the context by the entry point, before any check
+// can refuse the call, so that it is used by this call or by none.
+struct fill_armed {
+    const float *hub_levels = nullptr;
+    const float *coarse = nullptr;
+    const int32_t *row_map = nullptr;
+    int ch = 0, cw = 0, shift = 0;
+};
+
+fill_armed fill_take_armed(hdem_ctx *ctx)
+{
+    fill_armed a;
+    a.hub_levels = ctx->hub_levels_given;
+    a.coarse = ctx->start_coarse;
+    a.row_map = ctx->start_row_map;
+    a.ch = ctx->start_ch;
+    a.cw = ctx->start_cw;
+    a.shift = ctx->start_shift;
+    ctx->hub_levels_given = nullptr;
+    ctx->start_coarse = nullptr;
+    ctx->start_row_map = nullptr;
+    return a;
+}
+
 struct fill_call {
     const float *z;
     int H, W;
@@ -1942,6 +1983,7 @@ struct fill_call {
     int depth;                     // 0: a caller's fill and its coarse pre-solve, 1: of a hub raster,
                                    // 2: of that raster's hub raster; picks fill_ws[] and hub_buf[]
     fill_role role;
+    fill_armed armed = {};         // (a caller's fill only: the fills of start rasters have none)
 };
 
 struct fill_outcome {
@@ -2026,16 +2068,26 @@ int fill_read_counts(hdem_ctx *ctx, const fill_ws &ws, bool with_pend)
 }
 
 // ---- phase 1: what the relaxation starts from -------------------------------------------
-// Consumes the caller's hub levels (always) and allocates the hub buffers of an own hub start.
+// Works from what the entry point took out of the context (c.armed), allocates the hub buffers
+// of an own hub start and, at depth 0, marks a prepared hub start's rim lines as gone.
 int fill_choose_start(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, const fill_plan &p,
                       fill_start *s)
 {
     const int H = c.H, W = c.W;
     const bool ghosts = (p.flags & (HDEM_FILL_GHOST_TOP | HDEM_FILL_GHOST_BOTTOM)) != 0;
+    const float *const coarse_given = c.armed.coarse;
+    // A caller's coarse raster must cover the raster: the start kernels index it without a
+    // bound.  (With a row map the rows are the caller's: the map lives on the device.)
+    if (coarse_given) {
+        const int last_col = (W - 1) >> c.armed.shift, last_row = (H - 1) >> c.armed.shift;
+        HDEM_REQUIRE(last_col < c.armed.cw && (c.armed.row_map || last_row < c.armed.ch),
+                     HDEM_ERR_BAD_ARG,
+                     "the coarse start, %d x %d blocks of %d, does not cover the %d x %d raster",
+                     c.armed.ch, c.armed.cw, 1 << c.armed.shift, H, W);
+    }
     // hub start: the single-GPU INIT default from HUB_MIN_TILES tiles on; or the levels a
     // row-block partition worked out for this block (hdem_set_fill_hub_levels)
-    const float *const hub_given = ctx->hub_levels_given;
-    ctx->hub_levels_given = nullptr;
+    const float *const hub_given = c.armed.hub_levels;
     if (hub_given) {
         HDEM_REQUIRE(!(p.flags & HDEM_FILL_WARM) && c.eps == 0.0f && p.use_async &&
                          ctx->hub_prep_z == c.z && ctx->hub_prep_w == c.w && ctx->hub_prep_h == H &&
@@ -2046,7 +2098,7 @@ int fill_choose_start(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, c
         s->hub_lev = hub_given;
     } else if (p.flags & HDEM_FILL_WARM) {
         s->kind = START_WARM;
-    } else if (c.eps == 0.0f && !ctx->start_coarse && p.use_async && !ghosts &&
+    } else if (c.eps == 0.0f && !coarse_given && p.use_async && !ghosts &&
                // (NO_COARSE is the caller's "start from +inf"; the fill of a hub raster -- depth
                // 1 -- carries it only to keep the block-maximum start out, and may take a hub
                // start of its own, whose raster -- depth 2 -- is filled plainly)
@@ -2054,17 +2106,19 @@ int fill_choose_start(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, c
                H >= 3 && W >= 3 &&
                (int64_t)((W - 2 + FT - 1) / FT) * ((H - 2 + FT - 1) / FT) >=
                    (c.depth ? kn.hub_min_tiles_nested : kn.hub_min_tiles)) {
+        // (hub_buf[0] is also where hdem_fill_hub_prepare_dev keeps its rim lines)
+        if (c.depth == 0) ctx->hub_prep_lines = false;
         if (int rc = hub_alloc(ctx, c.depth, H, W, &s->hubs)) return rc;
         s->kind = START_HUB_OWN;
         s->hub_lev = s->hubs.lev;
-    } else if (c.eps == 0.0f || (kn.eps_coarse && !ctx->start_coarse)) {
+    } else if (c.eps == 0.0f || (kn.eps_coarse && !coarse_given)) {
         // coarse start (eps > 0: only on request, see fill_coarse_presolve)
-        if (ctx->start_coarse) {
+        if (coarse_given) {
             s->kind = START_COARSE_GIVEN;
-            s->coarse = ctx->start_coarse;
-            s->row_map = ctx->start_row_map;
-            s->cw = ctx->start_cw;
-            s->shift = ctx->start_shift;
+            s->coarse = coarse_given;
+            s->row_map = c.armed.row_map;
+            s->cw = c.armed.cw;
+            s->shift = c.armed.shift;
         } else if (p.use_async && !(p.flags & HDEM_FILL_NO_COARSE) && !ghosts &&
                    (int64_t)H * W >= kn.coarse_min_cells) {
             s->kind = START_COARSE_OWN;
@@ -2453,8 +2507,6 @@ int fill_run(hdem_ctx *ctx, const fill_knobs &kn, const fill_call &c, fill_outco
     if (int rc = fill_choose_start(ctx, kn, c, p, &start)) return rc;
     if (start.kind == START_COARSE_OWN)
         if (int rc = fill_coarse_presolve(ctx, kn, c, &start)) return rc;
-    ctx->start_coarse = nullptr;                // a caller's coarse raster is used once
-    ctx->start_row_map = nullptr;
     fill_ws ws;
     if (int rc = fill_workspace(ctx, kn, c, start, &p, &ws)) return rc;
     if (int rc = fill_write_start(ctx, kn, c, p, start, ws)) return rc;
@@ -2473,8 +2525,9 @@ extern "C" int hdem_sinkfill_f32_dev(hdem_ctx *ctx, const float *z, int H, int W
 {
     HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
     fill_outcome unused;
-    return fill_run(ctx, fill_read_knobs(),
-                    {z, H, W, eps, max_rounds, flags, w, stats, nullptr, 0, FILL_CALLER}, &unused);
+    const fill_call call = {z, H, W, eps, max_rounds, flags, w, stats, nullptr, 0, FILL_CALLER,
+                            fill_take_armed(ctx)};
+    return fill_run(ctx, fill_read_knobs(), call, &unused);
 }
 
 // rows 0 and H-1, columns 0 and W-1 of a D8 raster: no direction on the raster ring
@@ -2490,11 +2543,11 @@ extern "C" int hdem_sinkfill_d8_f32_dev(hdem_ctx *ctx, const float *z, int H, in
                                         hdem_fill_stats *stats)
 {
     HDEM_REQUIRE(ctx, HDEM_ERR_BAD_ARG, "ctx is null");
+    const fill_call call = {z, H, W, eps, max_rounds, flags, w, stats, d8, 0, FILL_CALLER,
+                            fill_take_armed(ctx)};
     if (int rc = hdem_check_raster(z, d8, H, W)) return rc;
     fill_outcome got;
-    if (int rc = fill_run(ctx, fill_read_knobs(),
-                          {z, H, W, eps, max_rounds, flags, w, stats, d8, 0, FILL_CALLER}, &got))
-        return rc;
+    if (int rc = fill_run(ctx, fill_read_knobs(), call, &got)) return rc;
     if (!got.d8_done)                   // no certifying pass over every tile: the plain kernel
         return hdem_d8_f32_dev(ctx, w, H, W, d8);
     if (!got.d8_ring_done)              // (tile visits write tile interiors only)
@@ -2520,6 +2573,7 @@ extern "C" int hdem_set_fill_coarse_start(hdem_ctx *ctx, const float *coarse_fil
     while ((1 << shift) < block) ++shift;
     ctx->start_coarse = coarse_filled;
     ctx->start_row_map = row_map;
+    ctx->start_ch = ch;
     ctx->start_cw = cw;
     ctx->start_shift = shift;
     return HDEM_OK;

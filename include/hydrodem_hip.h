@@ -74,7 +74,10 @@ int hdem_synchronize(hdem_ctx *ctx);
  * hdem_trim gives the cached blocks (and the scratch buffers the context keeps between calls)
  * back to the device -- for a process that shares the GPU with another allocator (a second
  * context, torch); every allocation the library makes for itself does the same before it
- * reports HDEM_ERR_OOM.  *released (may be NULL): bytes returned. */
+ * reports HDEM_ERR_OOM.  *released (may be NULL): bytes returned.  hdem_trim is safe at any
+ * point between two calls: what a later call still needs stays.  While a hub start is prepared
+ * (hdem_fill_hub_prepare_dev, until the fill that takes its levels) the buffer that holds it is
+ * not freed and its bytes are not counted in *released. */
 int hdem_malloc(hdem_ctx *ctx, size_t bytes, void **dptr);
 int hdem_free(hdem_ctx *ctx, void *dptr);
 int hdem_trim(hdem_ctx *ctx, size_t *released);
@@ -267,7 +270,16 @@ int hdem_fill_seam_apply_dev(hdem_ctx *ctx, float *w, int H, int W, const float 
  *   hdem_set_fill_hub_levels    the filled levels of this block's part of the stacked raster
  *                               (same shape), for the next INIT fill of the same z / w: that fill
  *                               skips its own start-value work; with GHOST_GIVEN the ghost rows
- *                               of w are the caller's upper bounds.  Used once. */
+ *                               of w are the caller's upper bounds.  Used once: the next call of
+ *                               hdem_sinkfill_f32_dev or hdem_sinkfill_d8_f32_dev on this context
+ *                               takes them, whether it is refused or not (a
+ *                               fill of another z / w, shape or kind is refused).
+ * A context holds one preparation, in a buffer that its own fills use too.  When a fill that
+ * takes a hub start of its own, or a preparation of another block, has used that buffer since
+ * the prepare, hdem_fill_hub_raster_dev returns HDEM_ERR_BAD_ARG ("the prepared hub start was
+ * overwritten") and drops the preparation: prepare again.  Once the raster is made the buffer is
+ * free: the fill of the (stacked) hub raster may take a hub start of its own, and
+ * hdem_set_fill_hub_levels and the fill behind it work as before. */
 int hdem_fill_hub_prepare_dev(hdem_ctx *ctx, const float *z, int H, int W, int flags, float *w);
 int hdem_fill_hub_raster_dev(hdem_ctx *ctx, float *raster);
 int hdem_set_fill_hub_levels(hdem_ctx *ctx, const float *levels);
@@ -277,7 +289,13 @@ int hdem_set_fill_hub_levels(hdem_ctx *ctx, const float *levels);
  * free cells (and ghost rows) start at max(z, coarse level of their block).  row_map
  * (device, H ints, or NULL for y / block) gives the coarse row of each raster row: a row
  * block of a partitioned raster points into the stacked coarse raster of all ranks.
- * Used once; NULL clears it. */
+ * The fill that takes the start returns HDEM_ERR_BAD_ARG, before any launch, when the coarse
+ * raster does not cover its raster: (W - 1) / block >= cw, or -- without a row map --
+ * (H - 1) / block >= ch.  With a row map the rows cannot be checked on the host: every entry
+ * of the map must be in 0 .. ch - 1, which is the caller's responsibility.
+ * Used once: the next call of hdem_sinkfill_f32_dev or hdem_sinkfill_d8_f32_dev on this
+ * context takes it, whether it is refused or not, and whether it is a call
+ * that can start from it or not; NULL clears it. */
 int hdem_set_fill_coarse_start(hdem_ctx *ctx, const float *coarse_filled, int ch, int cw,
                                int block, const int32_t *row_map);
 

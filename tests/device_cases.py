@@ -15,6 +15,8 @@ partial one,
     destripe (split inverse)                                                 (150, 168), (256, 256)
     FFTs and the other single steps of the Fourier chain                     (141, 155)
     fill and fill + D8 (the second takes the hub start)                      (200, 333), (519, 508)
+    the fill's protocols: a caller's hub start, coarse start, seam rows      (519, 508), (200, 333),
+                                                                             (130, 197)
 
 A case is ``Case(name, shapes, build, run, check, own, schedule)`` of test_gpu_scribble:
 ``build(shape, seed)`` makes the host inputs, ``run(call, inputs)`` makes the device calls through
@@ -40,6 +42,7 @@ import numpy as np
 
 import test_gpu_dinf as DI
 import test_gpu_dinfsum as DS
+import test_gpu_elevation_regimes as ER
 import test_gpu_flowpath as FP
 import test_gpu_flowsum as FS
 import test_gpu_proximity as PX
@@ -50,6 +53,7 @@ import test_gpu_terrain_attributes as TA
 import test_gpu_upextreme as UE
 import test_gpu_zonal as ZO
 from hydrodem_amd import backend as B
+from oracle import c_oracle
 from test_gpu_scribble import Case
 
 D8_SHAPE, WINDOW_SHAPE, TERRAIN_SHAPE, FFT_SHAPE = (130, 197), (131, 157), (33, 257), (141, 155)
@@ -161,6 +165,148 @@ def _check_memset(inp, got):
     assert got["x"].tobytes() == want.tobytes()
 
 
+# ---------------------------------------------------------------------------
+# the sink fill's protocols: what one call tells the context for a later one
+# ---------------------------------------------------------------------------
+FILL_TILE = 62                    # tile edge of the fill (hdem_fill_stats.tile_h)
+HUB_WALL = 3.0e38                 # a wall of the hub raster (hdem_sinkfill.hip, partition.HUB_BIG)
+COARSE_BLOCK = 16
+# the rows of _seam_inputs a variant receives as (top, bottom); None: no such neighbour
+SEAM_ROWS = {"both": ("top_zeros", "bot_same"), "top": ("top_same", None), "none": (None, None)}
+SEAM_PENDING, SEAM_PRESET = (-1, 0, 3), (0, 1)
+
+
+def hub_raster_shape(shape):
+    """(2 ty + 1, 2 tx + 1) of include/hydrodem_hip.h."""
+    return tuple(2 * -(-(n - 2) // FILL_TILE) + 1 for n in shape)
+
+
+def _assert_fill_and_codes(inp, got):
+    want = c_oracle.sinkfill_pflood(inp["z"])
+    assert got["filled"].dtype == np.float32 and S.equal(got["filled"], want)
+    assert got["codes"].dtype == np.uint8 and S.equal(got["codes"], c_oracle.d8(want))
+    return want
+
+
+def _run_hub_given(call, inp):
+    """The hub start of a partition of one block, every step of partition.hub_start."""
+    z = call.up(inp["z"])
+    ctx, shape = z.ctx, hub_raster_shape(z.shape)
+    w = call.empty(z.shape, np.float32)
+    ctx.fill_hub_prepare(z.ptr, z.shape[0], z.shape[1], 0, w.ptr)
+    d = w.to_host()                        # (the ring of w is nobody's yet: the raster's, below)
+    raster = call.empty(shape, np.float32)
+    ctx.fill_hub_raster(raster.ptr)
+    levels, _ = B.sinkfill_dev(raster, out=call.empty(shape, np.float32),
+                               flags=B.FILL_INIT | B.FILL_NO_VERIFY)
+    ctx.set_fill_hub_levels(levels.ptr)
+    out, codes, stats = B.sinkfill_d8_dev(z, out=w, codes=call.out(z.shape, np.uint8),
+                                          flags=B.FILL_INIT)
+    d[0], d[-1], d[:, 0], d[:, -1] = inp["z"][0], inp["z"][-1], inp["z"][:, 0], inp["z"][:, -1]
+    return {"raster": call.host(raster), "levels": call.host(levels), "d": d,
+            "filled": call.host(out), "codes": call.host(codes)}, stats
+
+
+def _check_hub_given(inp, got):
+    """The oracle's bits, and the start values the levels stand for -- max(d, level of the
+    cell's tile), an outlet tile (NaN) keeping d -- as upper bounds of the fill."""
+    z = inp["z"]
+    want = _assert_fill_and_codes(inp, got)
+    assert got["raster"].shape == got["levels"].shape == hub_raster_shape(z.shape)
+    level = got["levels"][1::2, 1::2].copy()
+    level[level >= HUB_WALL] = np.inf
+    level = np.repeat(np.repeat(level, FILL_TILE, 0), FILL_TILE, 1)[:z.shape[0] - 2, :z.shape[1] - 2]
+    u, d = got["d"].copy(), got["d"][1:-1, 1:-1]
+    with np.errstate(invalid="ignore"):
+        u[1:-1, 1:-1] = np.where(np.isnan(level) | np.isnan(d), d, np.maximum(d, level))
+    ER.assert_bounds(u, want)
+    assert np.isfinite(got["levels"][1::2, 1::2]).any()          # (there were levels to use)
+
+
+def _run_coarse_given(call, inp):
+    z = call.up(inp["z"])
+    shape = tuple(-(-n // COARSE_BLOCK) for n in z.shape)
+    coarse = B.blockmax_dev(z, COARSE_BLOCK, out=call.empty(shape, np.float32))
+    cfill, _ = B.sinkfill_dev(coarse, out=call.empty(shape, np.float32))
+    z.ctx.set_fill_coarse_start(cfill.ptr, shape[0], shape[1], COARSE_BLOCK, None)
+    out, codes, stats = B.sinkfill_d8_dev(z, out=call.out(z.shape, np.float32),
+                                          codes=call.out(z.shape, np.uint8))
+    return {"coarse": call.host(cfill), "filled": call.host(out), "codes": call.host(codes)}, stats
+
+
+def _check_coarse_given(inp, got):
+    z = inp["z"]
+    want = _assert_fill_and_codes(inp, got)
+    level = np.repeat(np.repeat(got["coarse"], COARSE_BLOCK, 0), COARSE_BLOCK, 1)
+    u = np.maximum(z, level[:z.shape[0], :z.shape[1]])
+    u[0], u[-1], u[:, 0], u[:, -1] = z[0], z[-1], z[:, 0], z[:, -1]
+    ER.assert_bounds(u, want)
+
+
+def _seam_inputs(shape, seed):
+    """A deferred block and the rows its neighbours send.  Rows 0 and H-1 hold a NaN, a -0.0 and
+    a +0.0.  ``top_zeros`` is row 0 with the signs of its zeros swapped: equal values, other
+    bits.  ``top_same`` / ``bot_same`` are the rows themselves: the NaN is no equal value, and
+    the same bits."""
+    rng = np.random.default_rng([seed, *shape])
+    w = (rng.standard_normal(shape) * 100).astype(np.float32)
+    for row in (0, shape[0] - 1):
+        w[row, 5], w[row, 70], w[row, shape[1] - 3] = np.nan, -0.0, 0.0
+    top_zeros = w[:1].copy()
+    top_zeros[0, 70], top_zeros[0, shape[1] - 3] = 0.0, -0.0
+    return {"w": w, "top_zeros": top_zeros, "top_same": w[:1].copy(), "bot_same": w[-1:].copy()}
+
+
+def _run_seam_apply(call, inp):
+    fresh = call.up(inp["w"])
+    ctx, (H, W) = fresh.ctx, fresh.shape
+    w = call.empty(fresh.shape, np.float32)
+    sent = {name: call.up(inp[name]) for name in ("top_zeros", "top_same", "bot_same")}
+    got = {}
+    for rows, (top, bot) in SEAM_ROWS.items():
+        for pending in SEAM_PENDING:
+            for preset in SEAM_PRESET:
+                ctx.check(ctx.lib.hdem_memcpy_d2d(ctx.handle, w.ptr, fresh.ptr, fresh.nbytes))
+                words = call.up(np.full((1, 4), preset, np.uint32))
+                ctx.fill_seam_apply(w.ptr, H, W, sent[top].ptr if top else 0,
+                                    sent[bot].ptr if bot else 0, pending, words.ptr)
+                got[f"w-{rows}-{pending}-{preset}"] = w.to_host()
+                got[f"words-{rows}-{pending}-{preset}"] = call.host(words)
+    return got, None
+
+
+def _check_seam_apply(inp, got):
+    """include/hydrodem_hip.h on hdem_fill_seam_apply_dev, in NumPy."""
+    bits = lambda row: row.view(np.uint32)
+    assert len(got) == 2 * len(SEAM_ROWS) * len(SEAM_PENDING) * len(SEAM_PRESET)
+    for rows, names in SEAM_ROWS.items():
+        top, bot = (None if name is None else inp[name] for name in names)
+        want_w = inp["w"].copy()
+        changed = [0, 0]
+        for k, (row, sent) in enumerate(((0, top), (-1, bot))):
+            if sent is not None:
+                changed[k] = int((bits(sent[0]) != bits(want_w[row])).any())
+                want_w[row] = sent[0]
+        assert changed == {"both": [1, 0], "top": [0, 0], "none": [0, 0]}[rows]
+        for pending in SEAM_PENDING:
+            for preset in SEAM_PRESET:
+                what = f"{rows}-{pending}-{preset}"
+                queued = int(pending > 0) if pending >= 0 else int(preset != 0)
+                want_words = [queued, *changed, int(bool(queued or any(changed)))]
+                assert got["words-" + what].ravel().tolist() == want_words, what
+                assert got["w-" + what].tobytes() == want_w.tobytes(), what
+
+
+FILL_PROTOCOL_CASES = [
+    Case("fill-hub-given", (FILL_SHAPES[1],), S.dem_of(False), _run_hub_given, _check_hub_given,
+         True, frozenset(S.FILL_SCHEDULE)),
+    Case("fill-coarse-given", (FILL_SHAPES[0],), S.dem_of(False), _run_coarse_given,
+         _check_coarse_given, True, frozenset(S.FILL_SCHEDULE)),
+    Case("fill-seam-apply", (D8_SHAPE,), _seam_inputs, _run_seam_apply, _check_seam_apply, False,
+         frozenset()),
+]
+
+
 # (132 x 156 floats: the copy kernel moves 16 bytes a lane and takes whole lanes only)
 BYTE_CASES = [Case("copy_rate", ((132, 156),), _bytes_of, _run_copy, _check_copy, True, frozenset()),
               Case("memset", ((132, 156),), _bytes_of, _run_memset, _check_memset, False,
@@ -183,21 +329,14 @@ ENTRIES = [Entry(entry, _shapes_of(entry.name)) for entry in S.CASES] + [
     Entry(DS.POISON_CASE, (D8_SHAPE,)),
     Entry(ZO.POISON_CASE, (D8_SHAPE,)),
     Entry(SN.POISON_CASE, (D8_SHAPE,)),
-] + [Entry(entry, entry.shapes) for entry in BYTE_CASES]
+] + [Entry(entry, entry.shapes) for entry in FILL_PROTOCOL_CASES + BYTE_CASES]
 
 PARAMS = [(e.case, shape) for e in ENTRIES for shape in e.shapes]
 IDS = [f"{case.name}-{shape[0]}x{shape[1]}" for case, shape in PARAMS]
 
-# Reached by no case, each with its reason: they are the partition's seam exchange and its hub
-# start, meaningful only between the row blocks of one fill that ``partition.py`` drives; the
-# partition tests hold them to the whole-raster fill.
-ALLOWED = {
-    "hdem_fill_seam_apply_dev": "writes a neighbour block's rows into the ghost rows of a "
-                                "deferred fill: needs the partition's exchange around it",
-    "hdem_fill_hub_prepare_dev": "prepares the hub start of one row block for the levels the "
-                                 "partition works out across blocks",
-    "hdem_fill_hub_raster_dev": "reads back what hdem_fill_hub_prepare_dev prepared",
-}
+# Reached by no case, each with its reason.  Empty: the partition's seam exchange and its hub
+# start, once excused here, are the fill's protocol cases above.
+ALLOWED = {}
 
 
 # ---------------------------------------------------------------------------
