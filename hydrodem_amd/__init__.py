@@ -33,6 +33,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      DInfFlowDirection, DInfFlowAccumulation, DemToDInfArea,
                                      WeightedDInfFlowAccumulation, AreaWetnessIndex,
                                      DemToDInfWetness,
+                                     DInfDistanceDown, DInfHeightAboveDrainage, DemToDInfHAND,
                                      MFDFlowDirection, MFDFlowAccumulation, DemToMFDArea,
                                      EuclideanDistance, EuclideanAllocation, BurnStreams,
                                      ResolveFlats,

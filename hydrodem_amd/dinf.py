@@ -1,12 +1,13 @@
 """
 D-infinity flow direction, accumulation and weighted accumulation (``hdem_dinf_f32`` /
-``hdem_dinfacc_u32`` / ``hdem_dinfsum_u32`` and their ``_dev`` twins): the binding, written once
-for host arrays and device rasters with the two sides of :mod:`hydrodem_amd.backend`, and the
-host helpers for the D-infinity word.
+``hdem_dinfacc_u32`` / ``hdem_dinfsum_u32`` and their ``_dev`` twins) and distance down
+(``hdem_dinfdist_u32``, one symbol that takes device pointers by a flag): the binding, written
+once for host arrays and device rasters with the two sides of :mod:`hydrodem_amd.backend`, and
+the host helpers for the D-infinity word.
 
 The word, one uint32 per cell: ``q`` in bits 0-15 (0 ... 32768, the share of the diagonal
 receiver in units of 2^-15), the facet in bits 16-19 (0: no outflow; 1 ... 8 as in Tarboton 1997,
-``FACETS``).  ``include/hydrodem_hip.h`` (A20, A21, A22) has the contract.
+``FACETS``).  ``include/hydrodem_hip.h`` (A20, A21, A22, A26) has the contract.
 """
 # pylint: disable=protected-access,too-many-arguments
 
@@ -33,6 +34,9 @@ D8_EIGHTHS = {1: 0, 128: 1, 64: 2, 32: 3, 16: 4, 8: 5, 4: 6, 2: 7}
 OUTPUTS = (("sum", np.int64), ("value", np.float32))    # in the order of the C ABI's pointers
 EXTRAS = ("angle", "slope")                             # float32, optional, of the direction
 TOTAL_LIMIT = 2 ** 48       # the quantised weights of a raster sum to less than this
+ON_DEVICE = 0x40000000      # HDEM_ON_DEVICE
+DIST_KINDS = {"horizontal": 0, "vertical": 1, "surface": 2}         # HDEM_DD_*
+DIST_STATISTICS = {"average": 0, "minimum": 1, "maximum": 2}
 
 
 # ---------------------------------------------------------------------------
@@ -299,3 +303,96 @@ def dinfsum(words, weights, frac_bits=16, want=("value",)):
     """Weighted D-infinity flow accumulation of host arrays (``hdem_dinfsum_u32``; see
     :func:`dinfsum_dev`): ``{name: ndarray}`` and the stats dict."""
     return _dinfsum(backend._HOST, words, weights, frac_bits, want, None)
+
+
+# ---------------------------------------------------------------------------
+# distance down (A26): one C symbol, host or device pointers by a flag
+# ---------------------------------------------------------------------------
+def dinfdist_args(words, streams=None, threshold=None, dem=None, cellsize=1.0,
+                  kind="horizontal", statistic="average"):
+    """The checks of the distance down that need no device: ``words``, ``streams`` and ``dem``
+    are anything with ``dtype`` and ``shape``.  Returns the kind, the statistic, the stream kind
+    and the threshold for the C call, and ``(dx, dy)``."""
+    if words is None:
+        raise ValueError("D-infinity distance down needs the words it follows")
+    shape = backend._check(words, np.uint32, "D-infinity distance down takes",
+                           "uint32 D-infinity words", flat="D-infinity distance down takes")
+    if shape[0] * shape[1] > 0xFFFFFFFF:
+        raise ValueError(f"D-infinity distance down works in uint32: {shape[0]} x {shape[1]} "
+                         "cells is more than 2^32 - 1")
+    if not isinstance(kind, str) or kind not in DIST_KINDS:
+        raise ValueError(f"kind is one of {list(DIST_KINDS)}, got {kind!r}")
+    if not isinstance(statistic, str) or statistic not in DIST_STATISTICS:
+        raise ValueError(f"statistic is one of {list(DIST_STATISTICS)}, got {statistic!r}")
+    if streams is None:
+        stream_kind = backend.FT_STREAMS_NONE
+        if threshold is not None:
+            raise ValueError("a threshold needs the uint32 raster it applies to")
+        threshold = 0
+    else:
+        backend._check(streams, None, "streams are", like=("the words", shape))
+        if np.dtype(streams.dtype) == np.uint8:
+            stream_kind = backend.FT_STREAMS_MASK_U8
+            if threshold is not None:
+                raise ValueError("a uint8 stream mask takes no threshold")
+            threshold = 0
+        elif np.dtype(streams.dtype) == np.uint32:
+            stream_kind = backend.FT_STREAMS_ACC_U32
+            if threshold is None:
+                raise ValueError("a uint32 stream raster needs a threshold")
+            if isinstance(threshold, bool) or int(threshold) != threshold or \
+                    not 1 <= int(threshold) <= 0xFFFFFFFF:
+                raise ValueError(f"threshold is an integer in 1 ... 2^32 - 1, got {threshold!r}")
+            threshold = int(threshold)
+        else:
+            raise ValueError("streams are a uint8 mask or a uint32 raster with a threshold, "
+                             f"got {streams.dtype}")
+    if kind == "horizontal":
+        if dem is not None:
+            raise ValueError("the horizontal distance takes no dem")
+    elif dem is None:
+        raise ValueError(f"the {kind} distance needs the dem it is measured on")
+    else:
+        backend._check(dem, np.float32, "the dem is", like=("the words", shape))
+    return DIST_KINDS[kind], DIST_STATISTICS[statistic], stream_kind, threshold, \
+        cellsizes(cellsize)
+
+
+def _dinfdist(side, words, streams, threshold, dem, cellsize, kind, statistic, out):
+    words = side.take("words", words, required=True)
+    streams, dem = side.take("streams", streams, mask=True), side.take("dem", dem)
+    kind, statistic, stream_kind, threshold, (dx, dy) = dinfdist_args(
+        words, streams, threshold, dem, cellsize, kind, statistic)
+    if out is not None:
+        backend._check(out, np.float32, "out is", like=("the words", tuple(words.shape)))
+    c = side.context(words)
+    st = backend._DInfDistStats()
+    with contextlib.ExitStack() as stack:
+        distance = side.result(stack, out, words.shape, np.float32, c)
+        c.check(c.lib.hdem_dinfdist_u32(
+            c.handle, side.address(words), *words.shape, side.address(streams), stream_kind,
+            threshold, side.address(dem), dx, dy, kind, statistic, side.address(distance),
+            ON_DEVICE if side.device else 0, ctypes.byref(st)))
+    return distance, st.as_dict()
+
+
+def dinfdist_dev(words, streams=None, threshold=None, dem=None, cellsize=1.0, kind="horizontal",
+                 statistic="average", out=None):
+    """D-infinity distance down of a uint32 word raster (``hdem_dinfdist_u32`` with
+    ``HDEM_ON_DEVICE``): for every cell the distance along its D-infinity paths to the stop set,
+    float32, NaN where a path ends without a stop.  ``streams``: ``None`` (the stops are the cells
+    with facet 0), a uint8 mask raster, or a uint32 raster with ``threshold`` (a stop where
+    ``>= threshold``).  ``kind``: ``horizontal``, ``vertical`` or ``surface`` (the last two need
+    the float32 ``dem``); ``statistic``: ``average`` (weighted by the flow proportions),
+    ``minimum`` or ``maximum``.  ``cellsize``: a number or ``(dx, dy)``.  ``out``: a float32 raster
+    to write into.  Returns the raster and the stats dict.  Synchronises once per round."""
+    return _dinfdist(backend._DEVICE, words, streams, threshold, dem, cellsize, kind, statistic,
+                     out)
+
+
+def dinfdist(words, streams=None, threshold=None, dem=None, cellsize=1.0, kind="horizontal",
+             statistic="average"):
+    """D-infinity distance down of host arrays (``hdem_dinfdist_u32``; see :func:`dinfdist_dev`):
+    the float32 array and the stats dict.  A bool ``streams`` array is a mask."""
+    return _dinfdist(backend._HOST, words, streams, threshold, dem, cellsize, kind, statistic,
+                     None)

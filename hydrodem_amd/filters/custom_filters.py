@@ -28,10 +28,10 @@ New operators (the reference has neither): ``SinkFill``,
 ``UpstreamExtreme``, ``BreachDepressions``, ``Watersheds``, ``FlowDistance``,
 ``FlowPathSum``, ``FlowPathExtreme``, ``HeightAboveDrainage``, ``UpstreamFlowLength``,
 ``StreamOrder``, ``StreamNetwork``, ``DInfFlowDirection``, ``DInfFlowAccumulation``,
-``WeightedDInfFlowAccumulation``, ``AreaWetnessIndex``, ``MFDFlowDirection``,
-``MFDFlowAccumulation`` and the chains ``DemToHAND``, ``DemToStreamOrder``,
-``DemToStreamNetwork``, ``DemToDInfArea``, ``DemToDInfWetness`` and ``DemToMFDArea``, shaped like
-every other ``Filter``.
+``WeightedDInfFlowAccumulation``, ``AreaWetnessIndex``, ``DInfDistanceDown``,
+``DInfHeightAboveDrainage``, ``MFDFlowDirection``, ``MFDFlowAccumulation`` and the chains
+``DemToHAND``, ``DemToStreamOrder``, ``DemToStreamNetwork``, ``DemToDInfArea``,
+``DemToDInfWetness``, ``DemToDInfHAND`` and ``DemToMFDArea``, shaped like every other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -2356,6 +2356,149 @@ class DemToDInfWetness(ComposedFilter):  # pylint: disable=too-few-public-method
                 self.dinf_slope = dinf_slope
                 stack.pop_all()                     # the caller's to free from here on
             return outs["twi"]
+
+
+class DInfDistanceDown(Filter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """D-infinity distance down (new operator; TauDEM ``dinfdistdown``).  Input: a uint32 H x W
+    raster of D-infinity words as ``DInfFlowDirection`` returns them.  Returns float32: the
+    distance from every cell down its D-infinity paths to the first *stop*, NaN where a path ends
+    without one.  A stop cell reads 0.  A cell with one receiver adds its step to the receiver's
+    distance; a cell with two combines the two sums by ``statistic``.
+
+    ``kind``: ``"horizontal"`` (``dx`` / ``dy`` / the diagonal per step), ``"vertical"`` (the
+    drop ``dem[c] - dem[r]`` per step: the height above the stop) or ``"surface"``
+    (``sqrt(h^2 + v^2)`` per step); the last two need ``dem``, a float32 array or
+    ``DeviceRaster`` of the words' shape.  ``statistic``: ``"average"`` weights the two receivers
+    by their flow proportions and is NaN unless *every* path reaches a stop (TauDEM's rule);
+    ``"maximum"`` is NaN in the same cells; ``"minimum"`` is the shortest way and NaN only where
+    no path reaches a stop.  ``streams``: ``None`` (a stop is a cell without outflow: the
+    distance to the outlet), a bool / uint8 mask, a uint32 raster with ``threshold`` (a stop where
+    ``>= threshold``: a D8 ``FlowAccumulation`` result goes in as it is), or a ``DeviceRaster`` of
+    uint8 or uint32.  ``cellsize``: a number or ``(dx, dy)``.  All arithmetic is float64 in a
+    fixed order, rounded to float32 once: identical from run to run.
+
+    ``ValueError`` for operands of another type, dtype or shape, an unknown ``kind`` or
+    ``statistic``, a ``dem`` that is missing or (horizontal) not wanted, ``threshold`` without a
+    uint32 raster, with a mask, or < 1, a ``cellsize`` that is not finite and positive (all
+    before the device is touched), an invalid word, a receiver outside the raster, a cycle that
+    holds no stop cell (only user-supplied words can form one) and more than 2^32 - 1 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        stop_cells, unreached_cells (the NaN results), split_cells, terminal_cells, invalid,
+        outside, unresolved, rounds and tile_visits (these two depend on the schedule), tile_h /
+        tile_w of the last call; phase times when profiling is on.
+    """
+
+    auto_device = False     # the input is uint32 words, not a float32 raster
+
+    def __init__(self, kind="horizontal", statistic="average", streams=None, threshold=None,
+                 dem=None, cellsize=1.0):
+        self.streams = _Given(streams, "streams", (np.bool_, np.uint8, np.uint32)).value
+        self.dem = _Given(dem, "dem", (np.float32,)).value
+        self.kind, self.statistic = kind, statistic
+        self.threshold, self.cellsize = threshold, cellsize
+        self.stats = {}
+        # everything but the shapes: 1 x 1 stand-ins for the words and the operands
+        _dinf.dinfdist_args(np.zeros((1, 1), np.uint32), _Given(self.streams).stand_in(),
+                            threshold, _Given(self.dem).stand_in(), cellsize, kind, statistic)
+
+    def _check(self, words):
+        _dinf.dinfdist_args(words, self.streams, self.threshold, self.dem, self.cellsize,
+                            self.kind, self.statistic)
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        self._check(image_to_filter)
+        out, self.stats = _dinf.dinfdist(
+            image_to_filter, _Given(self.streams).host(), self.threshold,
+            _Given(self.dem).host(), self.cellsize, self.kind, self.statistic)
+        return out
+
+    def apply_device(self, raster):
+        self._check(raster)
+        with _Given(self.streams).device(raster.ctx) as streams, \
+                _Given(self.dem).device(raster.ctx) as dem:
+            out, self.stats = _dinf.dinfdist_dev(raster, streams, self.threshold, dem,
+                                                 self.cellsize, self.kind, self.statistic)
+        return out
+
+
+class DInfHeightAboveDrainage(DInfDistanceDown):  # pylint: disable=too-few-public-methods
+    """D-infinity height above the nearest drainage (new operator): ``DInfDistanceDown`` with
+    ``kind="vertical"`` and ``statistic="average"``.  Input: uint32 D-infinity words.  Returns
+    float32: the drop from the cell to the stream cells its flow reaches, averaged over the flow
+    proportions, and NaN where some of its flow ends without meeting a stream.
+
+    ``dem``: float32 array or ``DeviceRaster`` of the words' shape; ``streams``, ``threshold``,
+    ``cellsize``, the errors and ``stats`` as for ``DInfDistanceDown``."""
+
+    def __init__(self, *, dem, streams, threshold=None, cellsize=1.0):
+        if dem is None:
+            raise ValueError("DInfHeightAboveDrainage needs the dem it is measured on")
+        if streams is None:
+            raise ValueError("DInfHeightAboveDrainage needs streams (a mask, or a uint32 raster "
+                             "with a threshold)")
+        super().__init__("vertical", "average", streams, threshold, dem, cellsize)
+
+
+class DemToDInfHAND(ComposedFilter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """A float32 DEM to its D-infinity height above the nearest drainage in one device-resident
+    chain, the way TauDEM users make HAND: ``SinkFill(epsilon)`` and ``D8FlowDirection`` (one
+    call, as in ``HydroConditioning``), ``FlowAccumulation`` on the D8 codes,
+    ``DInfFlowDirection`` on the **filled** DEM with the codes as fallback, then the vertical
+    ``DInfDistanceDown`` on the filled DEM down to the cells whose D8 accumulation is
+    ``>= threshold``.  Nothing is downloaded in between.  ``flats`` as in ``DemToHAND``;
+    ``statistic`` and ``cellsize`` as in ``DInfDistanceDown``.
+
+    ``stats`` maps ``SinkFill``, ``FlowAccumulation``, ``DInfFlowDirection`` and
+    ``DInfDistanceDown`` (and ``ResolveFlats``) to the stats of their stage.  With
+    ``keep_partial_results=True`` the last call leaves ``filled``, ``codes``, ``accumulation``
+    and ``words``: host arrays after ``apply``, device rasters (the caller's to free) after
+    ``apply_device``; otherwise they are ``None``."""
+
+    def __init__(self, *, threshold, epsilon=1e-3, flats="keep", cellsize=1.0,
+                 statistic="average", keep_partial_results=False):
+        super().__init__()
+        self.flats = _check_flats(flats)
+        # the checks of the distance's operands, on stand-ins of the types the chain makes
+        DInfDistanceDown("vertical", statistic, np.zeros((1, 1), np.uint32), threshold,
+                         np.zeros((1, 1), np.float32), cellsize)
+        self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection(), FlowAccumulation(),
+                        DInfFlowDirection(cellsize=cellsize)]
+        self.threshold, self.cellsize, self.statistic = threshold, cellsize, statistic
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.filled = self.codes = self.accumulation = self.words = None
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("DemToDInfHAND", image_to_filter, np.float32, "a float32 DEM")
+        return _through_device(self, image_to_filter,
+                               ("filled", "codes", "accumulation", "words")
+                               if self.keep_partial_results else ())
+
+    def apply_device(self, raster):
+        _check_raster("DemToDInfHAND", raster, np.float32, "a float32 DEM")
+        fill, _, accumulate, direct = self.filters
+        self.filled = self.codes = self.accumulation = self.words = None
+        with contextlib.ExitStack() as stack:
+            filled, codes, resolve_stats = _fill_d8(stack, raster, fill, self.flats)
+            acc, accumulate.stats = backend.flowacc_dev(codes)
+            stack.enter_context(acc)
+            words, _, direct.stats = _dinf.dinf_dev(filled, self.cellsize, codes)
+            stack.enter_context(words)
+            hand, stats = _dinf.dinfdist_dev(words, acc, self.threshold, filled, self.cellsize,
+                                             "vertical", self.statistic)
+            self.stats = {"SinkFill": fill.stats, "FlowAccumulation": accumulate.stats,
+                          "DInfFlowDirection": direct.stats, "DInfDistanceDown": stats}
+            if resolve_stats is not None:
+                self.stats["ResolveFlats"] = resolve_stats
+            if self.keep_partial_results:
+                self.filled, self.codes, self.accumulation, self.words = filled, codes, acc, words
+                stack.pop_all()                     # the caller's to free from here on
+            return hand
 
 
 class MFDFlowDirection(Filter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes

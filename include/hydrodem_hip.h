@@ -1684,6 +1684,96 @@ int hdem_mfdacc_u64(hdem_ctx *ctx, const uint64_t *words, int H, int W, const vo
                     int weight_type, int frac_bits, int64_t *sum, float *value, int flags,
                     hdem_mfdacc_stats *stats);
 
+/* ---- A26  DInfDistanceDown.apply  (new operator: D-infinity distance down and HAND) ----
+ * TauDEM's dinfdistdown: the distance from every cell down its D-infinity paths to a stop set S,
+ * measured horizontally, vertically (the drop: with a stream set, the D-infinity height above the
+ * nearest drainage) or along the surface, and combined over the two receivers of a split cell
+ * as the average weighted by the flow proportions, the minimum or the maximum.
+ * words: uint32 H x W, the D-infinity words of A20, validated exactly as A21 validates them (the
+ * same refusals, the same counts, stop cells included).
+ * The stop set S is given as hdem_flowtrace_u8 (A7) takes its streams:
+ *   stream_kind == HDEM_FT_STREAMS_NONE     streams == NULL, threshold == 0: S is the cells with
+ *                                           facet 0 (the distance to the outlet)
+ *   stream_kind == HDEM_FT_STREAMS_MASK_U8  streams is uint8 H x W, non-zero = in S; threshold 0
+ *   stream_kind == HDEM_FT_STREAMS_ACC_U32  streams is uint32 H x W (a D8 accumulation as A2
+ *                                           writes it), in S where >= threshold; threshold >= 1
+ * dem: float32 H x W; required for HDEM_DD_VERTICAL and HDEM_DD_SURFACE, NULL for
+ * HDEM_DD_HORIZONTAL.  dx, dy: the cell's extent eastwards and northwards, finite and > 0.
+ *
+ * All arithmetic is float64, one rounding per operation, no fused multiply-add.
+ *   c in S:                       D[c] = 0, whatever its word: a cycle that holds a stop cell is
+ *                                 cut there, as A7 cuts it
+ *   c not in S, facet 0:          D[c] = NaN: its path ends without a stop
+ *   otherwise c has the cardinal receiver r1 with share 32768 - q and the diagonal receiver r2
+ *   with share q; a receiver whose share is 0 is no receiver.  The step to receiver i costs
+ *     HDEM_DD_HORIZONTAL   h_i = dx (E, W), dy (N, S), or diag = sqrt(dx * dx + dy * dy) for the
+ *                          diagonal, which the host works out once
+ *     HDEM_DD_VERTICAL     v_i = (double)dem[c] - (double)dem[r_i]
+ *     HDEM_DD_SURFACE      sqrt(h_i * h_i + v_i * v_i)
+ *   and a_i = cost_i + D[r_i].  Then
+ *     one receiver:                 D[c] = a_i
+ *     two, HDEM_DD_AVERAGE:         D[c] = ((double)(32768 - q) * a1 + (double)q * a2) * 2^-15
+ *                                   (two products, their sum, one product, in this order): NaN
+ *                                   if either a_i is NaN -- TauDEM's rule, a cell is reported
+ *                                   only if every path from it reaches a stop
+ *     two, HDEM_DD_MAXIMUM:         NaN if either a_i is NaN, else a2 > a1 ? a2 : a1
+ *     two, HDEM_DD_MINIMUM:         a2 if a1 is NaN, a1 if a2 is NaN (NaN if both are), else
+ *                                   a2 < a1 ? a2 : a1
+ *   distance[c] = (float)D[c].  Every NaN is stored as the one canonical quiet NaN (float64
+ *   0x7FF8000000000000 on the way, float32 0x7FC00000 in distance): one NaN bit pattern.
+ * A NaN or infinite elevation goes through this arithmetic as it is.  With one receiver
+ * everywhere (the canonical words of D8 codes) the three statistics agree bit for bit; the
+ * vertical distance is then a telescoping sum of float32 differences.
+ *
+ * A cell's value is a function of its receivers' final values alone, so the result is the same
+ * bits from run to run, whatever the schedule, and between host and device pointers.  The scheme
+ * is A21's with the dependency reversed -- classify (words validated, the working raster set to
+ * 0, NaN or "not final", every tile listed), rounds of tile visits (a 64 x 64 tile and its halo
+ * in LDS; a cell whose receivers are all final becomes final; a tile runs again when one of its
+ * eight neighbours finalised a frame cell in the round before), a streaming pass that writes
+ * distance.  The host reads one word per round.  The working raster is one uint64 per cell (the
+ * bits of D; "not final" is a reserved NaN pattern no result is stored as): 8 B per cell of the
+ * context's arena beside 16 B per tile.
+ * One symbol, as A24: host pointers (staged through device buffers of the context, synchronous),
+ * or device pointers with HDEM_ON_DEVICE in flags.
+ * HDEM_ERR_BAD_ARG before any launch: a null context, words or distance, a dem missing (vertical,
+ * surface) or surplus (horizontal), an unknown kind, statistic, stream_kind or flag, streams
+ * and threshold that do not go with the stream_kind (a threshold without an accumulation among
+ * them), dx or dy not finite and > 0, more than 2^32 - 1 cells.  After classify, with the count
+ * in the text: an invalid word, a receiver outside the raster.  After the last round: a cycle
+ * without a stop cell ("N cells never resolve"; only user-supplied words can form one; the rounds
+ * are bounded by H * W + 1).  distance is unspecified then.
+ * stats may be NULL; otherwise the caller sets stats->struct_size = sizeof(hdem_dinfdist_stats)
+ * first (96 bytes in this version; a shorter struct is filled as far as it goes).  rounds and
+ * tile_visits depend on the schedule; every other count does not. */
+#define HDEM_DD_HORIZONTAL 0
+#define HDEM_DD_VERTICAL 1
+#define HDEM_DD_SURFACE 2
+#define HDEM_DD_AVERAGE 0
+#define HDEM_DD_MINIMUM 1
+#define HDEM_DD_MAXIMUM 2
+typedef struct hdem_dinfdist_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_dinfdist_stats), set by the caller           */
+    int32_t rounds;          /* rounds of tile visits that had work                          */
+    int64_t tile_visits;     /* workgroups launched over all rounds                          */
+    int64_t split_cells;     /* cells with two receivers (0 < q < 32768)                     */
+    int64_t terminal_cells;  /* cells with facet 0                                           */
+    int64_t stop_cells;      /* cells of the stop set                                        */
+    int64_t unreached_cells; /* cells whose distance is NaN                                  */
+    int64_t invalid;         /* invalid words: refused                                       */
+    int64_t outside;         /* cells with a receiver outside the raster: refused            */
+    int64_t unresolved;      /* cells that never became final (a cycle without a stop): refused */
+    int32_t tile_h, tile_w;
+    float ms_classify;       /* (HIP events; profiling)                                      */
+    float ms_relax;          /* all rounds, the host reads included                          */
+    float ms_final;
+    int32_t reserved;        /* 0                                                            */
+} hdem_dinfdist_stats;       /* sizeof == 96 */
+int hdem_dinfdist_u32(hdem_ctx *ctx, const uint32_t *words, int H, int W, const void *streams,
+                      int stream_kind, uint32_t threshold, const float *dem, double dx, double dy,
+                      int kind, int statistic, float *distance, int flags,
+                      hdem_dinfdist_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
