@@ -34,6 +34,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      WeightedDInfFlowAccumulation, AreaWetnessIndex,
                                      DemToDInfWetness,
                                      DInfDistanceDown, DInfHeightAboveDrainage, DemToDInfHAND,
+                                     DInfDistanceUp, DemToDInfDistanceUp,
                                      MFDFlowDirection, MFDFlowAccumulation, DemToMFDArea,
                                      EuclideanDistance, EuclideanAllocation, BurnStreams,
                                      ResolveFlats,

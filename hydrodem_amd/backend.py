@@ -259,6 +259,19 @@ class _DInfDistStats(_SizedStats):
                 ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class _DInfDistUpStats(_SizedStats):
+    """``hdem_dinfdistup_stats`` (the binding is hydrodem_amd/dinf.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("rounds", ctypes.c_int32),
+                ("tile_visits", ctypes.c_int64), ("ridge_cells", ctypes.c_int64),
+                ("counted_links", ctypes.c_int64), ("ignored_links", ctypes.c_int64),
+                ("merge_cells", ctypes.c_int64), ("nan_cells", ctypes.c_int64),
+                ("invalid", ctypes.c_int64), ("outside", ctypes.c_int64),
+                ("unresolved", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_classify", ctypes.c_float), ("ms_relax", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 class _MFDStats(_SizedStats):
     """``hdem_mfd_stats`` (the binding is hydrodem_amd/mfd.py)."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("ms_total", ctypes.c_float),
@@ -440,6 +453,8 @@ SIGNATURES = {
     "hdem_mfdacc_u64": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _c.POINTER(_MFDAccStats)],
     "hdem_dinfdist_u32": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _vp, _c.c_double, _c.c_double,
                           _i, _i, _vp, _i, _c.POINTER(_DInfDistStats)],
+    "hdem_dinfdistup_u32": [_vp, _vp, _i, _i, _vp, _c.c_double, _c.c_double, _i, _i, _c.c_uint32,
+                            _vp, _i, _c.POINTER(_DInfDistUpStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

@@ -1,13 +1,13 @@
 """
 D-infinity flow direction, accumulation and weighted accumulation (``hdem_dinf_f32`` /
-``hdem_dinfacc_u32`` / ``hdem_dinfsum_u32`` and their ``_dev`` twins) and distance down
-(``hdem_dinfdist_u32``, one symbol that takes device pointers by a flag): the binding, written
-once for host arrays and device rasters with the two sides of :mod:`hydrodem_amd.backend`, and
-the host helpers for the D-infinity word.
+``hdem_dinfacc_u32`` / ``hdem_dinfsum_u32`` and their ``_dev`` twins), distance down and distance
+up (``hdem_dinfdist_u32``, ``hdem_dinfdistup_u32``: one symbol each that takes device pointers by
+a flag): the binding, written once for host arrays and device rasters with the two sides of
+:mod:`hydrodem_amd.backend`, and the host helpers for the D-infinity word.
 
 The word, one uint32 per cell: ``q`` in bits 0-15 (0 ... 32768, the share of the diagonal
 receiver in units of 2^-15), the facet in bits 16-19 (0: no outflow; 1 ... 8 as in Tarboton 1997,
-``FACETS``).  ``include/hydrodem_hip.h`` (A20, A21, A22, A26) has the contract.
+``FACETS``).  ``include/hydrodem_hip.h`` (A20, A21, A22, A26, A27) has the contract.
 """
 # pylint: disable=protected-access,too-many-arguments
 
@@ -396,3 +396,94 @@ def dinfdist(words, streams=None, threshold=None, dem=None, cellsize=1.0, kind="
     the float32 array and the stats dict.  A bool ``streams`` array is a mask."""
     return _dinfdist(backend._HOST, words, streams, threshold, dem, cellsize, kind, statistic,
                      None)
+
+
+# ---------------------------------------------------------------------------
+# distance up (A27): one C symbol, host or device pointers by a flag
+# ---------------------------------------------------------------------------
+def min_share_of(min_proportion=None, min_share=None):
+    """``min_share`` of the C call, 1 ... 32768 in units of 2^-15: the integer given as
+    ``min_share``, or ``max(1, ceil(min_proportion * 32768))`` of a ``min_proportion`` in (0, 1]
+    (0.5 when neither is given)."""
+    if min_share is not None:
+        if min_proportion is not None:
+            raise ValueError("give min_proportion or min_share, not both")
+        if isinstance(min_share, bool) or not isinstance(min_share, (int, np.integer)) or \
+                not 1 <= int(min_share) <= Q_ONE:
+            raise ValueError(f"min_share is an integer in 1 ... {Q_ONE}, got {min_share!r}")
+        return int(min_share)
+    if min_proportion is None:
+        min_proportion = 0.5
+    if isinstance(min_proportion, bool) or \
+            not isinstance(min_proportion, (int, float, np.integer, np.floating)) or \
+            not 0.0 < float(min_proportion) <= 1.0:
+        raise ValueError(f"min_proportion is a number in (0, 1], got {min_proportion!r}")
+    return max(1, math.ceil(float(min_proportion) * Q_ONE))
+
+
+def dinfdistup_args(words, dem=None, cellsize=1.0, kind="horizontal", statistic="average",
+                    min_proportion=None, min_share=None):
+    """The checks of the distance up that need no device: ``words`` and ``dem`` are anything
+    with ``dtype`` and ``shape``.  Returns the kind, the statistic and ``min_share`` for the C
+    call, and ``(dx, dy)``."""
+    if words is None:
+        raise ValueError("D-infinity distance up needs the words it follows")
+    shape = backend._check(words, np.uint32, "D-infinity distance up takes",
+                           "uint32 D-infinity words", flat="D-infinity distance up takes")
+    if shape[0] * shape[1] > 0xFFFFFFFF:
+        raise ValueError(f"D-infinity distance up works in uint32: {shape[0]} x {shape[1]} "
+                         "cells is more than 2^32 - 1")
+    if not isinstance(kind, str) or kind not in DIST_KINDS:
+        raise ValueError(f"kind is one of {list(DIST_KINDS)}, got {kind!r}")
+    if not isinstance(statistic, str) or statistic not in DIST_STATISTICS:
+        raise ValueError(f"statistic is one of {list(DIST_STATISTICS)}, got {statistic!r}")
+    share = min_share_of(min_proportion, min_share)
+    if kind == "horizontal":
+        if dem is not None:
+            raise ValueError("the horizontal distance takes no dem")
+    elif dem is None:
+        raise ValueError(f"the {kind} distance needs the dem it is measured on")
+    else:
+        backend._check(dem, np.float32, "the dem is", like=("the words", shape))
+    return DIST_KINDS[kind], DIST_STATISTICS[statistic], share, cellsizes(cellsize)
+
+
+def _dinfdistup(side, words, dem, cellsize, kind, statistic, min_proportion, min_share, out):
+    words = side.take("words", words, required=True)
+    dem = side.take("dem", dem)
+    kind, statistic, share, (dx, dy) = dinfdistup_args(words, dem, cellsize, kind, statistic,
+                                                       min_proportion, min_share)
+    if out is not None:
+        backend._check(out, np.float32, "out is", like=("the words", tuple(words.shape)))
+    c = side.context(words)
+    st = backend._DInfDistUpStats()
+    with contextlib.ExitStack() as stack:
+        distance = side.result(stack, out, words.shape, np.float32, c)
+        c.check(c.lib.hdem_dinfdistup_u32(
+            c.handle, side.address(words), *words.shape, side.address(dem), dx, dy, kind,
+            statistic, share, side.address(distance), ON_DEVICE if side.device else 0,
+            ctypes.byref(st)))
+    return distance, st.as_dict()
+
+
+def dinfdistup_dev(words, dem=None, cellsize=1.0, kind="horizontal", statistic="average",
+                   min_proportion=None, out=None, *, min_share=None):
+    """D-infinity distance up of a uint32 word raster (``hdem_dinfdistup_u32`` with
+    ``HDEM_ON_DEVICE``): for every cell the distance up its D-infinity paths to the ridge,
+    float32, over the neighbours that send it at least ``min_proportion`` of their flow; 0 in a
+    cell that no neighbour does.  ``kind``: ``horizontal``, ``vertical`` or ``surface`` (the last
+    two need the float32 ``dem``); ``statistic``: ``average`` (weighted by the entering shares),
+    ``minimum`` or ``maximum``.  ``min_proportion``: a number in (0, 1], 0.5 by default, taken as
+    ``min_share = max(1, ceil(min_proportion * 32768))``; ``min_share=`` gives the integer itself
+    (1 ... 32768), and not both.  ``cellsize``: a number or ``(dx, dy)``.  ``out``: a float32
+    raster to write into.  Returns the raster and the stats dict.  Synchronises once per round."""
+    return _dinfdistup(backend._DEVICE, words, dem, cellsize, kind, statistic, min_proportion,
+                       min_share, out)
+
+
+def dinfdistup(words, dem=None, cellsize=1.0, kind="horizontal", statistic="average",
+               min_proportion=None, *, min_share=None):
+    """D-infinity distance up of host arrays (``hdem_dinfdistup_u32``; see
+    :func:`dinfdistup_dev`): the float32 array and the stats dict."""
+    return _dinfdistup(backend._HOST, words, dem, cellsize, kind, statistic, min_proportion,
+                       min_share, None)

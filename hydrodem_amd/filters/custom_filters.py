@@ -29,9 +29,10 @@ New operators (the reference has neither): ``SinkFill``,
 ``FlowPathSum``, ``FlowPathExtreme``, ``HeightAboveDrainage``, ``UpstreamFlowLength``,
 ``StreamOrder``, ``StreamNetwork``, ``DInfFlowDirection``, ``DInfFlowAccumulation``,
 ``WeightedDInfFlowAccumulation``, ``AreaWetnessIndex``, ``DInfDistanceDown``,
-``DInfHeightAboveDrainage``, ``MFDFlowDirection``, ``MFDFlowAccumulation`` and the chains
-``DemToHAND``, ``DemToStreamOrder``, ``DemToStreamNetwork``, ``DemToDInfArea``,
-``DemToDInfWetness``, ``DemToDInfHAND`` and ``DemToMFDArea``, shaped like every other ``Filter``.
+``DInfHeightAboveDrainage``, ``DInfDistanceUp``, ``MFDFlowDirection``, ``MFDFlowAccumulation``
+and the chains ``DemToHAND``, ``DemToStreamOrder``, ``DemToStreamNetwork``, ``DemToDInfArea``,
+``DemToDInfWetness``, ``DemToDInfHAND``, ``DemToDInfDistanceUp`` and ``DemToMFDArea``, shaped
+like every other ``Filter``.
 
 Module namespace.  The reference's ``custom_filters`` is also where its callers
 pick up the element-wise and SciPy wrappers (`image_srtm.py:7-8` takes
@@ -2499,6 +2500,130 @@ class DemToDInfHAND(ComposedFilter):  # pylint: disable=too-few-public-methods,t
                 self.filled, self.codes, self.accumulation, self.words = filled, codes, acc, words
                 stack.pop_all()                     # the caller's to free from here on
             return hand
+
+
+class DInfDistanceUp(Filter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """D-infinity distance up to the ridge (new operator; TauDEM ``dinfdistup``).  Input: a
+    uint32 H x W raster of D-infinity words as ``DInfFlowDirection`` returns them.  Returns
+    float32: the distance from every cell up its D-infinity paths to the ridge.  A neighbour
+    *counts* as a donor of a cell when it sends the cell at least ``min_proportion`` of its flow;
+    a cell without such a neighbour is a ridge cell and reads 0.  A cell with one counted donor
+    adds the step to the donor's distance; a cell with several combines the sums by ``statistic``.
+    With ``DInfDistanceDown`` on the same words: hillslope length, and the slope position
+    ``down / (down + up)``.
+
+    ``kind``: ``"horizontal"`` (``dx`` / ``dy`` / the diagonal per step), ``"vertical"`` (the
+    rise ``dem[donor] - dem[c]`` per step) or ``"surface"`` (``sqrt(h^2 + v^2)`` per step); the
+    last two need ``dem``, a float32 array or ``DeviceRaster`` of the words' shape.
+    ``statistic``: ``"average"`` weights the counted donors by the shares they send to the cell,
+    normalised by their sum (this project's contract; not claimed to match TauDEM bit for bit);
+    ``"minimum"`` and ``"maximum"`` are the shortest and the longest way.  ``min_proportion``: a
+    number in (0, 1], 0.5 by default, compared as the integer ``min_share = max(1,
+    ceil(min_proportion * 32768))``; ``min_share=`` gives that integer itself, 1 ... 32768, and
+    not both.  ``cellsize``: a number or ``(dx, dy)``.  All arithmetic is float64 in a fixed
+    order, rounded to float32 once: identical from run to run.
+
+    ``ValueError`` for operands of another type, dtype or shape, an unknown ``kind`` or
+    ``statistic``, a ``dem`` that is missing or (horizontal) not wanted, a ``min_proportion`` or
+    ``min_share`` out of range or both of them, a ``cellsize`` that is not finite and positive
+    (all before the device is touched), an invalid word, a receiver outside the raster, a cycle
+    of counted links (only user-supplied words can form one) and more than 2^32 - 1 cells.
+
+    Attributes
+    ----------
+    stats : dict
+        ridge_cells, counted_links, ignored_links (below ``min_share``), merge_cells (more than
+        one counted donor), nan_cells, invalid, outside, unresolved, rounds and tile_visits
+        (these two depend on the schedule), tile_h / tile_w of the last call; phase times when
+        profiling is on.
+    """
+
+    auto_device = False     # the input is uint32 words, not a float32 raster
+
+    def __init__(self, kind="horizontal", statistic="average", dem=None, cellsize=1.0,
+                 min_proportion=None, *, min_share=None):
+        self.dem = _Given(dem, "dem", (np.float32,)).value
+        self.kind, self.statistic, self.cellsize = kind, statistic, cellsize
+        self.stats = {}
+        # everything but the shapes: 1 x 1 stand-ins for the words and the dem
+        self.min_share = _dinf.dinfdistup_args(
+            np.zeros((1, 1), np.uint32), _Given(self.dem).stand_in(), cellsize, kind, statistic,
+            min_proportion, min_share)[2]
+
+    def _check(self, words):
+        _dinf.dinfdistup_args(words, self.dem, self.cellsize, self.kind, self.statistic,
+                              min_share=self.min_share)
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        self._check(image_to_filter)
+        out, self.stats = _dinf.dinfdistup(
+            image_to_filter, _Given(self.dem).host(), self.cellsize, self.kind, self.statistic,
+            min_share=self.min_share)
+        return out
+
+    def apply_device(self, raster):
+        self._check(raster)
+        with _Given(self.dem).device(raster.ctx) as dem:
+            out, self.stats = _dinf.dinfdistup_dev(raster, dem, self.cellsize, self.kind,
+                                                   self.statistic, min_share=self.min_share)
+        return out
+
+
+class DemToDInfDistanceUp(ComposedFilter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """A float32 DEM to its D-infinity distance up to the ridge in one device-resident chain:
+    ``SinkFill(epsilon)`` and ``D8FlowDirection`` (one call, as in ``HydroConditioning``),
+    ``DInfFlowDirection`` on the **filled** DEM with the codes as fallback, then
+    ``DInfDistanceUp``, the vertical and surface kinds on the filled DEM.  Nothing is downloaded
+    in between.  ``flats`` as in ``DemToHAND``; ``kind``, ``statistic``, ``min_proportion`` /
+    ``min_share`` and ``cellsize`` as in ``DInfDistanceUp``.
+
+    ``stats`` maps ``SinkFill``, ``DInfFlowDirection`` and ``DInfDistanceUp`` (and
+    ``ResolveFlats``) to the stats of their stage.  With ``keep_partial_results=True`` the last
+    call leaves ``filled``, ``codes`` and ``words``: host arrays after ``apply``, device rasters
+    (the caller's to free) after ``apply_device``; otherwise they are ``None``."""
+
+    def __init__(self, *, kind="horizontal", statistic="average", min_proportion=None,
+                 min_share=None, epsilon=1e-3, flats="keep", cellsize=1.0,
+                 keep_partial_results=False):
+        super().__init__()
+        self.flats = _check_flats(flats)
+        # the checks of the distance's operands, on a stand-in of the dem the chain makes
+        stand_in = None if kind == "horizontal" else np.zeros((1, 1), np.float32)
+        self.min_share = DInfDistanceUp(kind, statistic, stand_in, cellsize, min_proportion,
+                                        min_share=min_share).min_share
+        self.filters = [SinkFill(epsilon=epsilon), D8FlowDirection(),
+                        DInfFlowDirection(cellsize=cellsize)]
+        self.kind, self.statistic, self.cellsize = kind, statistic, cellsize
+        self.keep_partial_results = keep_partial_results
+        self.stats = {}
+        self.filled = self.codes = self.words = None
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("DemToDInfDistanceUp", image_to_filter, np.float32, "a float32 DEM")
+        return _through_device(self, image_to_filter,
+                               ("filled", "codes", "words") if self.keep_partial_results else ())
+
+    def apply_device(self, raster):
+        _check_raster("DemToDInfDistanceUp", raster, np.float32, "a float32 DEM")
+        fill, _, direct = self.filters
+        self.filled = self.codes = self.words = None
+        with contextlib.ExitStack() as stack:
+            filled, codes, resolve_stats = _fill_d8(stack, raster, fill, self.flats)
+            words, _, direct.stats = _dinf.dinf_dev(filled, self.cellsize, codes)
+            stack.enter_context(words)
+            up, stats = _dinf.dinfdistup_dev(
+                words, None if self.kind == "horizontal" else filled, self.cellsize, self.kind,
+                self.statistic, min_share=self.min_share)
+            self.stats = {"SinkFill": fill.stats, "DInfFlowDirection": direct.stats,
+                          "DInfDistanceUp": stats}
+            if resolve_stats is not None:
+                self.stats["ResolveFlats"] = resolve_stats
+            if self.keep_partial_results:
+                self.filled, self.codes, self.words = filled, codes, words
+                stack.pop_all()                     # the caller's to free from here on
+            return up
 
 
 class MFDFlowDirection(Filter):  # pylint: disable=too-few-public-methods,too-many-instance-attributes

@@ -1774,6 +1774,93 @@ int hdem_dinfdist_u32(hdem_ctx *ctx, const uint32_t *words, int H, int W, const 
                       int kind, int statistic, float *distance, int flags,
                       hdem_dinfdist_stats *stats);
 
+/* ---- A27  DInfDistanceUp.apply  (new operator: D-infinity distance up to the ridge) ----
+ * TauDEM's dinfdistup: the distance from every cell up its D-infinity paths to the ridge,
+ * measured horizontally, vertically (the rise) or along the surface, and combined over the cells
+ * that drain into it as the average weighted by the entering flow proportions, the minimum or
+ * the maximum.  With A26 on the same words: hillslope length, slope position down / (down + up).
+ * words: uint32 H x W, the D-infinity words of A20, validated exactly as A21 and A26 validate
+ * them (the same refusals, the same counts).
+ * dem: float32 H x W; required for HDEM_DD_VERTICAL and HDEM_DD_SURFACE, NULL for
+ * HDEM_DD_HORIZONTAL.  dx, dy: the cell's extent eastwards and northwards, finite and > 0.
+ * kind and statistic: the HDEM_DD_* of A26.
+ *
+ * A donor of a cell c is an 8-neighbour d inside the raster whose word names c: as its cardinal
+ * receiver, with share p = 32768 - q, or as its diagonal receiver, with share p = q, in units of
+ * 2^-15; a share of 0 is no link.  A donor is COUNTED when p >= min_share, min_share an integer
+ * in 1 ... 32768: TauDEM's proportion threshold as an exact integer comparison, so that a cell
+ * which receives a sliver of dispersed flow is not taken to lie below its neighbour.  A cell
+ * without a counted donor is a ridge cell.
+ *
+ * All arithmetic is float64, one rounding per operation, no fused multiply-add.
+ *   c without a counted donor:    D[c] = 0
+ *   otherwise the counted donors are taken in the order of their position around c, A20's
+ *   direction numbering: 0 = E, counter-clockwise, to 7 = SE.  The step from d down to c costs
+ *     HDEM_DD_HORIZONTAL   h = dx (E, W), dy (N, S), or diag = sqrt(dx * dx + dy * dy) for the
+ *                          diagonal, which the host works out once
+ *     HDEM_DD_VERTICAL     v = (double)dem[d] - (double)dem[c]
+ *     HDEM_DD_SURFACE      sqrt(h * h + v * v)
+ *   and a_d = cost(d, c) + D[d].  Then
+ *     one counted donor:            D[c] = a_d: no product, no quotient
+ *     several, HDEM_DD_AVERAGE:     num = the sum, from left to right in that order, of
+ *                                   (double)p_d * a_d; den = (double)(the sum of the p_d, in
+ *                                   integers); D[c] = num / den.  NaN if any a_d is NaN
+ *     several, HDEM_DD_MAXIMUM:     NaN if any a_d is NaN, else the running a > m ? a : m in
+ *                                   that order, from m = the first a_d
+ *     several, HDEM_DD_MINIMUM:     over the a_d that are not NaN, the running a < m ? a : m in
+ *                                   that order, from m = the first of them; NaN if all are NaN
+ *   distance[c] = (float)D[c].  Every NaN is stored as the one canonical quiet NaN (float64
+ *   0x7FF8000000000000 on the way, float32 0x7FC00000 in distance): one NaN bit pattern.
+ * A NaN or infinite elevation goes through this arithmetic as it is.
+ * The average weighs each counted donor by the share it sends to c, normalised by the sum of the
+ * counted shares that enter c.  This weighting is this project's contract; it is not claimed to
+ * reproduce TauDEM's dinfdistup bit for bit.
+ *
+ * A cell's value is a function of its counted donors' final values alone, and which donors are
+ * counted follows from the words and min_share alone, so the result is the same bits from run
+ * to run, whatever the schedule, and between host and device pointers.  The scheme is A21's
+ * dependency on A26's values -- classify (words validated, links counted, the working raster
+ * set to "not final", every tile listed), rounds of tile visits (a 64 x 64 tile and its halo in
+ * LDS; each cell's counted donors as a bit mask; a cell without one becomes final with 0, a cell
+ * whose counted donors are all final becomes final; a tile runs again when one of its eight
+ * neighbours finalised a frame cell in the round before), a streaming pass that writes
+ * distance.  The host reads one word per round.  The working raster is one uint64 per cell (the
+ * bits of D; "not final" is a reserved NaN pattern no result is stored as): 8 B per cell of the
+ * context's arena beside 16 B per tile.
+ * One symbol, as A26: host pointers (staged through device buffers of the context, synchronous),
+ * or device pointers with HDEM_ON_DEVICE in flags.
+ * HDEM_ERR_BAD_ARG before any launch: a null context, words or distance, a dem missing (vertical,
+ * surface) or surplus (horizontal), an unknown kind, statistic or flag, min_share outside
+ * 1 ... 32768, dx or dy not finite and > 0, more than 2^32 - 1 cells, a distance that overlaps
+ * words or dem.  After classify, with the count in the text: an invalid word, a receiver outside
+ * the raster.  After the last round: a cycle of counted links, and every cell that waits on one
+ * ("N cells never resolve"; only user-supplied words can form one; the rounds are bounded by
+ * H * W + 1).  distance is unspecified then.
+ * stats may be NULL; otherwise the caller sets stats->struct_size = sizeof(hdem_dinfdistup_stats)
+ * first (104 bytes in this version; a shorter struct is filled as far as it goes).  rounds and
+ * tile_visits depend on the schedule; every other count does not. */
+typedef struct hdem_dinfdistup_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_dinfdistup_stats), set by the caller         */
+    int32_t rounds;          /* rounds of tile visits that had work                          */
+    int64_t tile_visits;     /* workgroups launched over all rounds                          */
+    int64_t ridge_cells;     /* cells without a counted donor: distance 0                    */
+    int64_t counted_links;   /* (donor, cell) links with share >= min_share                  */
+    int64_t ignored_links;   /* (donor, cell) links with share 1 ... min_share - 1           */
+    int64_t merge_cells;     /* cells with more than one counted donor                       */
+    int64_t nan_cells;       /* cells whose distance is NaN                                  */
+    int64_t invalid;         /* invalid words: refused                                       */
+    int64_t outside;         /* cells with a receiver outside the raster: refused            */
+    int64_t unresolved;      /* cells that never became final (a cycle of counted links): refused */
+    int32_t tile_h, tile_w;
+    float ms_classify;       /* (HIP events; profiling)                                      */
+    float ms_relax;          /* all rounds, the host reads included                          */
+    float ms_final;
+    int32_t reserved;        /* 0                                                            */
+} hdem_dinfdistup_stats;     /* sizeof == 104 */
+int hdem_dinfdistup_u32(hdem_ctx *ctx, const uint32_t *words, int H, int W, const float *dem,
+                        double dx, double dy, int kind, int statistic, uint32_t min_share,
+                        float *distance, int flags, hdem_dinfdistup_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
