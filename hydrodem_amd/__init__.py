@@ -37,6 +37,7 @@ from .filters.custom_filters import (QuadraticFilter, MaskTallGroves,  # noqa: F
                                      DInfDistanceUp, DemToDInfDistanceUp,
                                      MFDFlowDirection, MFDFlowAccumulation, DemToMFDArea,
                                      EuclideanDistance, EuclideanAllocation, BurnStreams,
+                                     CostDistance, CostAllocation, CostPath,
                                      ResolveFlats,
                                      Depressions, DepressionInventory,
                                      HydroConditioning, DemToHAND,

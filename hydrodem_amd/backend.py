@@ -272,6 +272,19 @@ class _DInfDistUpStats(_SizedStats):
                 ("ms_final", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class _CostDistanceStats(_SizedStats):
+    """``hdem_costdistance_stats`` (the binding is hydrodem_amd/costdistance.py)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("rounds", ctypes.c_int32),
+                ("tile_visits", ctypes.c_int64), ("sources", ctypes.c_int64),
+                ("barriers", ctypes.c_int64), ("unreached", ctypes.c_int64),
+                ("tie_cells", ctypes.c_int64), ("invalid", ctypes.c_int64),
+                ("max_units", ctypes.c_int64),
+                ("tile_h", ctypes.c_int32), ("tile_w", ctypes.c_int32),
+                ("ms_classify", ctypes.c_float), ("ms_relax", ctypes.c_float),
+                ("ms_final", ctypes.c_float), ("ms_trace", ctypes.c_float),
+                ("reserved", ctypes.c_int32 * 2)]
+
+
 class _MFDStats(_SizedStats):
     """``hdem_mfd_stats`` (the binding is hydrodem_amd/mfd.py)."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("ms_total", ctypes.c_float),
@@ -455,6 +468,9 @@ SIGNATURES = {
                           _i, _i, _vp, _i, _c.POINTER(_DInfDistStats)],
     "hdem_dinfdistup_u32": [_vp, _vp, _i, _i, _vp, _c.c_double, _c.c_double, _i, _i, _c.c_uint32,
                             _vp, _i, _c.POINTER(_DInfDistUpStats)],
+    "hdem_costdistance_f32": [_vp, _vp, _i, _i, _vp, _i, _c.c_uint32, _i, _c.c_double,
+                              _c.c_int64, _vp, _vp, _vp, _vp, _vp, _i,
+                              _c.POINTER(_CostDistanceStats)],
 }
 OTHER_SYMBOLS = {"hdem_last_error": _c.c_char_p, "hdem_version": _i}
 

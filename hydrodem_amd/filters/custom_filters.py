@@ -29,7 +29,8 @@ New operators (the reference has neither): ``SinkFill``,
 ``FlowPathSum``, ``FlowPathExtreme``, ``HeightAboveDrainage``, ``UpstreamFlowLength``,
 ``StreamOrder``, ``StreamNetwork``, ``DInfFlowDirection``, ``DInfFlowAccumulation``,
 ``WeightedDInfFlowAccumulation``, ``AreaWetnessIndex``, ``DInfDistanceDown``,
-``DInfHeightAboveDrainage``, ``DInfDistanceUp``, ``MFDFlowDirection``, ``MFDFlowAccumulation``
+``DInfHeightAboveDrainage``, ``DInfDistanceUp``, ``MFDFlowDirection``, ``MFDFlowAccumulation``,
+``CostDistance``, ``CostAllocation``, ``CostPath``
 and the chains ``DemToHAND``, ``DemToStreamOrder``, ``DemToStreamNetwork``, ``DemToDInfArea``,
 ``DemToDInfWetness``, ``DemToDInfHAND``, ``DemToDInfDistanceUp`` and ``DemToMFDArea``, shaped
 like every other ``Filter``.
@@ -74,6 +75,7 @@ from .. import upextreme as _upextreme
 from .. import flowpath as _flowpath
 from .. import dinf as _dinf
 from .. import mfd as _mfd
+from .. import costdistance as _costdistance
 
 
 def _check_raster(name, raster, dtype, takes):
@@ -1531,6 +1533,166 @@ class BurnStreams(_Proximity):  # pylint: disable=too-few-public-methods
         self._args(self.sources, "burned", raster)
         with _Given(self.sources).device(raster.ctx) as streams:
             return self._call(_proximity.proximity_dev, streams, "burned", raster)["burned"]
+
+
+class _CostFromSources(Filter):  # pylint: disable=too-few-public-methods
+    """What ``CostDistance`` and ``CostAllocation`` share: the operands of one
+    ``hdem_costdistance_f32`` call, checked as far as they can be before the shapes are known,
+    and the call on host arrays or device rasters.  Input: the float32 cost raster, the price per
+    cell length of crossing a cell; NaN is a barrier.  ``sources``: a bool / uint8 mask, a uint32
+    raster with ``threshold`` (source where ``>= threshold``) or a uint32 label raster without
+    one; array or ``DeviceRaster`` of the cost's shape.
+
+    Every cost is quantised once, ``q = rint(float64(cost) * 2^frac_bits)``, ``frac_bits``
+    0 ... 16, and must come to 1 ... 2^28 - 1.  A step between 8-neighbours ``a`` and ``b`` weighs
+    ``s = q(a) + q(b)`` units of ``cellsize * 2^-(frac_bits+1)``, a diagonal one
+    ``(s * 3037000500 + 2^30) >> 31``; cutting the corner of a barrier is legal.  The distance
+    ``D`` of a cell is the least sum over all paths to a source: integers, identical from run to
+    run and between ``apply`` and ``apply_device``.  Out of reach are barriers, cells with no
+    path, and cells beyond ``max_distance`` (in the units of the distance output).
+
+    ``ValueError`` (before the device is touched) for operands of another type, dtype or shape,
+    a ``threshold`` that does not go with the sources, ``frac_bits``, ``cellsize`` or
+    ``max_distance`` out of range and more than 2^32 - 1 cells; from the call for a negative or
+    infinite cost and one that quantises to 0 or to more than 2^28 - 1, with their count.
+
+    Attributes
+    ----------
+    stats : dict
+        sources (that are no barrier), barriers, unreached, tie_cells, invalid, max_units,
+        rounds and tile_visits (these two depend on the schedule), tile_h / tile_w of the last
+        call; ms_classify, ms_relax, ms_final and ms_trace when profiling is on.
+    """
+
+    auto_device = True      # device form == host form for a float32 raster
+    SOURCE_TYPES = (np.bool_, np.uint8, np.uint32)
+    OUTPUTS = ()
+
+    def __init__(self, sources, *, threshold=None, output=None, cellsize=1.0, frac_bits=16,
+                 max_distance=None):
+        name = type(self).__name__
+        if sources is None:
+            raise ValueError(f"{name} needs the sources it measures from (a mask, a uint32 "
+                             "raster with a threshold, or labels)")
+        self.sources = _Given(sources, "sources", self.SOURCE_TYPES).value
+        if output is None:
+            output = self._default_output(threshold)
+        if not isinstance(output, str) or output not in self.OUTPUTS:
+            raise ValueError(f"output is one of {list(self.OUTPUTS)}, got {output!r}")
+        self.threshold, self.output, self.cellsize = threshold, output, cellsize
+        self.frac_bits, self.max_distance = frac_bits, max_distance
+        self.stats = {}
+        # everything but the shapes, on 1 x 1 stand-ins
+        self._args(np.zeros((1, 1), np.float32), _Given(self.sources).stand_in())
+
+    def _default_output(self, threshold):
+        raise NotImplementedError
+
+    def _args(self, cost, sources):
+        _costdistance.costdistance_args(cost, sources, self.threshold, self.output,
+                                        self.cellsize, self.frac_bits, self.max_distance)
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        self._args(image_to_filter, self.sources)
+        outs, self.stats = _costdistance.costdistance(
+            image_to_filter, _Given(self.sources).host(), self.threshold, self.output,
+            self.cellsize, self.frac_bits, self.max_distance)
+        return outs[self.output]
+
+    def apply_device(self, raster):
+        self._args(raster, self.sources)
+        with _Given(self.sources).device(raster.ctx) as sources:
+            outs, self.stats = _costdistance.costdistance_dev(
+                raster, sources, self.threshold, self.output, self.cellsize, self.frac_bits,
+                self.max_distance)
+        return outs[self.output]
+
+
+class CostDistance(_CostFromSources):  # pylint: disable=too-few-public-methods
+    """Least accumulated cost to the nearest source (new operator; ArcGIS *Cost Distance* and
+    *Cost Back Link*, Whitebox ``CostDistance``, GRASS ``r.cost``).  Input, ``sources``,
+    arithmetic, errors and ``stats``: ``_CostFromSources``.  ``output``: ``"distance"`` float32
+    ``float32(float64(D) * cellsize * 2^-(frac_bits+1))``, NaN out of reach; ``"units"`` int64
+    ``D``, -1 out of reach; ``"backlink"`` uint8, the ESRI D8 code of the first neighbour in
+    window order (NW, N, NE, W, E, SW, S, SE) on a least path, 0 at sources and out of reach.
+    The back links are D8 codes whose paths end at sources: ``Watersheds``, ``FlowDistance``,
+    ``FlowPathSum``, ``WeightedFlowAccumulation`` and ``CostPath`` take them as they are."""
+
+    OUTPUTS = ("distance", "units", "backlink")
+
+    def _default_output(self, threshold):
+        return "distance"
+
+
+class CostAllocation(_CostFromSources):  # pylint: disable=too-few-public-methods
+    """The source every cell's least-cost path ends in (new operator; ArcGIS *Cost Allocation*,
+    Whitebox ``CostAllocation``).  Input, ``sources``, arithmetic, errors and ``stats``:
+    ``_CostFromSources``.  ``output``: ``"nearest"`` uint32, the flat index of the source the
+    back links of ``CostDistance`` lead to, 0xFFFFFFFF out of reach; ``"label"`` uint32, that
+    source's label, 0 out of reach (uint32 label sources only, where it is the default)."""
+
+    OUTPUTS = ("nearest", "label")
+
+    def _default_output(self, threshold):
+        labels = np.dtype(self.sources.dtype) == np.uint32 and threshold is None
+        return "label" if labels else "nearest"
+
+
+class CostPath(Filter):  # pylint: disable=too-few-public-methods
+    """Least-cost paths from destinations back to their sources (new operator; ArcGIS *Cost
+    Path*, Whitebox ``CostPathway``).  Input: the uint8 back-link raster of ``CostDistance``.
+    ``destinations``: a bool / uint8 mask of its shape (array or ``DeviceRaster``; non-zero = a
+    destination), or a list of ``(row, column)`` cells.  Returns a uint8 mask: 1 on every cell
+    of a back-link path from a destination to its source, both ends included; a destination out
+    of reach marks only itself.  It is ``WeightedFlowAccumulation`` on the back links with the
+    destinations as uint8 weights, written as its mask at threshold 1: exact, device-resident,
+    with that operator's errors and ``stats``."""
+
+    auto_device = True      # device form == host form for a uint8 code raster
+
+    def __init__(self, destinations):
+        if destinations is None:
+            raise ValueError("CostPath needs the destinations it starts from (a mask or a list "
+                             "of (row, column) cells)")
+        if isinstance(destinations, np.ndarray) or backend.is_device_raster(destinations):
+            self.cells = None
+            self.destinations = _Given(destinations, "destinations", (np.bool_, np.uint8)).value
+        else:
+            try:
+                cells = [(int(r), int(c)) for r, c in destinations]
+            except (TypeError, ValueError):
+                raise ValueError("destinations are a uint8 mask or a list of (row, column) "
+                                 f"cells, got {destinations!r}") from None
+            if not cells or any(r < 0 or c < 0 for r, c in cells):
+                raise ValueError("destinations are a uint8 mask or a list of (row, column) "
+                                 f"cells, got {destinations!r}")
+            self.cells, self.destinations = cells, None
+        self.stats = {}
+
+    def _mask(self, shape):
+        if self.cells is None:
+            return self.destinations
+        mask = np.zeros(shape, np.uint8)
+        for row, col in self.cells:
+            if row >= shape[0] or col >= shape[1]:
+                raise ValueError(f"destination ({row}, {col}) lies outside the {shape[0]} x "
+                                 f"{shape[1]} raster")
+            mask[row, col] = 1
+        return mask
+
+    def apply(self, image_to_filter):
+        Filter.apply(self, image_to_filter)
+        _check_raster("CostPath", image_to_filter, np.uint8, "uint8 back-link codes")
+        mask = _Given(self._mask(tuple(image_to_filter.shape))).host()
+        outs, self.stats = _flowsum.flowsum(image_to_filter, mask, 0, "mask", 1)
+        return outs["mask"]
+
+    def apply_device(self, raster):
+        _check_raster("CostPath", raster, np.uint8, "uint8 back-link codes")
+        with _Given(self._mask(tuple(raster.shape))).device(raster.ctx) as mask:
+            outs, self.stats = _flowsum.flowsum_dev(raster, mask, 0, "mask", 1)
+        return outs["mask"]
 
 
 class ResolveFlats(Filter):  # pylint: disable=too-few-public-methods

@@ -1861,6 +1861,90 @@ int hdem_dinfdistup_u32(hdem_ctx *ctx, const uint32_t *words, int H, int W, cons
                         double dx, double dy, int kind, int statistic, uint32_t min_share,
                         float *distance, int flags, hdem_dinfdistup_stats *stats);
 
+/* ---- A28  CostDistance.apply / CostAllocation.apply  (new operator: cost distance, back link,
+ *           allocation) ----
+ * ArcGIS Cost Distance / Cost Back Link / Cost Allocation, Whitebox CostDistance, GRASS r.cost:
+ * the least accumulated cost from every cell to a source set when crossing a cell has a price.
+ * Everything is integers after one rounding per cell, so the result is the same bytes from run to
+ * run, whatever the schedule, and between host and device pointers.
+ * cost: float32 H x W, the price per cell length of crossing the cell.
+ * sources, source_kind, threshold: the set S exactly as A15 takes it (HDEM_FT_STREAMS_MASK_U8,
+ * HDEM_FT_STREAMS_ACC_U32 with threshold >= 1, HDEM_PX_SOURCES_LABELS_U32).
+ * frac_bits: 0 ... 16.  cellsize: square cells, finite and > 0.  max_units: >= 0, 0 = no limit.
+ *
+ * Quantisation (A13's and A16's rule: the exact double product, rounded once to nearest even):
+ *   q(c) = (int64)rint((double)cost[c] * 2^frac_bits)
+ * A NaN cost is a BARRIER: the cell is not in the graph, even when it is in S.  A negative or
+ * infinite cost, q == 0 (a step costs at least 1, so distances strictly decrease along back
+ * links) and q > 2^28 - 1 (with H * W < 2^32 every path sum then stays below 2^62) are refused
+ * with their count.
+ * Graph: the non-barrier cells, 8-connected; a diagonal step needs only its two end cells
+ * (cutting the corner of a barrier is legal).  Step weights, symmetric, in units of
+ * 2^-(frac_bits+1) cost * cell, with s = q(a) + q(b) <= 2^29:
+ *   cardinal   w = s
+ *   diagonal   w = (s * 3037000500 + 2^30) >> 31 in uint64: s * sqrt(2) rounded to nearest with
+ *              the constant round(sqrt(2) * 2^31)
+ * D[c]: the least sum of step weights over all paths from c to a non-barrier cell of S; 0 there;
+ * "out of reach" at barriers, at cells with no path, and at cells with D > max_units when a limit
+ * is given (the search itself is not bounded by the limit).  D is the unique solution of
+ * D[src] = 0, D[c] = min over neighbours n of D[n] + w(c, n).
+ * Back link of a reached cell outside S: the ESRI code of the FIRST neighbour n in D8 window
+ * order (NW, N, NE, W, E, SW, S, SE) with D[n] + w(c, n) == D[c]; 0 in S and out of reach.  The
+ * tie rule is part of the contract.  D strictly decreases along back links: the codes are valid,
+ * acyclic A5 / A6 / A7 / A16 / A19 input whose paths end in S.
+ * Outputs, all H x W, each may be NULL, at least one must not be:       out of reach
+ *   units     int64    D                                                  -1
+ *   distance  float32  (float)((double)D * ldexp(cellsize, -(frac_bits+1)))  NaN (0x7FC00000)
+ *   backlink  uint8    as above                                           0
+ *   nearest   uint32   flat index of the cell of S the back-link path ends in   0xFFFFFFFF
+ *   label     uint32   sources[nearest]; HDEM_PX_SOURCES_LABELS_U32 only  0
+ * A subset of the outputs holds the bytes the call for all of them writes.
+ *
+ * The scheme is A8's with weights: classify (costs validated and counted, the working raster
+ * uint64 D = 0 in S, 2^64 - 1 elsewhere, the tiles that hold a source listed and, where one lies
+ * on the tile's frame, stamped so that the neighbours run in the next round), rounds of tile
+ * visits (a 64 x 64 tile and its halo in LDS, four directional sweeps racing through 64-bit LDS
+ * atomic min until the tile stops changing; a tile runs again when one of its eight neighbours
+ * changed a frame cell in the round before), a streaming pass that writes units, distance and
+ * backlink and checks the local equation at every non-barrier cell (HDEM_ERR_NOT_CONVERGED on a
+ * violation, or past H * W rounds), and -- only when nearest or label is wanted -- A7's trace
+ * (hdem_flowtrace_u8_dev) over the back links with S as its streams.  The host reads one word per
+ * round.  Workspace from the context's arena: 8 B per cell and 8 B per tile; with nearest or
+ * label A7's 8 B per cell more, 1 B per cell when backlink is not wanted, 4 B per cell when
+ * nearest is not.
+ * One symbol, as A24 - A27: host pointers (staged through device buffers of the context,
+ * synchronous), or device pointers with HDEM_ON_DEVICE in flags; any other flag is refused.
+ * HDEM_ERR_BAD_ARG before any allocation or launch: a null context, cost or sources, more than
+ * 2^32 - 1 cells, an unknown kind or a threshold that does not go with it, frac_bits outside
+ * 0 ... 16, cellsize not finite and > 0 when distance is wanted, max_units < 0, no output, label
+ * without label sources, an output that overlaps an input or another output, a stats struct_size
+ * of 0.  After the call's first synchronisation: "cost out of range in N cells: ...".
+ * stats may be NULL; otherwise the caller sets stats->struct_size =
+ * sizeof(hdem_costdistance_stats) first (96 bytes in this version; a shorter struct is filled as
+ * far as it goes).  rounds and tile_visits depend on the schedule; every other count does not. */
+typedef struct hdem_costdistance_stats {
+    uint32_t struct_size;    /* in: sizeof(hdem_costdistance_stats), set by the caller       */
+    int32_t rounds;          /* rounds of tile visits that had work                          */
+    int64_t tile_visits;     /* workgroups launched over all rounds                          */
+    int64_t sources;         /* cells of S that are no barrier                               */
+    int64_t barriers;        /* cells whose cost is NaN                                      */
+    int64_t unreached;       /* non-barrier cells out of reach                               */
+    int64_t tie_cells;       /* reached cells outside S where several neighbours attain D    */
+    int64_t invalid;         /* costs out of range: refused                                  */
+    int64_t max_units;       /* the largest D of a reached cell                              */
+    int32_t tile_h, tile_w;
+    float ms_classify;       /* (HIP events; profiling)                                      */
+    float ms_relax;          /* all rounds, the host reads included                          */
+    float ms_final;
+    float ms_trace;          /* 0 when neither nearest nor label is wanted                   */
+    int32_t reserved[2];     /* 0                                                            */
+} hdem_costdistance_stats;   /* sizeof == 96 */
+int hdem_costdistance_f32(hdem_ctx *ctx, const float *cost, int H, int W, const void *sources,
+                          int source_kind, uint32_t threshold, int frac_bits, double cellsize,
+                          int64_t max_units, int64_t *units, float *distance, uint8_t *backlink,
+                          uint32_t *nearest, uint32_t *label, int flags,
+                          hdem_costdistance_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
